@@ -18,6 +18,12 @@ A "step" is one pass of the hot path over the whole mesh, in one of three modes:
 
   python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run)
 
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, and the roofline of the
+same timed steps).  --full adds what takes work of its own: the CPU baseline (cpu_baseline, gpu_over_cpu and mode A's
+matrix_assembly) and, for N > 1, the same step on rank 0's GPU alone (same_step_one_gpu, exchange_checked).
+--dump-outputs DIR writes what the last timed step computed (Pipeline.outputs) as DIR/<name>.npy, float64, at most
+DUMP_BYTES in all: a larger output is cut to a fixed sample of its rows (dump_plan), the same in every run and build.
+
 Defaults: N = 1 -> the north-star target, 1024 x 1024, k = 2 (hho_degree_info(3, 2)), tensor Gauss, fancy stabilization,
 mode L.  N > 1 -> BASELINE.json's config 5, 2048 x 2048, k = 3, mode C, STRONG scaling: the cell rows are block-partitioned
 over the ranks, every rank assembles the CSR rows of the faces it owns, and the one exchange of a step is the packed
@@ -74,6 +80,44 @@ BASELINE_METRIC = 'cells assembled/sec (+ achieved HBM GB/s) on N×N quad mesh, 
 HBM_PEAK_GBS = 8000.0        # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 FP64_PEAK_TFLOPS = 78.6      # 256 CU x 4 SIMD x 16 FMA/clk x 2 x 2.4 GHz; v_mfma_f64_16x16x4_f64 measured at 64 clk = the same rate
 FP64_SUSTAINED_TFLOPS = 62.7  # measured on the box (tools/probe/valu_rate.hip): a wave64 v_fma_f64 every 2.09 ns per SIMD = 1.91 GHz sustained
+DUMP_BYTES = 64_000_000      # --dump-outputs: the most it writes, all files and ranks together
+DUMP_SEED = 20251016
+
+
+def dump_plan(shapes, budget):
+    """--dump-outputs: which rows (first index) of each output to write, within `budget` bytes of float64 files in all.
+    Every row when everything fits; otherwise the same fraction of every array's rows, one row drawn from each of that
+    many equal strata by numpy default_rng(DUMP_SEED) -- sorted, distinct, and the same from run to run and build to build
+    (arrays with as many rows get the same rows: lc and rhs of the same cells).
+    shapes: {name: shape}.  Returns {name: None (every row) or an int64 index array}."""
+    import numpy as np
+    header = 256                                               # bytes of one .npy header, rounded up
+    row_bytes = {k: 8 * int(np.prod(s[1:], dtype=np.int64)) for k, s in shapes.items()}
+    total = sum(s[0] * row_bytes[k] for k, s in shapes.items())
+    room = budget - header * len(shapes)
+    if total <= room:
+        return {k: None for k in shapes}
+    frac = (room - sum(row_bytes.values())) / total              # (keeping at least one row of each costs at most one row more)
+    plan = {}
+    for k, s in shapes.items():
+        rows = int(s[0])
+        keep = min(rows, max(1, int(rows * frac))) if rows else 0
+        edges = (np.arange(keep + 1, dtype=np.int64) * rows) // keep if keep else np.zeros(1, dtype=np.int64)
+        rng = np.random.default_rng(DUMP_SEED)
+        plan[k] = edges[:-1] + (rng.random(keep) * (edges[1:] - edges[:-1])).astype(np.int64)
+    return plan
+
+
+def dump_outputs(torch, outputs, directory, budget, suffix=""):
+    """write {name: device tensor} as directory/<name><suffix>.npy (float64), sampled by dump_plan within `budget`"""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    plan = dump_plan({k: tuple(t.shape) for k, t in outputs.items()}, budget)
+    for k, t in outputs.items():
+        idx = plan[k]
+        if idx is not None and len(idx) < t.shape[0]:
+            t = t.reshape(t.shape[0], -1).index_select(0, torch.from_numpy(idx).to(t.device)).reshape((len(idx),) + tuple(t.shape[1:]))
+        np.save(os.path.join(directory, k + suffix + ".npy"), t.to(torch.float64).cpu().numpy())
 
 
 def reference_flops_per_cell(w):
@@ -425,6 +469,24 @@ class Pipeline:
                 acc[b] = acc.get(b, 0.0) + ea.elapsed_time(eb)
         return {k: v / steps for k, v in acc.items()}
 
+    def outputs(self):
+        """what a caller of the step receives, by name, as the step leaves it in device memory (lc: one column-major
+        matrix per cell, the library's layout) -- the arrays --dump-outputs writes"""
+        asm = self.asm
+        if self.mode in ("L", "A"):
+            out = {"lc": self.lc, "rhs": self.rhs}
+            if self.cut and self.w.get("interface"):
+                out.update(cut_lc=self.cut_lc[:asm.ncut], cut_rhs=self.cut_rhs[:asm.ncut])     # the cut cells' two-sided operators
+            if self.mode == "A":
+                out.update(dirichlet=self.g, csr_values=self.values[:int(self.ainfo.nnz)], csr_rhs=self.b[:int(self.ainfo.nrows)])
+            return out
+        ci = self.ci
+        out = {"rhs": self.rhs, "records": self.rec, "csr_values": self.values[:int(ci.nnz_owned)],
+               "csr_rhs": self.b[:int(ci.row_end) - int(ci.row_begin)]}
+        if self.gather is not None:
+            out.update(all_csr_values=self.all_values, all_csr_rhs=self.all_b)
+        return out
+
     def check(self):
         """the timed work produced finite, non-trivial results (not a cached / skipped pass)"""
         torch = self.torch
@@ -495,12 +557,17 @@ def main():
                     help="N>1, mode C.  halo (default): the packed top-face rows of each slab, one slab up, are all that travels.  allgather: "
                          "behind it the north star's literal collective -- every rank all-gathers every rank's CSR values and right-hand "
                          "side (pa_comm_allgather_start) and ends the step holding the whole face-only system")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beyond the timed steps: the CPU baseline, and for N > 1 the same step on rank 0's GPU alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64, at most 64 MB in all; "
+                         "a fixed sample of the rows of larger outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--rccl-timeout", type=float, default=180.0,
                     help="N>1: seconds to wait for the RCCL communicator before the step falls back to the host-staged exchange")
     ap.add_argument("--settle-ms", type=float, default=250.0,
                     help="untimed passes of the step before the warmup steps, in ms of GPU work (clock ramp after idle); 0 = none")
-    ap.add_argument("--no-one-gpu-reference", action="store_true", help="N>1: skip the same step on rank 0's GPU alone")
+    ap.add_argument("--no-one-gpu-reference", action="store_true", help="N>1, with --full: skip the same step on rank 0's GPU alone")
     ap.add_argument("--cpu-sample-rows", type=int, default=0, help="cell rows timed by the CPU baseline (0 = auto)")
     args = ap.parse_args()
 
@@ -622,12 +689,14 @@ def main():
     else:
         kern_ms = stages["ops"] + stages.get("cut", 0.0) + stages.get("merge", 0.0)
     pipe.check()
+    if args.dump_outputs:
+        dump_outputs(torch, pipe.outputs(), args.dump_outputs, DUMP_BYTES // world, "" if world == 1 else "_rank%d" % rank)
 
-    # N > 1: the same step, same mode, same code, whole mesh, on rank 0's GPU alone (the other ranks wait): the
+    # N > 1, --full: the same step, same mode, same code, whole mesh, on rank 0's GPU alone (the other ranks wait): the
     # like-for-like one-GPU number of this run
     one_gpu = None
     exchange_checked = None
-    if world > 1 and not args.no_one_gpu_reference:
+    if world > 1 and args.full and not args.no_one_gpu_reference:
         ref_sums = None
         if rank == 0:
             ref = Pipeline(torch, pa, w, mode, (0, N), N, local_rank)
@@ -788,7 +857,7 @@ def main():
                                                                    what="the identical step (mode %s, whole mesh) on rank 0's GPU alone" % mode),
             "exchange_checked": exchange_checked,      # N > 1: sums of the ranks' CSR values / right-hand sides == the one-GPU reference's
         }
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # the CPU loop in the same run at every N (rank 0's host cores; the other ranks wait at the barrier below)
             res["cpu_baseline"] = cpu_baseline_cut(w) if pipe.cut else cpu_baseline(w, args.cpu_sample_rows)
             res["gpu_over_cpu"] = value / res["cpu_baseline"]["value"]
