@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define PA_ABI_VERSION 2
+#define PA_ABI_VERSION 3
 
 /* status codes (reference: C++ exceptions / silent NaNs) */
 enum {
@@ -492,6 +492,23 @@ int pa_interface_triplets_batch(pa_context *ctx, int face_deg, const double *d_l
 /* cell dofs read back by interface_assembler::take_local_data (:1356-1379): d_offsets ncells x 2 =
  * offset in the solution of the cell block of the negative / positive side (equal for uncut cells) */
 int pa_interface_cell_offsets(pa_context *ctx, int face_deg, int64_t *d_offsets);
+/* The same system -- what assemble / assemble_cut (:1203-1354) + finalize = setFromTriplets (:1437-1441) leave in `LHS` /
+ * `RHS` -- built DIRECTLY in CSR from the tables of pa_cut_preprocess: no triplets, no sort.  With pa_cut_interface_uncut_batch,
+ * pa_cut_interface_ops_batch and pa_conjugated_gradient it is the loop of run_cuthho_interface (:1664-1716) and its solve
+ * (:1737-1743) on the device.  Symbolic phase, once per cut mesh and face degree (kept by the context, rebuilt by the next
+ * pa_cut_preprocess or another face_deg): nrows = system_size, nnz; d_rowptr nrows + 1 (int64), d_colind nnz (int32,
+ * ascending within a row; may be NULL).  Numeric phase, once per assembly: d_values nnz and d_RHS nrows (may be NULL) from
+ * d_lc / d_rhs (ncells x msize^2 / ncells x cbs, pa_cut_interface_uncut_batch; rows of cut cells unused; d_rhs may be NULL),
+ * d_g (pa_dirichlet_data_batch or NULL) and d_lc_cut / d_rhs_cut (ncut x (2msize)^2 / ncut x 2cbs,
+ * pa_cut_interface_ops_batch; d_rhs_cut may be NULL).  Local matrices column-major.  Structure and values bit-identical to
+ * pa_csr_from_triplets of pa_interface_triplets_batch's slots taken in cell order (a cut cell's block in place of its
+ * uncut one); d_RHS the scatter-add of its d_rhs_vals / d_rhs_vals_cut in the same order.  Refuses what
+ * pa_interface_triplets_batch refuses (face_deg 0..3, whole-mesh cut contexts, system_size < 2^31, d_lc_cut when ncut > 0);
+ * joins pending side-stream work (pa_context_set_cut_overlap) first. */
+int pa_interface_csr_query(pa_context *ctx, int face_deg, pa_assembler_csr_info *out);
+int pa_interface_csr_pattern(pa_context *ctx, int face_deg, int64_t *d_rowptr, int32_t *d_colind);
+int pa_interface_csr_fill(pa_context *ctx, int face_deg, const double *d_lc, const double *d_rhs, const double *d_g,
+                          const double *d_lc_cut, const double *d_rhs_cut, double *d_values, double *d_RHS);
 
 /* ---- multi-GPU exchange: one process per GPU, RCCL over xGMI ------------
  * The reference is a single process without any communication.  Cells shard by rows (pa_mesh_generate's

@@ -417,6 +417,25 @@ class BatchAssembler:
                                     t["rhs_vals_cut"].data_ptr())
         return t
 
+    def interface_csr_pattern(self, fd):
+        """interface_assembler's system directly in CSR, symbolic phase -> (rowptr int64 [nrows+1], colind int32 [nnz])"""
+        info = self.ctx.interface_csr_query(fd)
+        rowptr = torch.empty(info.nrows + 1, dtype=torch.int64, device=self.device)
+        colind = torch.empty(max(info.nnz, 1), dtype=torch.int32, device=self.device)
+        self.ctx.interface_csr_pattern(fd, rowptr.data_ptr(), colind.data_ptr())
+        return rowptr, colind[:info.nnz]
+
+    def interface_csr_fill(self, fd, ops, g=None, values=None, RHS=None):
+        """numeric phase of the same from interface_local_ops' dict -> (values [nnz], RHS [nrows])"""
+        info = self.ctx.interface_csr_query(fd)
+        if values is None:
+            values = torch.empty(max(info.nnz, 1), dtype=torch.float64, device=self.device)
+        if RHS is None:
+            RHS = torch.empty(max(info.nrows, 1), dtype=torch.float64, device=self.device)
+        self.ctx.interface_csr_fill(fd, ops["lc"].data_ptr(), _ptr(ops.get("rhs")), _ptr(g), _ptr(ops.get("lc_cut")),
+                                    _ptr(ops.get("rhs_cut")), values.data_ptr(), RHS.data_ptr())
+        return values[:info.nnz], RHS[:info.nrows]
+
     def interface_cell_offsets(self, fd):
         out = torch.empty((self.ncells, 2), dtype=torch.int64, device=self.device)
         self.ctx.interface_cell_offsets(fd, out.data_ptr())

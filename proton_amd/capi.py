@@ -33,6 +33,7 @@ EXPORTS = [
     "pa_cut_preprocess_agglomeration", "pa_cut_agglo_query", "pa_cut_query_tags", "pa_cut_quadrature_points", "pa_cut_rhs_sampled_batch",
     "pa_cut_interface_ops_batch", "pa_cut_interface_uncut_batch", "pa_interface_assembler_query",
     "pa_interface_triplets_batch", "pa_interface_cell_offsets",
+    "pa_interface_csr_query", "pa_interface_csr_pattern", "pa_interface_csr_fill",
     "pa_condensed_ops_batch", "pa_condensed_recover_batch", "pa_condensed_query", "pa_condensed_triplets_batch",
     "pa_assembler_csr_query", "pa_assembler_csr_pattern", "pa_assembler_csr_fill",
     "pa_condensed_csr_pattern", "pa_condensed_csr_fill", "pa_condensed_halo_pack", "pa_condensed_take_faces",
@@ -194,6 +195,9 @@ def lib():
     L.pa_interface_assembler_query.argtypes = [vp, C.c_int, C.POINTER(InterfaceInfo)]
     L.pa_interface_triplets_batch.argtypes = [vp, C.c_int] + [dp] * 15
     L.pa_interface_cell_offsets.argtypes = [vp, C.c_int, dp]
+    L.pa_interface_csr_query.argtypes = [vp, C.c_int, C.POINTER(AssemblerCsrInfo)]
+    L.pa_interface_csr_pattern.argtypes = [vp, C.c_int, dp, dp]
+    L.pa_interface_csr_fill.argtypes = [vp, C.c_int] + [dp] * 7
     L.pa_condensed_ops_batch.argtypes = [vp, DegreeInfo, C.c_int, C.c_int, sz, sz, dp, dp, dp]
     L.pa_condensed_recover_batch.argtypes = [vp, DegreeInfo, C.c_int, C.c_int, sz, sz, dp, dp, dp, dp]
     L.pa_condensed_query.argtypes = [vp, DegreeInfo, C.POINTER(CondensedInfo)]
@@ -499,6 +503,17 @@ class Context:
 
     def interface_cell_offsets(self, face_deg, out):
         self._ck(self._L.pa_interface_cell_offsets(self.h, face_deg, out), "pa_interface_cell_offsets")
+
+    def interface_csr_query(self, face_deg):
+        out = AssemblerCsrInfo()
+        self._ck(self._L.pa_interface_csr_query(self.h, face_deg, C.byref(out)), "pa_interface_csr_query")
+        return out
+
+    def interface_csr_pattern(self, face_deg, rowptr, colind):
+        self._ck(self._L.pa_interface_csr_pattern(self.h, face_deg, rowptr, colind), "pa_interface_csr_pattern")
+
+    def interface_csr_fill(self, face_deg, lc, rhs, g, lc_cut, rhs_cut, values, RHS):
+        self._ck(self._L.pa_interface_csr_fill(self.h, face_deg, lc, rhs, g, lc_cut, rhs_cut, values, RHS), "pa_interface_csr_fill")
 
     def cut_preprocess(self, Nx, Ny, ls, refsteps, lo=(0.0, 0.0), hi=(1.0, 1.0), rows=None):
         if rows is None:

@@ -15,6 +15,7 @@
 #include "cut_interface_device.hpp"
 #include "condensed.hpp"
 #include "assembler_csr.hpp"
+#include "interface_csr.hpp"
 #include "cut_host.hpp"
 #include "hho_assembly.hpp"
 #include "hho_aux.hpp"
@@ -132,6 +133,9 @@ struct pa_context {
     // interface_assembler tables (cuthho_square.cpp:1137-1185)
     int32_t *d_if_cell_table = nullptr, *d_if_face_table = nullptr;
     size_t if_num_all_cells = 0, if_num_other_faces = 0;
+    // direct CSR of the interface_assembler's system (interface_csr.hip): row groups and column units of one face degree, built on
+    // first use, dropped with the cut mesh
+    pa::IfCsrTables ifcsr;
     // scratch of pa_cut_interface_ops_batch ([data | stab- | stab+] of the cut cells), kept between calls
     double *d_if_scratch = nullptr;
     size_t if_scratch_cap = 0;                // doubles
@@ -203,6 +207,7 @@ static void release_cut(pa_context *ctx)
     ctx->d_cut_cells = nullptr; ctx->d_cell_loc = nullptr; ctx->d_face_loc = nullptr; ctx->d_cut_index = nullptr;
     ctx->d_if_cell_table = ctx->d_if_face_table = nullptr;
     ctx->if_num_all_cells = ctx->if_num_other_faces = 0;
+    pa::ifcsr_release(&ctx->ifcsr);
 }
 
 static void release_mesh(pa_context *ctx)
@@ -2022,6 +2027,70 @@ int pa_interface_cell_offsets(pa_context *ctx, int face_deg, int64_t *d_offsets)
     }
     PA_HIP(ctx, hipMemcpyAsync(d_offsets, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     PA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return PA_OK;
+}
+
+// ---- interface_assembler's system directly in CSR: interface_csr.hip -------------------------------------------------
+static pa::IfCsrMesh ifcsr_mesh(const pa_context *ctx)
+{
+    pa::IfCsrMesh m;
+    m.cell_faces = ctx->d_cell_faces; m.cell_loc = ctx->d_cell_loc; m.face_loc = ctx->d_face_loc; m.cut_index = ctx->d_cut_index;
+    m.cell_table = ctx->d_if_cell_table; m.face_table = ctx->d_if_face_table;
+    m.ncells = (uint32_t)ctx->ncells; m.nfaces = (uint32_t)ctx->cut->nfaces();
+    m.num_all_cells = (uint32_t)ctx->if_num_all_cells; m.num_other_faces = (uint32_t)ctx->if_num_other_faces;
+    return m;
+}
+
+// the refusals of pa_interface_triplets_batch, in its order (cut_arrays: the cut-cell inputs are present or not needed), then the
+// side stream joined and the symbolic tables of face_deg built if the context does not hold them
+static int ifcsr_prepare(pa_context *ctx, int face_deg, bool cut_arrays)
+{
+    (void)hipSetDevice(ctx->device);
+    if (face_deg < 0 || face_deg > 3) return PA_ERR_INVALID_DEGREE;
+    if (!ctx->cut || !ctx->d_cell_faces) return PA_ERR_NO_MESH;
+    if (!ctx->d_if_cell_table) {
+        ctx->last_error = "the interface_assembler's numbering covers the whole mesh: not available on a slab of pa_cut_preprocess_rows";
+        return PA_ERR_INVALID_ARG;
+    }
+    if (ctx->cut->cut_cells.size() && !cut_arrays) return PA_ERR_INVALID_ARG;
+    pa_interface_info info;
+    pa_interface_assembler_query(ctx, face_deg, &info);
+    if (info.system_size >= ((uint64_t)1 << 31)) return PA_ERR_INVALID_ARG;      // int32 column ids, as Eigen::Triplet's
+    if (ctx->side_pending) {                              // cut-cell work still out on the side stream
+        PA_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_side, 0));
+        ctx->side_pending = false;
+    }
+    if (ctx->ifcsr.groups == nullptr || ctx->ifcsr.face_deg != face_deg)
+        PA_HIP(ctx, pa::ifcsr_build(ctx->stream, ifcsr_mesh(ctx), face_deg, &ctx->ifcsr));
+    return PA_OK;
+}
+
+int pa_interface_csr_query(pa_context *ctx, int face_deg, pa_assembler_csr_info *out)
+{
+    if (!ctx || !out) return PA_ERR_INVALID_ARG;
+    const int st = ifcsr_prepare(ctx, face_deg, true);
+    if (st != PA_OK) return st;
+    out->nrows = ctx->ifcsr.nrows;
+    out->nnz = ctx->ifcsr.nnz;
+    return PA_OK;
+}
+
+int pa_interface_csr_pattern(pa_context *ctx, int face_deg, int64_t *d_rowptr, int32_t *d_colind)
+{
+    if (!ctx || !d_rowptr) return PA_ERR_INVALID_ARG;
+    const int st = ifcsr_prepare(ctx, face_deg, true);
+    if (st != PA_OK) return st;
+    PA_HIP(ctx, pa::ifcsr_pattern(ctx->stream, ifcsr_mesh(ctx), ctx->ifcsr, d_rowptr, d_colind));
+    return PA_OK;
+}
+
+int pa_interface_csr_fill(pa_context *ctx, int face_deg, const double *d_lc, const double *d_rhs, const double *d_g,
+                          const double *d_lc_cut, const double *d_rhs_cut, double *d_values, double *d_RHS)
+{
+    if (!ctx || !d_lc || !d_values) return PA_ERR_INVALID_ARG;
+    const int st = ifcsr_prepare(ctx, face_deg, d_lc_cut != nullptr);
+    if (st != PA_OK) return st;
+    PA_HIP(ctx, pa::ifcsr_fill(ctx->stream, ifcsr_mesh(ctx), ctx->ifcsr, d_lc, d_rhs, d_g, d_lc_cut, d_rhs_cut, d_values, d_RHS));
     return PA_OK;
 }
 

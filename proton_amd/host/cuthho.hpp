@@ -415,10 +415,62 @@ class interface_assembler {
         return ret;
     }
 
+    // :1437-1441: LHS.setFromTriplets (duplicates summed).  After assemble_all() the CSR was already built on the device.
     void finalize(void)
     {
+        if (device_csr_) { device_csr_ = false; return; }
         LHS.set_from_triplets(RHS.size(), triplets);
         triplets.clear();
+    }
+
+  private:
+    bool device_csr_ = false;
+
+  public:
+    // Batched equivalent of the whole loop of run_cuthho_interface (:1664-1716) with built-in source and Dirichlet functions:
+    // the uncut cells' operators (pa_cut_interface_uncut_batch), the cut cells' (pa_cut_interface_ops_batch), the Dirichlet data
+    // and the global system directly in CSR (pa_interface_csr_*), all on the device; LHS / RHS as assemble / assemble_cut +
+    // finalize leave them (a following finalize() is a no-op).
+    void assemble_all(const Mesh &msh, const params<T> &parms = params<T>(), int rhs_fn = PA_FN_SIN_SIN_RHS,
+                      int dirichlet_fn = PA_FN_SIN_SIN_SOL)
+    {
+        if (!msh.preprocessed) throw std::logic_error("cutHHO mesh not preprocessed");
+        for (size_t c = 0; c < msh.cells.size(); ++c) {                                  // :1304-1305, as assemble_cut
+            if (msh.cell_tags[c] != element_location::ON_INTERFACE) continue;
+            for (auto f : proton_amd::face_offsets(msh, msh.cells[c]))
+                if (face_table[f] < 0) throw std::invalid_argument("Dirichlet boundary on cut cell not supported.");
+        }
+        auto &dev = proton_amd::device::instance();
+        pa_sizes sz;
+        dev.check(pa_sizes_for(di.c_abi(), PA_QUAD_FAN, &sz), "pa_sizes_for");
+        const int fd = (int)di.face_degree();
+        const size_t n = msh.cells.size(), ncut = msh.num_cut_cells, ms = sz.msize, mm = ms * ms;
+        const pa_interface_params ip{parms.kappa_1, parms.kappa_2, parms.eta};
+        proton_amd::device_buffer<double> d_lc(n * mm), d_rhs(n * sz.cbs), d_lc_cut(4 * ncut * mm + 1), d_rhs_cut(2 * ncut * sz.cbs + 1),
+            d_g(msh.faces.size() * sz.fbs);
+        dev.check(pa_cut_interface_uncut_batch(dev.ctx(), fd, &ip, rhs_fn, d_lc.get(), d_rhs.get(), nullptr), "pa_cut_interface_uncut_batch");
+        if (ncut)
+            dev.check(pa_cut_interface_ops_batch(dev.ctx(), fd, &msh.level_set, &ip, rhs_fn, nullptr, nullptr, d_lc_cut.get(), d_rhs_cut.get(),
+                                                 nullptr), "pa_cut_interface_ops_batch");
+        dev.check(pa_dirichlet_data_batch(dev.ctx(), fd, dirichlet_fn, nullptr, d_g.get()), "pa_dirichlet_data_batch");
+        pa_assembler_csr_info info;
+        dev.check(pa_interface_csr_query(dev.ctx(), fd, &info), "pa_interface_csr_query");
+        if (info.nrows != RHS.size()) throw std::logic_error("interface_assembler::assemble_all: system size differs from the device's");
+        proton_amd::device_buffer<int64_t> d_rowptr(info.nrows + 1);
+        proton_amd::device_buffer<int32_t> d_colind(info.nnz + 1);
+        proton_amd::device_buffer<double> d_values(info.nnz + 1), d_RHS(info.nrows + 1);
+        dev.check(pa_interface_csr_pattern(dev.ctx(), fd, d_rowptr.get(), d_colind.get()), "pa_interface_csr_pattern");
+        dev.check(pa_interface_csr_fill(dev.ctx(), fd, d_lc.get(), d_rhs.get(), d_g.get(), ncut ? d_lc_cut.get() : nullptr,
+                                        ncut ? d_rhs_cut.get() : nullptr, d_values.get(), d_RHS.get()), "pa_interface_csr_fill");
+        LHS.nrows = LHS.ncols = info.nrows;
+        LHS.rowptr.resize(info.nrows + 1); LHS.colind.resize(info.nnz); LHS.values.resize(info.nnz);
+        d_rowptr.download(LHS.rowptr.data(), LHS.rowptr.size());
+        if (info.nnz) { d_colind.download(LHS.colind.data(), info.nnz); d_values.download(LHS.values.data(), info.nnz); }
+        std::vector<T> b(info.nrows);
+        if (info.nrows) d_RHS.download(b.data(), b.size());
+        for (size_t i = 0; i < b.size(); ++i) RHS[i] += b[i];
+        triplets.clear();
+        device_csr_ = true;
     }
 };
 
