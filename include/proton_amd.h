@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define PA_ABI_VERSION 3
+#define PA_ABI_VERSION 4
 
 /* status codes (reference: C++ exceptions / silent NaNs) */
 enum {
@@ -509,6 +509,48 @@ int pa_interface_csr_query(pa_context *ctx, int face_deg, pa_assembler_csr_info 
 int pa_interface_csr_pattern(pa_context *ctx, int face_deg, int64_t *d_rowptr, int32_t *d_colind);
 int pa_interface_csr_fill(pa_context *ctx, int face_deg, const double *d_lc, const double *d_rhs, const double *d_g,
                           const double *d_lc_cut, const double *d_rhs_cut, double *d_values, double *d_RHS);
+/* The same system after static condensation: the cell unknowns of every cell eliminated (each couples only inside its cell), the
+ * face unknowns left in interface_assembler's numbering without its cell blocks -- unknown k of face block b at
+ * (face_table[F] + b) * fbs + k (:1152-1185), system_size = fbs * num_other_faces.  nf = 4 fbs face unknowns per uncut cell,
+ * NF = 8 fbs per cut cell ([faces-, faces+] of pa_cut_interface_ops_batch).  Stands in for the assembly loop (:1664-1716), the
+ * solve (:1737-1743) and the cell part of take_local_data (:1356-1379): the face-only system goes to pa_conjugated_gradient,
+ * pa_interface_condensed_recover gives back the full solution vector.
+ *   _query: system_size, nnz, nf, NF and the doubles per uncut / cut record.
+ *   _ops_batch: records from the inputs of pa_interface_csr_fill.  d_cond ncells x cond_doubles laid out as [S of every cell |
+ *     g of every cell] (S the upper triangle of A_FF - A_FT A_TT^-1 A_TF, column-packed, nf(nf+1)/2; g = -A_FT A_TT^-1 f_T),
+ *     bit-identical to pa_static_condensation_packed_batch of d_lc / d_rhs (rows of cut cells computed, never read); d_cond_cut
+ *     ncut x cond_cut_doubles the same for the cut cells, computed in double-double (the cut cells' A_TT has condition numbers
+ *     to 1e8) and rounded once.  d_info (ncells) / d_info_cut (ncut), may be NULL: 200 + j + 1 for a failed pivot j, else 0.
+ *   _triplets_batch: the assembly of the records as triplets in the reference's push order (cells ascending, local row, local
+ *     column): d_rows / d_cols / d_vals ncells x nf^2 (cut cells: all -1), *_cut ncut x NF^2, d_rhs_rows / d_rhs_vals ncells x nf,
+ *     *_cut ncut x NF.  Dirichlet columns of uncut cells go to the right-hand side with d_g (g_i - sum_j S_ij u_D,j, as
+ *     pa_condensed_triplets_batch); a cut cell's slots on a Dirichlet face are dropped (pa_interface_triplets_batch).
+ *   _csr_pattern / _csr_fill: the same matrix directly in CSR (d_rowptr system_size + 1, d_colind nnz may be NULL; d_values nnz,
+ *     d_rhs system_size may be NULL), bit-identical to pa_csr_from_triplets of the triplets taken in cell order.  It is the
+ *     face-face block of pa_interface_csr_pattern with column ids shifted by cbs * num_all_cells.
+ *   _recover: u_T = A_TT^-1 (f_T - A_TF u_F) of every cell (cut cells in double-double) from the face-only solution d_xF and the
+ *     inputs of _ops_batch; d_full (pa_interface_assembler_query's system_size) is the full solution vector in the reference's
+ *     numbering: cell blocks at cell_table offsets, then d_xF -- what take_local_data and pa_interface_cell_offsets read.  u_F of
+ *     a Dirichlet face is d_g for an uncut cell, zero for a cut cell (its slots were dropped).
+ * All refuse what pa_interface_csr_* refuses, in its order (face_deg 0..3, whole-mesh cut contexts, system_size < 2^31, the
+ * cut-cell arrays when ncut > 0), and join pending side-stream work (pa_context_set_cut_overlap) first. */
+typedef struct {
+    uint64_t system_size, nnz;
+    int32_t nf, NF;                              /* face unknowns of an uncut / cut cell */
+    int32_t cond_doubles, cond_cut_doubles;      /* doubles per uncut / cut record */
+} pa_interface_condensed_info;
+int pa_interface_condensed_query(pa_context *ctx, int face_deg, pa_interface_condensed_info *out);
+int pa_interface_condensed_ops_batch(pa_context *ctx, int face_deg, const double *d_lc, const double *d_rhs, const double *d_lc_cut,
+                                     const double *d_rhs_cut, double *d_cond, double *d_cond_cut, int32_t *d_info, int32_t *d_info_cut);
+int pa_interface_condensed_triplets_batch(pa_context *ctx, int face_deg, const double *d_cond, const double *d_cond_cut, const double *d_g,
+                                          int32_t *d_rows, int32_t *d_cols, double *d_vals, int32_t *d_rows_cut, int32_t *d_cols_cut,
+                                          double *d_vals_cut, int32_t *d_rhs_rows, double *d_rhs_vals, int32_t *d_rhs_rows_cut,
+                                          double *d_rhs_vals_cut);
+int pa_interface_condensed_csr_pattern(pa_context *ctx, int face_deg, int64_t *d_rowptr, int32_t *d_colind);
+int pa_interface_condensed_csr_fill(pa_context *ctx, int face_deg, const double *d_cond, const double *d_cond_cut, const double *d_g,
+                                    double *d_values, double *d_rhs);
+int pa_interface_condensed_recover(pa_context *ctx, int face_deg, const double *d_lc, const double *d_rhs, const double *d_lc_cut,
+                                   const double *d_rhs_cut, const double *d_g, const double *d_xF, double *d_full);
 
 /* ---- multi-GPU exchange: one process per GPU, RCCL over xGMI ------------
  * The reference is a single process without any communication.  Cells shard by rows (pa_mesh_generate's

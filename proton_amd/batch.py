@@ -436,6 +436,66 @@ class BatchAssembler:
                                     _ptr(ops.get("rhs_cut")), values.data_ptr(), RHS.data_ptr())
         return values[:info.nnz], RHS[:info.nrows]
 
+    def interface_condensed_ops(self, fd, ops):
+        """static condensation of interface_local_ops' dict -> dict(cond [ncells * cond_doubles]: [S of every cell | g of every
+        cell], cond_cut [ncut * cond_cut_doubles] the same for the cut cells (double-double), info, info_cut)"""
+        qi = self.ctx.interface_condensed_query(fd)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        out = {"cond": torch.empty(max(self.ncells * qi.cond_doubles, 1), **f64),
+               "cond_cut": torch.empty(max(self.ncut * qi.cond_cut_doubles, 1), **f64),
+               "info": torch.empty(max(self.ncells, 1), **i32), "info_cut": torch.empty(max(self.ncut, 1), **i32)}
+        self.ctx.interface_condensed_ops(fd, ops["lc"].data_ptr(), _ptr(ops.get("rhs")), _ptr(ops.get("lc_cut")), _ptr(ops.get("rhs_cut")),
+                                         out["cond"].data_ptr(), out["cond_cut"].data_ptr(), out["info"].data_ptr(),
+                                         out["info_cut"].data_ptr())
+        out["cond"] = out["cond"][:self.ncells * qi.cond_doubles]
+        out["cond_cut"] = out["cond_cut"][:self.ncut * qi.cond_cut_doubles]
+        out["info"], out["info_cut"] = out["info"][:self.ncells], out["info_cut"][:self.ncut]
+        return out
+
+    def interface_condensed_triplets(self, fd, rec, g=None):
+        """the records' assembly as triplets in the reference's push order -> dict of device arrays (as interface_triplets)"""
+        nf, NF = 4 * (fd + 1), 8 * (fd + 1)
+        n, nc = self.ncut, self.ncells
+        i32 = dict(dtype=torch.int32, device=self.device)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        t = {"rows": torch.empty((nc, nf * nf), **i32), "cols": torch.empty((nc, nf * nf), **i32), "vals": torch.empty((nc, nf * nf), **f64),
+             "rows_cut": torch.empty((n, NF * NF), **i32), "cols_cut": torch.empty((n, NF * NF), **i32),
+             "vals_cut": torch.empty((n, NF * NF), **f64),
+             "rhs_rows": torch.empty((nc, nf), **i32), "rhs_vals": torch.empty((nc, nf), **f64),
+             "rhs_rows_cut": torch.empty((n, NF), **i32), "rhs_vals_cut": torch.empty((n, NF), **f64)}
+        self.ctx.interface_condensed_triplets(fd, rec["cond"].data_ptr(), rec["cond_cut"].data_ptr(), _ptr(g),
+                                              *[t[k].data_ptr() for k in ("rows", "cols", "vals", "rows_cut", "cols_cut", "vals_cut",
+                                                                          "rhs_rows", "rhs_vals", "rhs_rows_cut", "rhs_vals_cut")])
+        return t
+
+    def interface_condensed_csr_pattern(self, fd):
+        """the face-only system directly in CSR, symbolic phase -> (rowptr int64 [nrows+1], colind int32 [nnz])"""
+        qi = self.ctx.interface_condensed_query(fd)
+        rowptr = torch.empty(qi.system_size + 1, dtype=torch.int64, device=self.device)
+        colind = torch.empty(max(qi.nnz, 1), dtype=torch.int32, device=self.device)
+        self.ctx.interface_condensed_csr_pattern(fd, rowptr.data_ptr(), colind.data_ptr())
+        return rowptr, colind[:qi.nnz]
+
+    def interface_condensed_csr_fill(self, fd, rec, g=None, values=None, RHS=None):
+        """numeric phase of the same from interface_condensed_ops' dict -> (values [nnz], RHS [nrows])"""
+        qi = self.ctx.interface_condensed_query(fd)
+        if values is None:
+            values = torch.empty(max(qi.nnz, 1), dtype=torch.float64, device=self.device)
+        if RHS is None:
+            RHS = torch.empty(max(qi.system_size, 1), dtype=torch.float64, device=self.device)
+        self.ctx.interface_condensed_csr_fill(fd, rec["cond"].data_ptr(), _ptr(rec.get("cond_cut")), _ptr(g), values.data_ptr(),
+                                              RHS.data_ptr())
+        return values[:qi.nnz], RHS[:qi.system_size]
+
+    def interface_condensed_recover(self, fd, ops, xF, g=None):
+        """cell unknowns from the face-only solution -> the full solution vector in interface_assembler's numbering"""
+        info = self.ctx.interface_info(fd)
+        full = torch.empty(max(info.system_size, 1), dtype=torch.float64, device=self.device)
+        self.ctx.interface_condensed_recover(fd, ops["lc"].data_ptr(), _ptr(ops.get("rhs")), _ptr(ops.get("lc_cut")),
+                                             _ptr(ops.get("rhs_cut")), _ptr(g), xF.data_ptr(), full.data_ptr())
+        return full[:info.system_size]
+
     def interface_cell_offsets(self, fd):
         out = torch.empty((self.ncells, 2), dtype=torch.int64, device=self.device)
         self.ctx.interface_cell_offsets(fd, out.data_ptr())

@@ -34,6 +34,8 @@ EXPORTS = [
     "pa_cut_interface_ops_batch", "pa_cut_interface_uncut_batch", "pa_interface_assembler_query",
     "pa_interface_triplets_batch", "pa_interface_cell_offsets",
     "pa_interface_csr_query", "pa_interface_csr_pattern", "pa_interface_csr_fill",
+    "pa_interface_condensed_query", "pa_interface_condensed_ops_batch", "pa_interface_condensed_triplets_batch",
+    "pa_interface_condensed_csr_pattern", "pa_interface_condensed_csr_fill", "pa_interface_condensed_recover",
     "pa_condensed_ops_batch", "pa_condensed_recover_batch", "pa_condensed_query", "pa_condensed_triplets_batch",
     "pa_assembler_csr_query", "pa_assembler_csr_pattern", "pa_assembler_csr_fill",
     "pa_condensed_csr_pattern", "pa_condensed_csr_fill", "pa_condensed_halo_pack", "pa_condensed_take_faces",
@@ -85,6 +87,11 @@ class AssemblerInfo(C.Structure):
 
 class AssemblerCsrInfo(C.Structure):
     _fields_ = [("nrows", C.c_uint64), ("nnz", C.c_uint64)]
+
+
+class InterfaceCondensedInfo(C.Structure):
+    _fields_ = [("system_size", C.c_uint64), ("nnz", C.c_uint64), ("nf", C.c_int32), ("NF", C.c_int32),
+                ("cond_doubles", C.c_int32), ("cond_cut_doubles", C.c_int32)]
 
 
 class CondensedInfo(C.Structure):
@@ -198,6 +205,12 @@ def lib():
     L.pa_interface_csr_query.argtypes = [vp, C.c_int, C.POINTER(AssemblerCsrInfo)]
     L.pa_interface_csr_pattern.argtypes = [vp, C.c_int, dp, dp]
     L.pa_interface_csr_fill.argtypes = [vp, C.c_int] + [dp] * 7
+    L.pa_interface_condensed_query.argtypes = [vp, C.c_int, C.POINTER(InterfaceCondensedInfo)]
+    L.pa_interface_condensed_ops_batch.argtypes = [vp, C.c_int] + [dp] * 8
+    L.pa_interface_condensed_triplets_batch.argtypes = [vp, C.c_int] + [dp] * 13
+    L.pa_interface_condensed_csr_pattern.argtypes = [vp, C.c_int, dp, dp]
+    L.pa_interface_condensed_csr_fill.argtypes = [vp, C.c_int] + [dp] * 5
+    L.pa_interface_condensed_recover.argtypes = [vp, C.c_int] + [dp] * 7
     L.pa_condensed_ops_batch.argtypes = [vp, DegreeInfo, C.c_int, C.c_int, sz, sz, dp, dp, dp]
     L.pa_condensed_recover_batch.argtypes = [vp, DegreeInfo, C.c_int, C.c_int, sz, sz, dp, dp, dp, dp]
     L.pa_condensed_query.argtypes = [vp, DegreeInfo, C.POINTER(CondensedInfo)]
@@ -514,6 +527,28 @@ class Context:
 
     def interface_csr_fill(self, face_deg, lc, rhs, g, lc_cut, rhs_cut, values, RHS):
         self._ck(self._L.pa_interface_csr_fill(self.h, face_deg, lc, rhs, g, lc_cut, rhs_cut, values, RHS), "pa_interface_csr_fill")
+
+    def interface_condensed_query(self, face_deg):
+        out = InterfaceCondensedInfo()
+        self._ck(self._L.pa_interface_condensed_query(self.h, face_deg, C.byref(out)), "pa_interface_condensed_query")
+        return out
+
+    def interface_condensed_ops(self, face_deg, lc, rhs, lc_cut, rhs_cut, cond, cond_cut, info, info_cut):
+        self._ck(self._L.pa_interface_condensed_ops_batch(self.h, face_deg, lc, rhs, lc_cut, rhs_cut, cond, cond_cut, info, info_cut),
+                 "pa_interface_condensed_ops_batch")
+
+    def interface_condensed_triplets(self, face_deg, *ptrs):
+        self._ck(self._L.pa_interface_condensed_triplets_batch(self.h, face_deg, *ptrs), "pa_interface_condensed_triplets_batch")
+
+    def interface_condensed_csr_pattern(self, face_deg, rowptr, colind):
+        self._ck(self._L.pa_interface_condensed_csr_pattern(self.h, face_deg, rowptr, colind), "pa_interface_condensed_csr_pattern")
+
+    def interface_condensed_csr_fill(self, face_deg, cond, cond_cut, g, values, rhs):
+        self._ck(self._L.pa_interface_condensed_csr_fill(self.h, face_deg, cond, cond_cut, g, values, rhs), "pa_interface_condensed_csr_fill")
+
+    def interface_condensed_recover(self, face_deg, lc, rhs, lc_cut, rhs_cut, g, xF, full):
+        self._ck(self._L.pa_interface_condensed_recover(self.h, face_deg, lc, rhs, lc_cut, rhs_cut, g, xF, full),
+                 "pa_interface_condensed_recover")
 
     def cut_preprocess(self, Nx, Ny, ls, refsteps, lo=(0.0, 0.0), hi=(1.0, 1.0), rows=None):
         if rows is None:

@@ -2094,4 +2094,103 @@ int pa_interface_csr_fill(pa_context *ctx, int face_deg, const double *d_lc, con
     return PA_OK;
 }
 
+// ---- the interface problem condensed to its face unknowns: interface_condensed.hip ---------------------------------------
+// the refusals of pa_interface_csr_* (ifcsr_prepare), then the face groups' offsets of the face-only system
+static int ifcond_prepare(pa_context *ctx, int face_deg, bool cut_arrays)
+{
+    const int st = ifcsr_prepare(ctx, face_deg, cut_arrays);
+    if (st != PA_OK) return st;
+    PA_HIP(ctx, pa::ifcond_build(ctx->stream, ifcsr_mesh(ctx), &ctx->ifcsr));
+    return PA_OK;
+}
+
+static pa::IfCondArgs ifcond_args(const pa_context *ctx, const double *d_cond, const double *d_cond_cut, const double *d_g)
+{
+    pa::IfCondArgs a;
+    a.cond = d_cond; a.cond_cut = d_cond_cut; a.g = d_g; a.cut_cells = ctx->d_cut_cells;
+    a.ncut = (uint32_t)ctx->cut->cut_cells.size();
+    return a;
+}
+
+int pa_interface_condensed_query(pa_context *ctx, int face_deg, pa_interface_condensed_info *out)
+{
+    if (!ctx || !out) return PA_ERR_INVALID_ARG;
+    const int st = ifcond_prepare(ctx, face_deg, true);
+    if (st != PA_OK) return st;
+    const int fbs = face_deg + 1, nf = 4 * fbs, NF = 8 * fbs;
+    out->system_size = (uint64_t)fbs * ctx->if_num_other_faces;
+    out->nnz = ctx->ifcsr.cnnz;
+    out->nf = nf;
+    out->NF = NF;
+    out->cond_doubles = nf * (nf + 1) / 2 + nf;
+    out->cond_cut_doubles = NF * (NF + 1) / 2 + NF;
+    return PA_OK;
+}
+
+int pa_interface_condensed_ops_batch(pa_context *ctx, int face_deg, const double *d_lc, const double *d_rhs, const double *d_lc_cut,
+                                     const double *d_rhs_cut, double *d_cond, double *d_cond_cut, int32_t *d_info, int32_t *d_info_cut)
+{
+    if (!ctx || !d_lc || !d_cond) return PA_ERR_INVALID_ARG;
+    const int st = ifcond_prepare(ctx, face_deg, d_lc_cut != nullptr && d_cond_cut != nullptr);
+    if (st != PA_OK) return st;
+    const size_t n = ctx->ncells, ncut = ctx->cut->cut_cells.size();
+    const int nf = 4 * (face_deg + 1), ntri = nf * (nf + 1) / 2;
+    const pa_degree_info di = {face_deg + 1, face_deg, face_deg + 1};
+    // the uncut cells: the plain mesh's static condensation of every row of d_lc (rows of cut cells included, never read back)
+    const int sc = condense(ctx, di, n, d_lc, d_rhs, d_cond, d_cond + n * (size_t)ntri, nullptr, d_info, 1);
+    if (sc != PA_OK) return sc;
+    PA_HIP(ctx, pa::ifcond_info_remap(ctx->stream, n, d_info));
+    if (ncut) {
+        const size_t blocks = (size_t)ctx->num_cus * 8;
+        PA_HIP(ctx, pa::ifcond_cut_records(ctx->stream, face_deg, (int)blocks, (uint32_t)ncut, d_lc_cut, d_rhs_cut, d_cond_cut, d_info_cut));
+    }
+    return PA_OK;
+}
+
+int pa_interface_condensed_triplets_batch(pa_context *ctx, int face_deg, const double *d_cond, const double *d_cond_cut, const double *d_g,
+                                          int32_t *d_rows, int32_t *d_cols, double *d_vals, int32_t *d_rows_cut, int32_t *d_cols_cut,
+                                          double *d_vals_cut, int32_t *d_rhs_rows, double *d_rhs_vals, int32_t *d_rhs_rows_cut,
+                                          double *d_rhs_vals_cut)
+{
+    if (!ctx || !d_cond || !d_rows || !d_cols || !d_vals || !d_rhs_rows || !d_rhs_vals) return PA_ERR_INVALID_ARG;
+    const bool cut_arrays = d_cond_cut && d_rows_cut && d_cols_cut && d_vals_cut && d_rhs_rows_cut && d_rhs_vals_cut;
+    const int st = ifcsr_prepare(ctx, face_deg, cut_arrays);
+    if (st != PA_OK) return st;
+    pa::IfCondTriplets o;
+    o.rows = d_rows; o.cols = d_cols; o.vals = d_vals; o.rows_cut = d_rows_cut; o.cols_cut = d_cols_cut; o.vals_cut = d_vals_cut;
+    o.rhs_rows = d_rhs_rows; o.rhs_vals = d_rhs_vals; o.rhs_rows_cut = d_rhs_rows_cut; o.rhs_vals_cut = d_rhs_vals_cut;
+    PA_HIP(ctx, pa::ifcond_triplets(ctx->stream, ifcsr_mesh(ctx), face_deg, ctx->num_cus * 8, ifcond_args(ctx, d_cond, d_cond_cut, d_g), o));
+    return PA_OK;
+}
+
+int pa_interface_condensed_csr_pattern(pa_context *ctx, int face_deg, int64_t *d_rowptr, int32_t *d_colind)
+{
+    if (!ctx || !d_rowptr) return PA_ERR_INVALID_ARG;
+    const int st = ifcond_prepare(ctx, face_deg, true);
+    if (st != PA_OK) return st;
+    PA_HIP(ctx, pa::ifcond_pattern(ctx->stream, ifcsr_mesh(ctx), ctx->ifcsr, d_rowptr, d_colind));
+    return PA_OK;
+}
+
+int pa_interface_condensed_csr_fill(pa_context *ctx, int face_deg, const double *d_cond, const double *d_cond_cut, const double *d_g,
+                                    double *d_values, double *d_rhs)
+{
+    if (!ctx || !d_cond || !d_values) return PA_ERR_INVALID_ARG;
+    const int st = ifcond_prepare(ctx, face_deg, d_cond_cut != nullptr);
+    if (st != PA_OK) return st;
+    PA_HIP(ctx, pa::ifcond_fill(ctx->stream, ifcsr_mesh(ctx), ctx->ifcsr, ifcond_args(ctx, d_cond, d_cond_cut, d_g), d_values, d_rhs));
+    return PA_OK;
+}
+
+int pa_interface_condensed_recover(pa_context *ctx, int face_deg, const double *d_lc, const double *d_rhs, const double *d_lc_cut,
+                                   const double *d_rhs_cut, const double *d_g, const double *d_xF, double *d_full)
+{
+    if (!ctx || !d_lc || !d_xF || !d_full) return PA_ERR_INVALID_ARG;
+    const int st = ifcsr_prepare(ctx, face_deg, d_lc_cut != nullptr);
+    if (st != PA_OK) return st;
+    PA_HIP(ctx, pa::ifcond_recover(ctx->stream, ifcsr_mesh(ctx), face_deg, ctx->num_cus * 16, ifcond_args(ctx, nullptr, nullptr, d_g), d_lc,
+                                   d_rhs, d_lc_cut, d_rhs_cut, d_xF, d_full));
+    return PA_OK;
+}
+
 }  // extern "C"

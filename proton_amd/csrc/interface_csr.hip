@@ -34,13 +34,6 @@ constexpr int IFC_MAX_UNITS = 2 * IFC_MAX_CELL_UNITS;
 
 inline unsigned blocks_for(size_t n) { return (unsigned)(n ? (n + 255) / 256 : 1); }
 
-// 16-bit code of at most two local indices (ascending): count in bits 0-1, first in bits 2-8, second in bits 9-15
-__host__ __device__ __forceinline__ uint32_t ifc_code1(int a) { return 1u | ((uint32_t)a << 2); }
-__host__ __device__ __forceinline__ uint32_t ifc_code2(int a, int b) { return 2u | ((uint32_t)a << 2) | ((uint32_t)b << 9); }
-__device__ __forceinline__ int ifc_count(uint32_t c) { return (int)(c & 3u); }
-__device__ __forceinline__ int ifc_first(uint32_t c) { return (int)((c >> 2) & 127u); }
-__device__ __forceinline__ int ifc_second(uint32_t c) { return (int)((c >> 9) & 127u); }
-
 struct IfcDims {
     int cbs, fbs;
     uint32_t ngroups;
@@ -334,6 +327,7 @@ void ifcsr_release(IfCsrTables *t)
 {
     if (t->groups) (void)hipFree(t->groups);
     if (t->units) (void)hipFree(t->units);
+    if (t->cvstart) (void)hipFree(t->cvstart);
     *t = IfCsrTables();
 }
 

@@ -17,6 +17,13 @@ struct IfCsrMesh {
     uint32_t num_all_cells, num_other_faces;    // cell blocks / face blocks (cut elements counted twice)
 };
 
+// 16-bit code of at most two local indices (ascending): count in bits 0-1, first in bits 2-8, second in bits 9-15
+__host__ __device__ __forceinline__ uint32_t ifc_code1(int a) { return 1u | ((uint32_t)a << 2); }
+__host__ __device__ __forceinline__ uint32_t ifc_code2(int a, int b) { return 2u | ((uint32_t)a << 2) | ((uint32_t)b << 9); }
+__device__ __forceinline__ int ifc_count(uint32_t c) { return (int)(c & 3u); }
+__device__ __forceinline__ int ifc_first(uint32_t c) { return (int)((c >> 2) & 127u); }
+__device__ __forceinline__ int ifc_second(uint32_t c) { return (int)((c >> 9) & 127u); }
+
 // A row group is one block of unknowns: a cell block (cbs rows) or a face block (fbs rows).  Every row of a group has the same
 // columns, a sorted run of units (a unit is one whole block of columns).  `cell` lists the (at most two) cells that push rows
 // into the group, lower id first; rcode[s] packs their local row bases (see ifc_code in interface_csr.hip).
@@ -41,6 +48,10 @@ struct IfCsrTables {
     uint32_t ngroups = 0, nunits = 0;
     IfGroup *groups = nullptr;
     IfUnit *units = nullptr;
+    // the face-only (condensed) system of the same numbering (interface_condensed.hip), built on first use: first entry of every
+    // face group's rows (num_other_faces + 1) and the total
+    uint64_t *cvstart = nullptr;
+    uint64_t cnnz = 0;
 };
 
 // builds *t (freeing what it holds first); on failure every allocation is released and *t is left empty
@@ -49,5 +60,37 @@ void ifcsr_release(IfCsrTables *t);
 hipError_t ifcsr_pattern(hipStream_t stream, const IfCsrMesh &m, const IfCsrTables &t, int64_t *rowptr, int32_t *colind);
 hipError_t ifcsr_fill(hipStream_t stream, const IfCsrMesh &m, const IfCsrTables &t, const double *lc, const double *rhs, const double *g,
                       const double *lc_cut, const double *rhs_cut, double *values, double *RHS);
+
+// ---- the face-only system after static condensation (interface_condensed.hip) ------------------------------------------
+// Records: uncut cells [S packed (ncells x nf(nf+1)/2) | g (ncells x nf)], cut cells [S (ncut x NF(NF+1)/2) | g (ncut x NF)],
+// nf = 4 fbs, NF = 8 fbs; S the upper triangle of the Schur complement, column-packed.
+struct IfCondArgs {
+    const double *cond, *cond_cut;      // records
+    const double *g;                    // nfaces x fbs Dirichlet data or null
+    const uint32_t *cut_cells;          // ncut cell ids
+    uint32_t ncut;
+};
+// the face groups' entry offsets (t->cvstart, t->cnnz) if not built yet
+hipError_t ifcond_build(hipStream_t stream, const IfCsrMesh &m, IfCsrTables *t);
+hipError_t ifcond_pattern(hipStream_t stream, const IfCsrMesh &m, const IfCsrTables &t, int64_t *rowptr, int32_t *colind);
+hipError_t ifcond_fill(hipStream_t stream, const IfCsrMesh &m, const IfCsrTables &t, const IfCondArgs &a, double *values, double *RHS);
+// the cut cells' records in double-double (one wavefront per cut cell); info[cc] = 200 + j + 1 for a failed pivot j, else 0
+hipError_t ifcond_cut_records(hipStream_t stream, int face_deg, int max_blocks, uint32_t ncut, const double *lc_cut,
+                              const double *rhs_cut, double *cond_cut, int32_t *info);
+// the uncut cells' info of static_condensation_kernel (j + 1) in the same convention
+hipError_t ifcond_info_remap(hipStream_t stream, size_t n, int32_t *info);
+// triplets in the reference's push order: uncut slots ncells x nf^2 (cut cells: all -1), cut slots ncut x NF^2; right-hand side
+// slots ncells x nf / ncut x NF
+struct IfCondTriplets {
+    int32_t *rows, *cols; double *vals;
+    int32_t *rows_cut, *cols_cut; double *vals_cut;
+    int32_t *rhs_rows; double *rhs_vals;
+    int32_t *rhs_rows_cut; double *rhs_vals_cut;
+};
+hipError_t ifcond_triplets(hipStream_t stream, const IfCsrMesh &m, int face_deg, int max_blocks, const IfCondArgs &a, const IfCondTriplets &o);
+// u_T = A_TT^-1 (f_T - A_TF u_F) of every cell (cut cells in double-double) into the interface_assembler's full solution vector:
+// cell blocks at cell_table, then xF
+hipError_t ifcond_recover(hipStream_t stream, const IfCsrMesh &m, int face_deg, int max_blocks, const IfCondArgs &a, const double *lc,
+                          const double *rhs, const double *lc_cut, const double *rhs_cut, const double *xF, double *full);
 
 }  // namespace pa

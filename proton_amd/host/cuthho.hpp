@@ -472,6 +472,65 @@ class interface_assembler {
         triplets.clear();
         device_csr_ = true;
     }
+
+    // The same loop (:1664-1716) and its solve (:1737-1743) with the cell unknowns eliminated on the device: the operators as
+    // assemble_all, the cells' static condensation (cut cells in double-double, pa_interface_condensed_ops_batch), the face-only
+    // system directly in CSR (pa_interface_condensed_csr_*), pa_conjugated_gradient on it and the cell unknowns recovered
+    // (pa_interface_condensed_recover).  Returns the full solution vector in the reference's numbering -- what
+    // conjugated_gradient(LHS, RHS, sol) leaves in `sol` -- for take_local_data; LHS / RHS are left untouched.
+    std::vector<T> solve_condensed(const Mesh &msh, const params<T> &parms, int rhs_fn, int dirichlet_fn, const cg_params<T> &cgp,
+                                   size_t *iterations = nullptr, cg_exit_reason *exit_reason = nullptr)
+    {
+        if (!msh.preprocessed) throw std::logic_error("cutHHO mesh not preprocessed");
+        for (size_t c = 0; c < msh.cells.size(); ++c) {                                  // :1304-1305, as assemble_cut
+            if (msh.cell_tags[c] != element_location::ON_INTERFACE) continue;
+            for (auto f : proton_amd::face_offsets(msh, msh.cells[c]))
+                if (face_table[f] < 0) throw std::invalid_argument("Dirichlet boundary on cut cell not supported.");
+        }
+        auto &dev = proton_amd::device::instance();
+        pa_sizes sz;
+        dev.check(pa_sizes_for(di.c_abi(), PA_QUAD_FAN, &sz), "pa_sizes_for");
+        const int fd = (int)di.face_degree();
+        const size_t n = msh.cells.size(), ncut = msh.num_cut_cells, ms = sz.msize, mm = ms * ms;
+        const pa_interface_params ip{parms.kappa_1, parms.kappa_2, parms.eta};
+        proton_amd::device_buffer<double> d_lc(n * mm), d_rhs(n * sz.cbs), d_lc_cut(4 * ncut * mm + 1), d_rhs_cut(2 * ncut * sz.cbs + 1),
+            d_g(msh.faces.size() * sz.fbs);
+        dev.check(pa_cut_interface_uncut_batch(dev.ctx(), fd, &ip, rhs_fn, d_lc.get(), d_rhs.get(), nullptr), "pa_cut_interface_uncut_batch");
+        if (ncut)
+            dev.check(pa_cut_interface_ops_batch(dev.ctx(), fd, &msh.level_set, &ip, rhs_fn, nullptr, nullptr, d_lc_cut.get(), d_rhs_cut.get(),
+                                                 nullptr), "pa_cut_interface_ops_batch");
+        dev.check(pa_dirichlet_data_batch(dev.ctx(), fd, dirichlet_fn, nullptr, d_g.get()), "pa_dirichlet_data_batch");
+        pa_interface_condensed_info info;
+        dev.check(pa_interface_condensed_query(dev.ctx(), fd, &info), "pa_interface_condensed_query");
+        if (info.system_size != numbering.fbs * num_other_faces)
+            throw std::logic_error("interface_assembler::solve_condensed: system size differs from the device's");
+        const double *lc_cut = ncut ? d_lc_cut.get() : nullptr, *rhs_cut = ncut ? d_rhs_cut.get() : nullptr;
+        proton_amd::device_buffer<double> d_cond(n * info.cond_doubles + 1), d_cond_cut(ncut * info.cond_cut_doubles + 1);
+        dev.check(pa_interface_condensed_ops_batch(dev.ctx(), fd, d_lc.get(), d_rhs.get(), lc_cut, rhs_cut, d_cond.get(),
+                                                   ncut ? d_cond_cut.get() : nullptr, nullptr, nullptr), "pa_interface_condensed_ops_batch");
+        const size_t nF = info.system_size;
+        proton_amd::device_buffer<int64_t> d_rowptr(nF + 1);
+        proton_amd::device_buffer<int32_t> d_colind(info.nnz + 1);
+        proton_amd::device_buffer<double> d_values(info.nnz + 1), d_b(nF + 1), d_xF(nF + 1), d_full(RHS.size() + 1);
+        dev.check(pa_interface_condensed_csr_pattern(dev.ctx(), fd, d_rowptr.get(), d_colind.get()), "pa_interface_condensed_csr_pattern");
+        dev.check(pa_interface_condensed_csr_fill(dev.ctx(), fd, d_cond.get(), ncut ? d_cond_cut.get() : nullptr, d_g.get(), d_values.get(),
+                                                  d_b.get()), "pa_interface_condensed_csr_fill");
+        int32_t reason = 0;
+        size_t iters = 0;
+        double rr = 0.0;
+        dev.check(pa_conjugated_gradient(dev.ctx(), nF, d_rowptr.get(), d_colind.get(), d_values.get(), d_b.get(), d_xF.get(),
+                                         cgp.convergence_threshold, cgp.divergence_threshold, cgp.max_iter, cgp.apply_preconditioner ? 1 : 0,
+                                         &reason, &iters, &rr), "pa_conjugated_gradient");
+        if (cgp.verbose) std::cout << " -> Iteration " << iters << ", rr = " << rr << std::endl;
+        if (iterations) *iterations = iters;
+        if (exit_reason)
+            *exit_reason = reason == 0 ? cg_exit_reason::CONVERGED : reason == 1 ? cg_exit_reason::DIVERGED : cg_exit_reason::MAX_ITER_REACHED;
+        dev.check(pa_interface_condensed_recover(dev.ctx(), fd, d_lc.get(), d_rhs.get(), lc_cut, rhs_cut, d_g.get(), d_xF.get(), d_full.get()),
+                  "pa_interface_condensed_recover");
+        std::vector<T> sol(RHS.size());
+        if (!sol.empty()) d_full.download(sol.data(), sol.size());
+        return sol;
+    }
 };
 
 template <typename Mesh>
