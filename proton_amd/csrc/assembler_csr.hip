@@ -20,15 +20,12 @@
 // (tests/test_gpu_assembler.py); the right-hand side is the triplet path's per-row sums (:401, :405) added in cell order.
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include <cstdint>
 
 #include "assembler_csr.hpp"
+#include "device_tmp.hpp"
 
 namespace pa {
-
-static inline unsigned blocks_for(size_t n) { return (unsigned)((n + 255) / 256 ? (n + 255) / 256 : 1); }
 
 // ---- symbolic: per cell the number of its non-Dirichlet faces, per non-Dirichlet face the number of its cells ------------
 __global__ __launch_bounds__(256) void asm_counts_kernel(uint32_t ncells, uint32_t nown, const uint32_t *cell_faces,
@@ -51,22 +48,13 @@ hipError_t asm_build_tables(hipStream_t stream, const CondMesh &m, uint32_t ncel
     const uint32_t top = ncells > nown ? ncells : nown;
     hipLaunchKernelGGL(asm_counts_kernel, dim3(blocks_for((size_t)top + 1)), dim3(256), 0, stream, ncells, nown, m.cell_faces,
                        m.face_compress, lean, nfc, nfcell);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    size_t b1 = 0, b2 = 0;
-    e = rocprim::exclusive_scan(nullptr, b1, nfc, cprefix, 0u, (size_t)ncells + 1, rocprim::plus<uint32_t>(), stream);
-    if (e != hipSuccess) return e;
-    e = rocprim::exclusive_scan(nullptr, b2, nfcell, fprefix, 0u, (size_t)nown + 1, rocprim::plus<uint32_t>(), stream);
-    if (e != hipSuccess) return e;
-    void *tmp = nullptr;
-    const size_t tb = b1 > b2 ? b1 : b2;
-    e = hipMalloc(&tmp, tb ? tb : 1);
-    if (e != hipSuccess) return e;
-    e = rocprim::exclusive_scan(tmp, b1, nfc, cprefix, 0u, (size_t)ncells + 1, rocprim::plus<uint32_t>(), stream);
-    if (e == hipSuccess) e = rocprim::exclusive_scan(tmp, b2, nfcell, fprefix, 0u, (size_t)nown + 1, rocprim::plus<uint32_t>(), stream);
-    const hipError_t e2 = hipStreamSynchronize(stream);
-    (void)hipFree(tmp);
-    return e != hipSuccess ? e : e2;
+    DeviceTmp tmp(stream);
+    if (!tmp.ok(hipGetLastError()) ||
+        exclusive_scan_with_total<uint32_t>(stream, nfc, cprefix, (size_t)ncells + 1, tmp, nullptr) != hipSuccess ||
+        exclusive_scan_with_total<uint32_t>(stream, nfcell, fprefix, (size_t)nown + 1, tmp, nullptr) != hipSuccess)
+        return tmp.error();
+    tmp.ok(hipStreamSynchronize(stream));
+    return tmp.error();
 }
 
 // the non-Dirichlet faces of a cell in ascending compressed order: comp[s], local index lf[s], s < n

@@ -1954,20 +1954,58 @@ int pa_cut_interface_uncut_batch(pa_context *ctx, int face_deg, const pa_interfa
     return PA_OK;
 }
 
+// ---- interface_assembler's system: triplets, CSR (interface_csr.hip) and condensed to the faces (interface_condensed.hip) ----
+// the interface numbering is built by pa_cut_preprocess on whole-mesh contexts only
+static int if_numbering(pa_context *ctx)
+{
+    if (ctx->d_if_cell_table) return PA_OK;
+    ctx->last_error = "the interface_assembler's numbering covers the whole mesh: not available on a slab of pa_cut_preprocess_rows";
+    return PA_ERR_INVALID_ARG;
+}
+
+static pa::IfCsrMesh ifcsr_mesh(const pa_context *ctx)
+{
+    pa::IfCsrMesh m;
+    m.cell_faces = ctx->d_cell_faces; m.cell_loc = ctx->d_cell_loc; m.face_loc = ctx->d_face_loc; m.cut_index = ctx->d_cut_index;
+    m.cell_table = ctx->d_if_cell_table; m.face_table = ctx->d_if_face_table;
+    m.ncells = (uint32_t)ctx->ncells; m.nfaces = (uint32_t)ctx->cut->nfaces();
+    m.num_all_cells = (uint32_t)ctx->if_num_all_cells; m.num_other_faces = (uint32_t)ctx->if_num_other_faces;
+    return m;
+}
+
 int pa_interface_assembler_query(pa_context *ctx, int face_deg, pa_interface_info *out)
 {
     if (!ctx || !out || face_deg < 0 || face_deg > 3) return PA_ERR_INVALID_ARG;
     (void)hipSetDevice(ctx->device);
     if (!ctx->cut) return PA_ERR_NO_MESH;
-    if (!ctx->d_if_cell_table) {
-        ctx->last_error = "the interface_assembler's numbering covers the whole mesh: not available on a slab of pa_cut_preprocess_rows";
-        return PA_ERR_INVALID_ARG;
-    }
+    if (const int st = if_numbering(ctx)) return st;
     out->num_all_cells = ctx->if_num_all_cells;
     out->num_other_faces = ctx->if_num_other_faces;
     out->system_size = (uint64_t)pa::P2(face_deg + 1) * ctx->if_num_all_cells + (uint64_t)(face_deg + 1) * ctx->if_num_other_faces;
     out->ncut = ctx->cut->cut_cells.size();
     return PA_OK;
+}
+
+// the refusals every entry point of the interface system shares, in this order (cut_arrays: the cut-cell arrays are present or
+// not needed)
+static int if_refusals(pa_context *ctx, int face_deg, bool cut_arrays)
+{
+    (void)hipSetDevice(ctx->device);
+    if (face_deg < 0 || face_deg > 3) return PA_ERR_INVALID_DEGREE;
+    if (!ctx->cut || !ctx->d_cell_faces) return PA_ERR_NO_MESH;
+    if (const int st = if_numbering(ctx)) return st;
+    if (ctx->cut->cut_cells.size() && !cut_arrays) return PA_ERR_INVALID_ARG;
+    pa_interface_info info;
+    pa_interface_assembler_query(ctx, face_deg, &info);
+    if (info.system_size >= ((uint64_t)1 << 31)) return PA_ERR_INVALID_ARG;      // int32 indices, as Eigen::Triplet's
+    return PA_OK;
+}
+
+static pa::IfTriplets if_triplets(int32_t *d_rows, int32_t *d_cols, double *d_vals, int32_t *d_rows_cut, int32_t *d_cols_cut,
+                                  double *d_vals_cut, int32_t *d_rhs_rows, double *d_rhs_vals, int32_t *d_rhs_rows_cut,
+                                  double *d_rhs_vals_cut)
+{
+    return {d_rows, d_cols, d_vals, d_rows_cut, d_cols_cut, d_vals_cut, d_rhs_rows, d_rhs_vals, d_rhs_rows_cut, d_rhs_vals_cut};
 }
 
 int pa_interface_triplets_batch(pa_context *ctx, int face_deg, const double *d_lc, const double *d_rhs, const double *d_g,
@@ -1976,32 +2014,12 @@ int pa_interface_triplets_batch(pa_context *ctx, int face_deg, const double *d_l
                                 int32_t *d_rhs_rows, double *d_rhs_vals, int32_t *d_rhs_rows_cut, double *d_rhs_vals_cut)
 {
     if (!ctx || !d_lc || !d_rows || !d_cols || !d_vals || !d_rhs_rows || !d_rhs_vals) return PA_ERR_INVALID_ARG;
-    (void)hipSetDevice(ctx->device);
-    if (face_deg < 0 || face_deg > 3) return PA_ERR_INVALID_DEGREE;
-    if (!ctx->cut || !ctx->d_cell_faces) return PA_ERR_NO_MESH;
-    if (!ctx->d_if_cell_table) {
-        ctx->last_error = "the interface_assembler's numbering covers the whole mesh: not available on a slab of pa_cut_preprocess_rows";
-        return PA_ERR_INVALID_ARG;
-    }
-    const size_t ncut = ctx->cut->cut_cells.size();
-    if (ncut && (!d_lc_cut || !d_rows_cut || !d_cols_cut || !d_vals_cut || !d_rhs_rows_cut || !d_rhs_vals_cut)) return PA_ERR_INVALID_ARG;
-    pa_interface_info info;
-    pa_interface_assembler_query(ctx, face_deg, &info);
-    if (info.system_size >= ((uint64_t)1 << 31)) return PA_ERR_INVALID_ARG;      // Eigen::Triplet stores int indices
-    pa::InterfaceTripletArgs a;
-    a.cell_faces = ctx->d_cell_faces; a.cell_loc = ctx->d_cell_loc; a.face_loc = ctx->d_face_loc; a.cut_index = ctx->d_cut_index;
-    a.cell_table = ctx->d_if_cell_table; a.face_table = ctx->d_if_face_table; a.g = d_g;
-    a.lc = d_lc; a.rhs = d_rhs; a.lc_cut = d_lc_cut; a.rhs_cut = d_rhs_cut;
-    a.ncells = ctx->ncells; a.num_all_cells = ctx->if_num_all_cells;
-    a.cbs = pa::P2(face_deg + 1); a.fbs = face_deg + 1;
-    a.rows = d_rows; a.cols = d_cols; a.vals = d_vals; a.rows_cut = d_rows_cut; a.cols_cut = d_cols_cut; a.vals_cut = d_vals_cut;
-    a.rhs_rows = d_rhs_rows; a.rhs_vals = d_rhs_vals; a.rhs_rows_cut = d_rhs_rows_cut; a.rhs_vals_cut = d_rhs_vals_cut;
-    const int m2 = 2 * (a.cbs + 4 * a.fbs);
-    const size_t shmem = m2 * sizeof(double) + m2 * sizeof(int32_t);
-    const size_t resident = (size_t)ctx->num_cus * 8;
-    const int grid = (int)(ctx->ncells < resident ? ctx->ncells : resident);
-    hipLaunchKernelGGL(pa::interface_triplets_kernel, dim3(grid), dim3(256), shmem, ctx->stream, a);
-    PA_HIP(ctx, hipGetLastError());
+    const bool cut_arrays = d_lc_cut && d_rows_cut && d_cols_cut && d_vals_cut && d_rhs_rows_cut && d_rhs_vals_cut;
+    const int st = if_refusals(ctx, face_deg, cut_arrays);            // no symbolic tables: the triplets need the mesh alone
+    if (st != PA_OK) return st;
+    PA_HIP(ctx, pa::ifcsr_triplets(ctx->stream, ifcsr_mesh(ctx), face_deg, ctx->num_cus * 8, {d_lc, d_rhs, d_g, d_lc_cut, d_rhs_cut},
+                                   if_triplets(d_rows, d_cols, d_vals, d_rows_cut, d_cols_cut, d_vals_cut, d_rhs_rows, d_rhs_vals,
+                                               d_rhs_rows_cut, d_rhs_vals_cut)));
     return PA_OK;
 }
 
@@ -2010,10 +2028,7 @@ int pa_interface_cell_offsets(pa_context *ctx, int face_deg, int64_t *d_offsets)
     if (!ctx || !d_offsets || face_deg < 0 || face_deg > 3) return PA_ERR_INVALID_ARG;
     (void)hipSetDevice(ctx->device);
     if (!ctx->cut) return PA_ERR_NO_MESH;
-    if (!ctx->d_if_cell_table) {
-        ctx->last_error = "the interface_assembler's numbering covers the whole mesh: not available on a slab of pa_cut_preprocess_rows";
-        return PA_ERR_INVALID_ARG;
-    }
+    if (const int st = if_numbering(ctx)) return st;
     const pa::CutMeshHost &cm = *ctx->cut;
     const size_t nc = cm.ncells();
     const int64_t cbs = pa::P2(face_deg + 1);
@@ -2030,32 +2045,11 @@ int pa_interface_cell_offsets(pa_context *ctx, int face_deg, int64_t *d_offsets)
     return PA_OK;
 }
 
-// ---- interface_assembler's system directly in CSR: interface_csr.hip -------------------------------------------------
-static pa::IfCsrMesh ifcsr_mesh(const pa_context *ctx)
-{
-    pa::IfCsrMesh m;
-    m.cell_faces = ctx->d_cell_faces; m.cell_loc = ctx->d_cell_loc; m.face_loc = ctx->d_face_loc; m.cut_index = ctx->d_cut_index;
-    m.cell_table = ctx->d_if_cell_table; m.face_table = ctx->d_if_face_table;
-    m.ncells = (uint32_t)ctx->ncells; m.nfaces = (uint32_t)ctx->cut->nfaces();
-    m.num_all_cells = (uint32_t)ctx->if_num_all_cells; m.num_other_faces = (uint32_t)ctx->if_num_other_faces;
-    return m;
-}
-
-// the refusals of pa_interface_triplets_batch, in its order (cut_arrays: the cut-cell inputs are present or not needed), then the
-// side stream joined and the symbolic tables of face_deg built if the context does not hold them
+// if_refusals, then the side stream joined and the symbolic tables of face_deg built if the context does not hold them
 static int ifcsr_prepare(pa_context *ctx, int face_deg, bool cut_arrays)
 {
-    (void)hipSetDevice(ctx->device);
-    if (face_deg < 0 || face_deg > 3) return PA_ERR_INVALID_DEGREE;
-    if (!ctx->cut || !ctx->d_cell_faces) return PA_ERR_NO_MESH;
-    if (!ctx->d_if_cell_table) {
-        ctx->last_error = "the interface_assembler's numbering covers the whole mesh: not available on a slab of pa_cut_preprocess_rows";
-        return PA_ERR_INVALID_ARG;
-    }
-    if (ctx->cut->cut_cells.size() && !cut_arrays) return PA_ERR_INVALID_ARG;
-    pa_interface_info info;
-    pa_interface_assembler_query(ctx, face_deg, &info);
-    if (info.system_size >= ((uint64_t)1 << 31)) return PA_ERR_INVALID_ARG;      // int32 column ids, as Eigen::Triplet's
+    const int st = if_refusals(ctx, face_deg, cut_arrays);
+    if (st != PA_OK) return st;
     if (ctx->side_pending) {                              // cut-cell work still out on the side stream
         PA_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_side, 0));
         ctx->side_pending = false;
@@ -2090,20 +2084,11 @@ int pa_interface_csr_fill(pa_context *ctx, int face_deg, const double *d_lc, con
     if (!ctx || !d_lc || !d_values) return PA_ERR_INVALID_ARG;
     const int st = ifcsr_prepare(ctx, face_deg, d_lc_cut != nullptr);
     if (st != PA_OK) return st;
-    PA_HIP(ctx, pa::ifcsr_fill(ctx->stream, ifcsr_mesh(ctx), ctx->ifcsr, d_lc, d_rhs, d_g, d_lc_cut, d_rhs_cut, d_values, d_RHS));
+    PA_HIP(ctx, pa::ifcsr_fill(ctx->stream, ifcsr_mesh(ctx), ctx->ifcsr, {d_lc, d_rhs, d_g, d_lc_cut, d_rhs_cut}, d_values, d_RHS));
     return PA_OK;
 }
 
-// ---- the interface problem condensed to its face unknowns: interface_condensed.hip ---------------------------------------
-// the refusals of pa_interface_csr_* (ifcsr_prepare), then the face groups' offsets of the face-only system
-static int ifcond_prepare(pa_context *ctx, int face_deg, bool cut_arrays)
-{
-    const int st = ifcsr_prepare(ctx, face_deg, cut_arrays);
-    if (st != PA_OK) return st;
-    PA_HIP(ctx, pa::ifcond_build(ctx->stream, ifcsr_mesh(ctx), &ctx->ifcsr));
-    return PA_OK;
-}
-
+// ---- condensed to the face unknowns: records and recovery in interface_condensed.hip, the face-only CSR in interface_csr.hip ----
 static pa::IfCondArgs ifcond_args(const pa_context *ctx, const double *d_cond, const double *d_cond_cut, const double *d_g)
 {
     pa::IfCondArgs a;
@@ -2115,7 +2100,7 @@ static pa::IfCondArgs ifcond_args(const pa_context *ctx, const double *d_cond, c
 int pa_interface_condensed_query(pa_context *ctx, int face_deg, pa_interface_condensed_info *out)
 {
     if (!ctx || !out) return PA_ERR_INVALID_ARG;
-    const int st = ifcond_prepare(ctx, face_deg, true);
+    const int st = ifcsr_prepare(ctx, face_deg, true);
     if (st != PA_OK) return st;
     const int fbs = face_deg + 1, nf = 4 * fbs, NF = 8 * fbs;
     out->system_size = (uint64_t)fbs * ctx->if_num_other_faces;
@@ -2131,7 +2116,7 @@ int pa_interface_condensed_ops_batch(pa_context *ctx, int face_deg, const double
                                      const double *d_rhs_cut, double *d_cond, double *d_cond_cut, int32_t *d_info, int32_t *d_info_cut)
 {
     if (!ctx || !d_lc || !d_cond) return PA_ERR_INVALID_ARG;
-    const int st = ifcond_prepare(ctx, face_deg, d_lc_cut != nullptr && d_cond_cut != nullptr);
+    const int st = ifcsr_prepare(ctx, face_deg, d_lc_cut != nullptr && d_cond_cut != nullptr);
     if (st != PA_OK) return st;
     const size_t n = ctx->ncells, ncut = ctx->cut->cut_cells.size();
     const int nf = 4 * (face_deg + 1), ntri = nf * (nf + 1) / 2;
@@ -2156,17 +2141,16 @@ int pa_interface_condensed_triplets_batch(pa_context *ctx, int face_deg, const d
     const bool cut_arrays = d_cond_cut && d_rows_cut && d_cols_cut && d_vals_cut && d_rhs_rows_cut && d_rhs_vals_cut;
     const int st = ifcsr_prepare(ctx, face_deg, cut_arrays);
     if (st != PA_OK) return st;
-    pa::IfCondTriplets o;
-    o.rows = d_rows; o.cols = d_cols; o.vals = d_vals; o.rows_cut = d_rows_cut; o.cols_cut = d_cols_cut; o.vals_cut = d_vals_cut;
-    o.rhs_rows = d_rhs_rows; o.rhs_vals = d_rhs_vals; o.rhs_rows_cut = d_rhs_rows_cut; o.rhs_vals_cut = d_rhs_vals_cut;
-    PA_HIP(ctx, pa::ifcond_triplets(ctx->stream, ifcsr_mesh(ctx), face_deg, ctx->num_cus * 8, ifcond_args(ctx, d_cond, d_cond_cut, d_g), o));
+    PA_HIP(ctx, pa::ifcond_triplets(ctx->stream, ifcsr_mesh(ctx), face_deg, ctx->num_cus * 8, ifcond_args(ctx, d_cond, d_cond_cut, d_g),
+                                    if_triplets(d_rows, d_cols, d_vals, d_rows_cut, d_cols_cut, d_vals_cut, d_rhs_rows, d_rhs_vals,
+                                                d_rhs_rows_cut, d_rhs_vals_cut)));
     return PA_OK;
 }
 
 int pa_interface_condensed_csr_pattern(pa_context *ctx, int face_deg, int64_t *d_rowptr, int32_t *d_colind)
 {
     if (!ctx || !d_rowptr) return PA_ERR_INVALID_ARG;
-    const int st = ifcond_prepare(ctx, face_deg, true);
+    const int st = ifcsr_prepare(ctx, face_deg, true);
     if (st != PA_OK) return st;
     PA_HIP(ctx, pa::ifcond_pattern(ctx->stream, ifcsr_mesh(ctx), ctx->ifcsr, d_rowptr, d_colind));
     return PA_OK;
@@ -2176,7 +2160,7 @@ int pa_interface_condensed_csr_fill(pa_context *ctx, int face_deg, const double 
                                     double *d_values, double *d_rhs)
 {
     if (!ctx || !d_cond || !d_values) return PA_ERR_INVALID_ARG;
-    const int st = ifcond_prepare(ctx, face_deg, d_cond_cut != nullptr);
+    const int st = ifcsr_prepare(ctx, face_deg, d_cond_cut != nullptr);
     if (st != PA_OK) return st;
     PA_HIP(ctx, pa::ifcond_fill(ctx->stream, ifcsr_mesh(ctx), ctx->ifcsr, ifcond_args(ctx, d_cond, d_cond_cut, d_g), d_values, d_rhs));
     return PA_OK;

@@ -16,11 +16,10 @@
 // cells, which arrives as fbs packed rows per cell (condensed_halo_pack_kernel) -- the whole exchange of a step.
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include <cstdint>
 
 #include "condensed.hpp"
+#include "device_tmp.hpp"
 
 namespace pa {
 
@@ -346,8 +345,6 @@ __global__ __launch_bounds__(256) void condensed_expand_kernel(size_t ncells_loc
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-static inline unsigned blocks_for(size_t n) { return (unsigned)((n + 255) / 256 ? (n + 255) / 256 : 1); }
-
 hipError_t cond_build_tables(hipStream_t stream, CondMesh m, uint32_t nfaces_local, uint32_t ncells, uint32_t owned_range,
                              int32_t p0, uint32_t nown, int32_t *adj, CondFace *faces, CondFaceLean *lean, uint32_t *ncols,
                              uint32_t *prefix)
@@ -358,18 +355,11 @@ hipError_t cond_build_tables(hipStream_t stream, CondMesh m, uint32_t nfaces_loc
     if (e != hipSuccess) return e;
     m.adj = adj;
     hipLaunchKernelGGL(cond_symbolic_kernel, dim3(blocks_for(owned_range)), dim3(256), 0, stream, m, owned_range, p0, nown, faces, lean, ncols);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    size_t tmp_bytes = 0;
-    void *tmp = nullptr;
-    e = rocprim::exclusive_scan(nullptr, tmp_bytes, ncols, prefix, 0u, (size_t)nown + 1, rocprim::plus<uint32_t>(), stream);
-    if (e != hipSuccess) return e;
-    e = hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 1);
-    if (e != hipSuccess) return e;
-    e = rocprim::exclusive_scan(tmp, tmp_bytes, ncols, prefix, 0u, (size_t)nown + 1, rocprim::plus<uint32_t>(), stream);
-    hipError_t e2 = hipStreamSynchronize(stream);
-    (void)hipFree(tmp);
-    return e != hipSuccess ? e : e2;
+    DeviceTmp tmp(stream);
+    if (!tmp.ok(hipGetLastError()) || exclusive_scan_with_total<uint32_t>(stream, ncols, prefix, (size_t)nown + 1, tmp, nullptr) != hipSuccess)
+        return tmp.error();
+    tmp.ok(hipStreamSynchronize(stream));
+    return tmp.error();
 }
 
 hipError_t cond_pattern(hipStream_t stream, uint32_t nown, int fbs, const CondFace *faces, const uint32_t *prefix, int64_t *rowptr,

@@ -13,6 +13,7 @@
 
 #include <cstdint>
 
+#include "device_tmp.hpp"
 #include "scan.hpp"
 
 namespace pa {
@@ -68,53 +69,40 @@ hipError_t csr_from_triplets(hipStream_t stream, size_t n, const int32_t *d_rows
                              size_t nrows, int64_t *d_rowptr, int32_t *d_colind, double *d_values, size_t *nnz_out)
 {
     if (n >= ((size_t)1 << 31)) return hipErrorInvalidValue;          // positions are int32 (the scan's tables)
-    hipError_t e;
-    uint64_t *keys = nullptr, *keys2 = nullptr, *ukeys = nullptr;
-    double *vals2 = nullptr;
-    uint8_t *flag = nullptr;
-    int32_t *pos = nullptr, *unused = nullptr;
-    uint32_t *counts = nullptr;
-    void *tmp = nullptr;
-    size_t tmp_bytes = 0;
-    const size_t nn = n ? n : 1;
-    const unsigned grid = (unsigned)((nn + 255) / 256);
-    auto cleanup = [&]() {
-        (void)hipFree(keys); (void)hipFree(keys2); (void)hipFree(ukeys); (void)hipFree(vals2); (void)hipFree(flag);
-        (void)hipFree(pos); (void)hipFree(unused); (void)hipFree(counts); (void)hipFree(tmp);
-    };
-#define CSR_TRY(call) do { e = (call); if (e != hipSuccess) { cleanup(); return e; } } while (0)
-    CSR_TRY(hipMalloc((void **)&keys, nn * 8));
-    CSR_TRY(hipMalloc((void **)&keys2, nn * 8));
-    CSR_TRY(hipMalloc((void **)&vals2, nn * 8));
+    DeviceTmp tmp(stream);
+    uint64_t *keys, *keys2, *ukeys;
+    double *vals2;
     size_t nnz = 0;
+    if (!tmp.alloc(&keys, n) || !tmp.alloc(&keys2, n) || !tmp.alloc(&vals2, n)) return tmp.error();
     if (n) {
-        hipLaunchKernelGGL(csr_keys_kernel, dim3(grid), dim3(256), 0, stream, n, d_rows, d_cols, keys);
-        CSR_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys, keys2, d_vals, vals2, n, 0, 64, stream));
-        CSR_TRY(hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 1));
-        CSR_TRY(rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, keys2, d_vals, vals2, n, 0, 64, stream));
-        CSR_TRY(hipMalloc((void **)&flag, nn));
-        CSR_TRY(hipMalloc((void **)&pos, nn * 4));
-        CSR_TRY(hipMalloc((void **)&unused, nn * 4));
-        hipLaunchKernelGGL(csr_heads_kernel, dim3(grid), dim3(256), 0, stream, n, keys2, flag);
+        uint8_t *flag;
+        int32_t *pos, *unused;
+        uint32_t *counts, total = 0;
+        char *work;
+        size_t work_bytes = 0;
+        const unsigned grid = blocks_for(n);
         const uint32_t nblocks = (uint32_t)((n + SCAN_TILE - 1) / SCAN_TILE);
-        CSR_TRY(hipMalloc((void **)&counts, (nblocks + 1) * sizeof(uint32_t)));
+        hipLaunchKernelGGL(csr_keys_kernel, dim3(grid), dim3(256), 0, stream, n, d_rows, d_cols, keys);
+        if (!tmp.ok(rocprim::radix_sort_pairs(nullptr, work_bytes, keys, keys2, d_vals, vals2, n, 0, 64, stream)) ||
+            !tmp.alloc(&work, work_bytes) ||
+            !tmp.ok(rocprim::radix_sort_pairs(work, work_bytes, keys, keys2, d_vals, vals2, n, 0, 64, stream)) ||
+            !tmp.alloc(&flag, n) || !tmp.alloc(&pos, n) || !tmp.alloc(&unused, n) || !tmp.alloc(&counts, (size_t)nblocks + 1))
+            return tmp.error();
+        hipLaunchKernelGGL(csr_heads_kernel, dim3(grid), dim3(256), 0, stream, n, keys2, flag);
         hipLaunchKernelGGL(active_count_kernel, dim3(nblocks), dim3(SCAN_BLOCK), 0, stream, flag, (uint32_t)n, counts);
         hipLaunchKernelGGL(active_block_scan_kernel, dim3(1), dim3(SCAN_BLOCK), 0, stream, counts, nblocks);
         hipLaunchKernelGGL(active_tables_kernel, dim3(nblocks), dim3(SCAN_BLOCK), 0, stream, flag, (uint32_t)n, counts, unused, pos);
-        uint32_t total = 0;
-        CSR_TRY(hipMemcpyAsync(&total, counts + nblocks, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        CSR_TRY(hipStreamSynchronize(stream));
+        if (!tmp.ok(hipMemcpyAsync(&total, counts + nblocks, sizeof(uint32_t), hipMemcpyDeviceToHost, stream)) ||
+            !tmp.ok(hipStreamSynchronize(stream)))
+            return tmp.error();
         nnz = total;
-        CSR_TRY(hipMalloc((void **)&ukeys, (nnz ? nnz : 1) * 8));
+        if (!tmp.alloc(&ukeys, nnz)) return tmp.error();
         hipLaunchKernelGGL(csr_reduce_kernel, dim3(grid), dim3(256), 0, stream, n, keys2, vals2, flag, pos, d_colind, d_values, ukeys);
-    } else {
-        CSR_TRY(hipMalloc((void **)&ukeys, 8));
+    } else if (!tmp.alloc(&ukeys, 1)) {
+        return tmp.error();
     }
-    hipLaunchKernelGGL(csr_rowptr_kernel, dim3((unsigned)((nrows + 1 + 255) / 256)), dim3(256), 0, stream, nrows, nnz, ukeys, d_rowptr);
-    CSR_TRY(hipGetLastError());
-    CSR_TRY(hipStreamSynchronize(stream));
-#undef CSR_TRY
-    cleanup();
+    hipLaunchKernelGGL(csr_rowptr_kernel, dim3(blocks_for(nrows + 1)), dim3(256), 0, stream, nrows, nnz, ukeys, d_rowptr);
+    if (!tmp.ok(hipGetLastError()) || !tmp.ok(hipStreamSynchronize(stream))) return tmp.error();
     if (nnz_out) *nnz_out = nnz;
     return hipSuccess;
 }

@@ -631,87 +631,4 @@ __global__ __launch_bounds__(256) void cut_interface_uncut_lc_kernel(size_t ncel
     lc[t] = (loc == LOC_NEG ? k1 : k2) * data[t] + stab[t];
 }
 
-// interface_assembler (cuthho_square.cpp:1091-1443): tables built on the host by pa_cut_preprocess
-struct InterfaceTripletArgs {
-    const uint32_t *cell_faces;          // ncells x 4 (global face ids: the cut mesh is never partitioned)
-    const int8_t *cell_loc, *face_loc;
-    const int32_t *cut_index;
-    const int32_t *cell_table, *face_table;   // face_table -1 for Dirichlet faces
-    const double *g;                     // nfaces x fbs Dirichlet data or null
-    const double *lc, *rhs;              // uncut: ncells x msize^2 / ncells x cbs (rows of cut cells unused)
-    const double *lc_cut, *rhs_cut;      // ncut x (2 msize)^2 / ncut x 2cbs
-    uint64_t ncells, num_all_cells;
-    int cbs, fbs;
-    int32_t *rows, *cols; double *vals;              // uncut slots: ncells x msize^2 (cut cells: all -1)
-    int32_t *rows_cut, *cols_cut; double *vals_cut;  // ncut x (2 msize)^2
-    int32_t *rhs_rows; double *rhs_vals;             // ncells x msize
-    int32_t *rhs_rows_cut; double *rhs_vals_cut;     // ncut x 2 msize
-};
-
-__global__ __launch_bounds__(256) void interface_triplets_kernel(InterfaceTripletArgs a)
-{
-    extern __shared__ double sh[];       // dirichlet data (2 msize), then int32 idx (2 msize)
-    const int msize = a.cbs + 4 * a.fbs, m2 = 2 * msize;
-    double *dd = sh;
-    int32_t *idx = reinterpret_cast<int32_t *>(sh + m2);
-    for (size_t c = blockIdx.x; c < a.ncells; c += gridDim.x) {
-        const bool cut = a.cell_loc[c] == LOC_CUT;
-        const int n = cut ? m2 : msize, ncd = cut ? 2 * a.cbs : a.cbs;
-        for (int i = threadIdx.x; i < n; i += blockDim.x) {
-            int32_t gi; double d = 0.0;
-            if (i < ncd) {
-                gi = (int32_t)((uint64_t)a.cell_table[c] * a.cbs + i);                               // :1223, :1291
-            } else {
-                const int u = i - ncd, pass = u / (4 * a.fbs), f = (u % (4 * a.fbs)) / a.fbs, k = u % a.fbs;
-                const uint32_t fid = a.cell_faces[4 * c + f];
-                const int32_t ft = a.face_table[fid];
-                const int dup = (pass == 1 && a.face_loc[fid] == LOC_CUT) ? a.fbs : 0;                // :1319
-                gi = ft < 0 ? -1 : (int32_t)(a.num_all_cells * a.cbs + (uint64_t)ft * a.fbs + dup + k);   // :1234, :1321
-                if (ft < 0 && a.g != nullptr) d = a.g[(size_t)fid * a.fbs + k];
-            }
-            idx[i] = gi; dd[i] = d;
-        }
-        __syncthreads();
-        if (!cut) {
-            const double *A = a.lc + c * (size_t)(msize * msize);
-            for (int e = threadIdx.x; e < msize * msize; e += blockDim.x) {
-                const int i = e / msize, j = e % msize;
-                const bool keep = idx[i] >= 0 && idx[j] >= 0;
-                const size_t o = c * (size_t)(msize * msize) + e;
-                a.rows[o] = keep ? idx[i] : -1;
-                a.cols[o] = keep ? idx[j] : -1;
-                a.vals[o] = A[i + j * msize];
-            }
-            for (int i = threadIdx.x; i < msize; i += blockDim.x) {
-                double s = (i < a.cbs && a.rhs != nullptr) ? a.rhs[c * a.cbs + i] : 0.0;              // :1265
-                if (idx[i] >= 0)
-                    for (int j = a.cbs; j < msize; ++j)
-                        if (idx[j] < 0) s -= A[i + j * msize] * dd[j];                                // :1261
-                a.rhs_rows[c * msize + i] = idx[i];
-                a.rhs_vals[c * msize + i] = idx[i] >= 0 ? s : 0.0;
-            }
-        } else {
-            const size_t cc = (size_t)a.cut_index[c];
-            const double *A = a.lc_cut + cc * (size_t)(m2 * m2);
-            for (int e = threadIdx.x; e < msize * msize; e += blockDim.x) {                           // nothing pushed in the uncut slots
-                const size_t o = c * (size_t)(msize * msize) + e;
-                a.rows[o] = -1; a.cols[o] = -1; a.vals[o] = 0.0;
-            }
-            for (int i = threadIdx.x; i < msize; i += blockDim.x) { a.rhs_rows[c * msize + i] = -1; a.rhs_vals[c * msize + i] = 0.0; }
-            for (int e = threadIdx.x; e < m2 * m2; e += blockDim.x) {                                 // :1337-1347
-                const int i = e / m2, j = e % m2;
-                const size_t o = cc * (size_t)(m2 * m2) + e;
-                const bool keep = idx[i] >= 0 && idx[j] >= 0;      // always true: the reference rejects Dirichlet faces on cut cells (:1304-1305)
-                a.rows_cut[o] = keep ? idx[i] : -1; a.cols_cut[o] = keep ? idx[j] : -1;
-                a.vals_cut[o] = A[i + j * m2];
-            }
-            for (int i = threadIdx.x; i < m2; i += blockDim.x) {                                      // :1349
-                a.rhs_rows_cut[cc * m2 + i] = idx[i];
-                a.rhs_vals_cut[cc * m2 + i] = (i < 2 * a.cbs && a.rhs_cut != nullptr) ? a.rhs_cut[cc * 2 * a.cbs + i] : 0.0;
-            }
-        }
-        __syncthreads();
-    }
-}
-
 }  // namespace pa

@@ -1,11 +1,14 @@
-// interface_csr.hpp -- host entry points of interface_csr.hip: interface_assembler's global system (cuthho_square.cpp:1091-1443,
-// cut cells and cut faces with two blocks of unknowns) in CSR, built from the tables of pa_cut_preprocess.
+// interface_csr.hpp -- host entry points of interface_csr.hip and interface_condensed.hip: interface_assembler's global system
+// (cuthho_square.cpp:1091-1443, cut cells and cut faces with two blocks of unknowns) and its face-only system after static
+// condensation, in CSR and as triplets, built from the tables of pa_cut_preprocess.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace pa {
+
+constexpr int8_t IF_LOC_CUT = 2;                // LOC_CUT of cut_host.hpp
 
 // the cut mesh as the interface numbering sees it (the context's device copies; whole-mesh contexts only)
 struct IfCsrMesh {
@@ -17,6 +20,36 @@ struct IfCsrMesh {
     uint32_t num_all_cells, num_other_faces;    // cell blocks / face blocks (cut elements counted twice)
 };
 
+struct IfDims {
+    int cbs, fbs;
+};
+__host__ __device__ __forceinline__ IfDims if_dims(int face_deg) { return {(face_deg + 3) * (face_deg + 2) / 2, face_deg + 1}; }
+
+// The numbering's index map (:1223-1234, :1291-1321): the global unknown of local unknown i of cell X, whose unknowns are
+// [cell | faces] (uncut) or [cell-, cell+, faces-, faces+] (cut).  faces+ of a cut face is its second block, faces+ of an uncut
+// face its only block (:1319).  -1 on a Dirichlet face; its entry of the boundary data (nfaces x fbs) goes to *bdof if given.
+__device__ __forceinline__ int32_t if_global_index(const IfCsrMesh &m, IfDims d, size_t X, bool cut, int i, size_t *bdof = nullptr)
+{
+    const int ncd = cut ? 2 * d.cbs : d.cbs;
+    if (i < ncd) return (int32_t)((uint64_t)m.cell_table[X] * d.cbs + i);
+    const int u = i - ncd, side = u / (4 * d.fbs), lf = (u / d.fbs) % 4, k = u % d.fbs;
+    const uint32_t f = m.cell_faces[4 * X + lf];
+    const int32_t b = m.face_table[f];
+    if (b < 0) {
+        if (bdof != nullptr) *bdof = (size_t)f * d.fbs + k;
+        return -1;
+    }
+    const int dup = (cut && side == 1 && m.face_loc[f] == IF_LOC_CUT) ? 1 : 0;
+    return (int32_t)((uint64_t)m.num_all_cells * d.cbs + (uint64_t)(b + dup) * d.fbs + k);
+}
+
+// the same in the face-only numbering (the numbering without its cell blocks), of local face unknown j
+__device__ __forceinline__ int32_t if_face_index(const IfCsrMesh &m, IfDims d, size_t X, bool cut, int j, size_t *bdof = nullptr)
+{
+    const int32_t gi = if_global_index(m, d, X, cut, (cut ? 2 : 1) * d.cbs + j, bdof);
+    return gi < 0 ? -1 : gi - (int32_t)m.num_all_cells * d.cbs;
+}
+
 // 16-bit code of at most two local indices (ascending): count in bits 0-1, first in bits 2-8, second in bits 9-15
 __host__ __device__ __forceinline__ uint32_t ifc_code1(int a) { return 1u | ((uint32_t)a << 2); }
 __host__ __device__ __forceinline__ uint32_t ifc_code2(int a, int b) { return 2u | ((uint32_t)a << 2) | ((uint32_t)b << 9); }
@@ -25,16 +58,18 @@ __device__ __forceinline__ int ifc_first(uint32_t c) { return (int)((c >> 2) & 1
 __device__ __forceinline__ int ifc_second(uint32_t c) { return (int)((c >> 9) & 127u); }
 
 // A row group is one block of unknowns: a cell block (cbs rows) or a face block (fbs rows).  Every row of a group has the same
-// columns, a sorted run of units (a unit is one whole block of columns).  `cell` lists the (at most two) cells that push rows
-// into the group, lower id first; rcode[s] packs their local row bases (see ifc_code in interface_csr.hip).
+// columns, a sorted run of units (a unit is one whole block of columns): the cell units first (cell blocks come first in the
+// numbering), then the face units, which are the row of the face-only system.  `cell` lists the (at most two) cells that push
+// rows into the group, lower id first; rcode[s] packs their local row bases (see ifc_code above).
 struct IfGroup {
     uint64_t vstart;        // first CSR entry of the group's first row
     uint32_t ustart;        // first unit
     uint16_t nunits, R;     // units; entries per row
     int32_t cell[2];        // -1: none
     uint32_t rcode;         // local row bases of cell[0] (low 16 bits) and cell[1] (high 16 bits)
-    uint32_t pad_;
+    uint16_t fu0, fpos;     // first face unit (nunits: none) and its position in the row (R: none)
 };
+static_assert(sizeof(IfGroup) == 32, "IfGroup is two 16-byte loads");
 struct IfUnit {
     int32_t gcol;           // first global column of the block
     uint16_t pos, width;    // position in the row, cbs or fbs
@@ -48,46 +83,52 @@ struct IfCsrTables {
     uint32_t ngroups = 0, nunits = 0;
     IfGroup *groups = nullptr;
     IfUnit *units = nullptr;
-    // the face-only (condensed) system of the same numbering (interface_condensed.hip), built on first use: first entry of every
-    // face group's rows (num_other_faces + 1) and the total
+    // the face-only (condensed) system of the same numbering: first entry of every face group's rows (num_other_faces + 1)
+    // and the total
     uint64_t *cvstart = nullptr;
     uint64_t cnnz = 0;
 };
 
-// builds *t (freeing what it holds first); on failure every allocation is released and *t is left empty
-hipError_t ifcsr_build(hipStream_t stream, const IfCsrMesh &m, int face_deg, IfCsrTables *t);
-void ifcsr_release(IfCsrTables *t);
-hipError_t ifcsr_pattern(hipStream_t stream, const IfCsrMesh &m, const IfCsrTables &t, int64_t *rowptr, int32_t *colind);
-hipError_t ifcsr_fill(hipStream_t stream, const IfCsrMesh &m, const IfCsrTables &t, const double *lc, const double *rhs, const double *g,
-                      const double *lc_cut, const double *rhs_cut, double *values, double *RHS);
-
-// ---- the face-only system after static condensation (interface_condensed.hip) ------------------------------------------
-// Records: uncut cells [S packed (ncells x nf(nf+1)/2) | g (ncells x nf)], cut cells [S (ncut x NF(NF+1)/2) | g (ncut x NF)],
-// nf = 4 fbs, NF = 8 fbs; S the upper triangle of the Schur complement, column-packed.
+// the local matrices and right-hand sides of the full system: uncut ncells x msize^2 / ncells x cbs (rows of cut cells unused),
+// cut ncut x (2 msize)^2 / ncut x 2 cbs; column-major
+struct IfLocalArgs {
+    const double *lc, *rhs, *g, *lc_cut, *rhs_cut;      // g: nfaces x fbs Dirichlet data or null
+};
+// The records of the face-only system: uncut cells [S packed (ncells x nf(nf+1)/2) | g (ncells x nf)], cut cells
+// [S (ncut x NF(NF+1)/2) | g (ncut x NF)], nf = 4 fbs, NF = 8 fbs; S the upper triangle of the Schur complement, column-packed.
 struct IfCondArgs {
     const double *cond, *cond_cut;      // records
     const double *g;                    // nfaces x fbs Dirichlet data or null
     const uint32_t *cut_cells;          // ncut cell ids
     uint32_t ncut;
 };
-// the face groups' entry offsets (t->cvstart, t->cnnz) if not built yet
-hipError_t ifcond_build(hipStream_t stream, const IfCsrMesh &m, IfCsrTables *t);
-hipError_t ifcond_pattern(hipStream_t stream, const IfCsrMesh &m, const IfCsrTables &t, int64_t *rowptr, int32_t *colind);
-hipError_t ifcond_fill(hipStream_t stream, const IfCsrMesh &m, const IfCsrTables &t, const IfCondArgs &a, double *values, double *RHS);
-// the cut cells' records in double-double (one wavefront per cut cell); info[cc] = 200 + j + 1 for a failed pivot j, else 0
-hipError_t ifcond_cut_records(hipStream_t stream, int face_deg, int max_blocks, uint32_t ncut, const double *lc_cut,
-                              const double *rhs_cut, double *cond_cut, int32_t *info);
-// the uncut cells' info of static_condensation_kernel (j + 1) in the same convention
-hipError_t ifcond_info_remap(hipStream_t stream, size_t n, int32_t *info);
-// triplets in the reference's push order: uncut slots ncells x nf^2 (cut cells: all -1), cut slots ncut x NF^2; right-hand side
-// slots ncells x nf / ncut x NF
-struct IfCondTriplets {
+// triplets in the reference's push order, n = msize (full) or nf (face-only) unknowns per uncut cell, N = 2 msize or NF per cut
+// cell: uncut slots ncells x n^2 (cut cells: all -1), cut slots ncut x N^2; right-hand side slots ncells x n / ncut x N
+struct IfTriplets {
     int32_t *rows, *cols; double *vals;
     int32_t *rows_cut, *cols_cut; double *vals_cut;
     int32_t *rhs_rows; double *rhs_vals;
     int32_t *rhs_rows_cut; double *rhs_vals_cut;
 };
-hipError_t ifcond_triplets(hipStream_t stream, const IfCsrMesh &m, int face_deg, int max_blocks, const IfCondArgs &a, const IfCondTriplets &o);
+
+// builds *t (freeing what it holds first); on failure every allocation is released and *t is left empty
+hipError_t ifcsr_build(hipStream_t stream, const IfCsrMesh &m, int face_deg, IfCsrTables *t);
+void ifcsr_release(IfCsrTables *t);
+// the full system (interface_csr.hip)
+hipError_t ifcsr_pattern(hipStream_t stream, const IfCsrMesh &m, const IfCsrTables &t, int64_t *rowptr, int32_t *colind);
+hipError_t ifcsr_fill(hipStream_t stream, const IfCsrMesh &m, const IfCsrTables &t, const IfLocalArgs &a, double *values, double *RHS);
+hipError_t ifcsr_triplets(hipStream_t stream, const IfCsrMesh &m, int face_deg, int max_blocks, const IfLocalArgs &a, const IfTriplets &o);
+// the face-only system: the same gather reading the records (interface_csr.hip)
+hipError_t ifcond_pattern(hipStream_t stream, const IfCsrMesh &m, const IfCsrTables &t, int64_t *rowptr, int32_t *colind);
+hipError_t ifcond_fill(hipStream_t stream, const IfCsrMesh &m, const IfCsrTables &t, const IfCondArgs &a, double *values, double *RHS);
+hipError_t ifcond_triplets(hipStream_t stream, const IfCsrMesh &m, int face_deg, int max_blocks, const IfCondArgs &a, const IfTriplets &o);
+
+// ---- the dense per-cell work of the condensation (interface_condensed.hip) ------------------------------------------------
+// the cut cells' records in double-double (one wavefront per cut cell); info[cc] = 200 + j + 1 for a failed pivot j, else 0
+hipError_t ifcond_cut_records(hipStream_t stream, int face_deg, int max_blocks, uint32_t ncut, const double *lc_cut,
+                              const double *rhs_cut, double *cond_cut, int32_t *info);
+// the uncut cells' info of static_condensation_kernel (j + 1) in the same convention
+hipError_t ifcond_info_remap(hipStream_t stream, size_t n, int32_t *info);
 // u_T = A_TT^-1 (f_T - A_TF u_F) of every cell (cut cells in double-double) into the interface_assembler's full solution vector:
 // cell blocks at cell_table, then xF
 hipError_t ifcond_recover(hipStream_t stream, const IfCsrMesh &m, int face_deg, int max_blocks, const IfCondArgs &a, const double *lc,

@@ -7,6 +7,9 @@ import math
 import numpy as np
 import pytest
 
+import interface_helpers as ih
+from interface_helpers import condensed_sizes as sizes, real_ops
+
 pytestmark = pytest.mark.gpu
 
 
@@ -19,54 +22,9 @@ def asm():
     return BatchAssembler(0)
 
 
-def sizes(k):
-    cbs = (k + 3) * (k + 2) // 2          # cell degree k + 1
-    fbs = k + 1
-    nf, NF = 4 * fbs, 8 * fbs
-    return cbs, fbs, nf, NF
-
-
-def in_cell_order(asm, uncut, cut, per_cell):
-    """[ncells, per_cell] uncut and [ncut, per_cut] cut slot arrays -> one flat array in the reference's push order: cells ascending,
-    a cut cell's block in place of its (empty) uncut block"""
-    import torch
-    dev = asm.device
-    nc = uncut.shape[0]
-    ci = torch.from_numpy(np.asarray(asm.cut_index, dtype=np.int64)).to(dev)
-    is_cut = ci >= 0
-    per_cut = cut.shape[1] if cut.numel() else 0
-    counts = torch.where(is_cut, per_cut, per_cell)
-    base = torch.where(is_cut, nc * per_cell + ci.clamp(min=0) * per_cut, torch.arange(nc, device=dev) * per_cell)
-    starts = torch.cumsum(counts, 0) - counts
-    total = int(counts.sum())
-    local = torch.arange(total, device=dev) - torch.repeat_interleave(starts, counts)
-    src = torch.repeat_interleave(base, counts) + local
-    return torch.cat([uncut.reshape(-1), cut.reshape(-1)])[src]
-
-
 def sorted_path(asm, k, rec, g):
-    """pa_interface_condensed_triplets_batch -> slots in cell order -> pa_csr_from_triplets; RHS = np.add.at of the per-row sums"""
-    cbs, fbs, nf, NF = sizes(k)
-    qi = asm.ctx.interface_condensed_query(k)
-    t = asm.interface_condensed_triplets(k, rec, g)
-    r = in_cell_order(asm, t["rows"], t["rows_cut"], nf * nf)
-    c = in_cell_order(asm, t["cols"], t["cols_cut"], nf * nf)
-    v = in_cell_order(asm, t["vals"], t["vals_cut"], nf * nf)
-    rowptr, colind, values = asm.csr_from_triplets(r, c, v, qi.system_size)
-    rr = in_cell_order(asm, t["rhs_rows"], t["rhs_rows_cut"], nf).cpu().numpy()
-    rv = in_cell_order(asm, t["rhs_vals"], t["rhs_vals_cut"], nf).cpu().numpy()
-    RHS = np.zeros(qi.system_size)
-    keep = rr >= 0
-    np.add.at(RHS, rr[keep], rv[keep])
-    return rowptr, colind, values, RHS
-
-
-def real_ops(asm, N, k, **kw):
-    import proton_amd as pa
-    asm.cut_preprocess(N, refsteps=4, **kw)
-    ops = asm.interface_local_ops(k)
-    g = asm.dirichlet_data(k, pa.capi.FN_SIN_SIN_SOL)
-    return ops, g
+    """pa_interface_condensed_triplets_batch -> slots in cell order -> pa_csr_from_triplets"""
+    return ih.sorted_path(asm, asm.interface_condensed_triplets(k, rec, g), sizes(k)[2], asm.ctx.interface_condensed_query(k).system_size)
 
 
 def synthetic_records(asm, N, k, seed, **kw):
@@ -83,16 +41,8 @@ def synthetic_records(asm, N, k, seed, **kw):
 
 
 def check_bit_identical(asm, k, rec, g):
-    import torch
-    rowptr, colind, values, RHS = sorted_path(asm, k, rec, g)
-    rp, ci = asm.interface_condensed_csr_pattern(k)
-    va, RH = asm.interface_condensed_csr_fill(k, rec, g)
-    asm.synchronize()
-    assert rp.numel() == rowptr.numel() and int(rp[-1]) == ci.numel() == colind.numel()
-    assert torch.equal(rp, rowptr) and torch.equal(ci, colind)
-    assert torch.equal(va, values)
-    assert np.array_equal(RH.cpu().numpy(), RHS)
-    return rp, ci, va, RH
+    return ih.check_bit_identical(asm, sorted_path(asm, k, rec, g), lambda: asm.interface_condensed_csr_pattern(k),
+                                  lambda: asm.interface_condensed_csr_fill(k, rec, g))
 
 
 def full_csr(asm, k, ops, g):
@@ -138,10 +88,13 @@ def test_condensed_csr_line_level_set_drops_the_boundary_slots(asm, k):
 
 
 # ---- 2. the Schur complement of the full system ----------------------------------------------------------------------------
-def test_condensed_pattern_is_the_face_block_of_the_full_pattern(asm):
-    N, k = 20, 2
+@pytest.mark.parametrize("N,k,kw", [(20, 2, {}), (10, 1, {}), (12, 1, {"line_y": 0.43})], ids=["circle-20-k2", "circle-10-k1", "line-12-k1"])
+def test_condensed_pattern_is_the_face_block_of_the_full_pattern(asm, N, k, kw):
+    """the face part of every face group's row (IfGroup::fu0, fpos) against the face-face block cut out of the full pattern on the
+    host: the circle, and the line level set with Dirichlet faces on the cut cells' rows"""
     cbs, fbs, nf, NF = sizes(k)
-    real_ops(asm, N, k)
+    asm.cut_preprocess(N, refsteps=4, **kw)
+    assert asm.ncut > 0
     info = asm.ctx.interface_info(k)
     rp, ci = asm.interface_csr_pattern(k)
     crp, cci = asm.interface_condensed_csr_pattern(k)

@@ -5,6 +5,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import interface_helpers as ih
+from interface_helpers import full_sizes as sizes, real_ops
+
 pytestmark = pytest.mark.gpu
 
 
@@ -17,52 +20,9 @@ def asm():
     return BatchAssembler(0)
 
 
-def sizes(k):
-    cbs = (k + 3) * (k + 2) // 2          # cell degree k + 1
-    return cbs, cbs + 4 * (k + 1)
-
-
-def in_cell_order(asm, uncut, cut, per_cell):
-    """[ncells, per_cell] uncut and [ncut, 4 per_cell or 2 per_cell] cut slot arrays -> one flat array in the reference's push
-    order: cells ascending, a cut cell's block in place of its (empty) uncut block"""
-    import torch
-    dev = asm.device
-    nc = uncut.shape[0]
-    ci = torch.from_numpy(np.asarray(asm.cut_index, dtype=np.int64)).to(dev)
-    is_cut = ci >= 0
-    per_cut = cut.shape[1] if cut.numel() else 0
-    counts = torch.where(is_cut, per_cut, per_cell)
-    base = torch.where(is_cut, nc * per_cell + ci.clamp(min=0) * per_cut, torch.arange(nc, device=dev) * per_cell)
-    starts = torch.cumsum(counts, 0) - counts
-    total = int(counts.sum())
-    local = torch.arange(total, device=dev) - torch.repeat_interleave(starts, counts)
-    src = torch.repeat_interleave(base, counts) + local
-    return torch.cat([uncut.reshape(-1), cut.reshape(-1)])[src]
-
-
 def sorted_path(asm, k, ops, g):
-    """pa_interface_triplets_batch -> slots in cell order -> pa_csr_from_triplets; RHS = np.add.at of the per-row sums in cell order"""
-    cbs, ms = sizes(k)
-    info = asm.ctx.interface_info(k)
-    t = asm.interface_triplets(k, ops, g)
-    r = in_cell_order(asm, t["rows"], t["rows_cut"], ms * ms)
-    c = in_cell_order(asm, t["cols"], t["cols_cut"], ms * ms)
-    v = in_cell_order(asm, t["vals"], t["vals_cut"], ms * ms)
-    rowptr, colind, values = asm.csr_from_triplets(r, c, v, info.system_size)
-    rr = in_cell_order(asm, t["rhs_rows"], t["rhs_rows_cut"], ms).cpu().numpy()
-    rv = in_cell_order(asm, t["rhs_vals"], t["rhs_vals_cut"], ms).cpu().numpy()
-    RHS = np.zeros(info.system_size)
-    keep = rr >= 0
-    np.add.at(RHS, rr[keep], rv[keep])
-    return rowptr, colind, values, RHS
-
-
-def real_ops(asm, N, k, **kw):
-    import proton_amd as pa
-    asm.cut_preprocess(N, refsteps=4, **kw)
-    ops = asm.interface_local_ops(k)
-    g = asm.dirichlet_data(k, pa.capi.FN_SIN_SIN_SOL)
-    return ops, g
+    """pa_interface_triplets_batch -> slots in cell order -> pa_csr_from_triplets"""
+    return ih.sorted_path(asm, asm.interface_triplets(k, ops, g), sizes(k)[1], asm.ctx.interface_info(k).system_size)
 
 
 def synthetic_ops(asm, N, k, seed, **kw):
@@ -82,16 +42,8 @@ def synthetic_ops(asm, N, k, seed, **kw):
 
 
 def check_bit_identical(asm, k, ops, g):
-    import torch
-    rowptr, colind, values, RHS = sorted_path(asm, k, ops, g)
-    rp, ci = asm.interface_csr_pattern(k)
-    va, RH = asm.interface_csr_fill(k, ops, g)
-    asm.synchronize()
-    assert rp.numel() == rowptr.numel() and int(rp[-1]) == ci.numel() == colind.numel()
-    assert torch.equal(rp, rowptr) and torch.equal(ci, colind)
-    assert torch.equal(va, values)
-    assert np.array_equal(RH.cpu().numpy(), RHS)
-    return rp, ci, va, RH
+    return ih.check_bit_identical(asm, sorted_path(asm, k, ops, g), lambda: asm.interface_csr_pattern(k),
+                                  lambda: asm.interface_csr_fill(k, ops, g))
 
 
 @pytest.mark.parametrize("N,k", [(10, 0), (20, 1), (20, 2)])

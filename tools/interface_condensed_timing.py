@@ -3,7 +3,8 @@ events after a warm-up.  Full: pa_interface_csr_fill (cell + face unknowns).  Co
 uncut cells in double, cut cells in double-double) + pa_interface_condensed_csr_fill, then pa_interface_condensed_recover after the
 solve.  Both systems go to pa_conjugated_gradient with Jacobi to the same tolerance.  The divergence test is set far out (1e10
 instead of the reference's 100, which the Jacobi-PCG residual of the 512 x 512 systems crosses in its first iterations): the
-tool measures the iterations to the tolerance.
+tool measures the iterations to the tolerance.  A tolerance of 0 skips the two solves (the recovery is then timed on the condensed
+right-hand side in place of a solution): the kernel timings alone, in seconds.
     python tools/interface_condensed_timing.py [N] [k] [reps] [tol]          (default 512 2 10 1e-9)"""
 import json
 import os
@@ -43,6 +44,8 @@ def cg(asm, rp, ci, va, b, tol, max_iter):
 
 
 def cg_text(r, max_iter):
+    if r is None:
+        return "no solve"
     if r["converged"]:
         return "CG converged in %d iterations, %.3f s, relative residual %.3e" % (r["iterations"], r["time_s"], r["relative_residual"])
     why = "max_iter %d reached" % max_iter if r["exit_reason"] == 2 else "exit reason %d" % r["exit_reason"]
@@ -84,16 +87,17 @@ def main():
     t_both = timed(lambda: asm.interface_condensed_csr_fill(k, asm.interface_condensed_ops(k, ops), g, cva, cRH), reps)
     info_bad = int((rec["info"] != 0).sum()) + int((rec["info_cut"] != 0).sum())
 
-    xF, cg_cond = cg(asm, crp, cci, cva[:qi.nnz], cRH[:qi.system_size], tol, max_iter)
+    solve = tol > 0
+    xF, cg_cond = cg(asm, crp, cci, cva[:qi.nnz], cRH[:qi.system_size], tol, max_iter) if solve else (cRH[:qi.system_size].clone(), None)
     asm.interface_condensed_recover(k, ops, xF, g)
     t_recover = timed(lambda: asm.interface_condensed_recover(k, ops, xF, g), reps)
     full_x = asm.interface_condensed_recover(k, ops, xF, g)
     del rec, crp, cci, cva, cRH
     torch.cuda.empty_cache()
-    x, cg_full = cg(asm, rp, ci, va, RH, tol, max_iter)
+    x, cg_full = cg(asm, rp, ci, va, RH, tol, max_iter) if solve else (None, None)
     asm.synchronize()
     # the two solutions are compared only if both reached the tolerance (an unconverged iterate says nothing about the recovery)
-    diff = float((full_x - x).abs().max()) / float(x.abs().max()) if cg_full["converged"] and cg_cond["converged"] else None
+    diff = float((full_x - x).abs().max()) / float(x.abs().max()) if solve and cg_full["converged"] and cg_cond["converged"] else None
 
     res = {"N": N, "k": k, "cells": asm.ncells, "cut_cells": asm.ncut, "reps": reps, "tol": tol, "divergence_threshold": DIV,
            "full": {"rows": info.system_size, "nnz": full_nnz, "fill_ms": statistics.median(t_full_fill), "cg": cg_full},

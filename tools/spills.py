@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Register footprint of every local-operator kernel instance (compiled to assembly with the flags _build.py uses):
-name, VGPRs, spilled VGPRs, scratch bytes.  A spill in the store phase costs a vmcnt(0) wait per reload."""
+name, VGPRs, spilled VGPRs, scratch bytes.  A spill in the store phase costs a vmcnt(0) wait per reload.
+    python tools/spills.py                          the local-operator instances
+    python tools/spills.py interface_csr [...]      every kernel of csrc/<unit>.hip instead"""
 import concurrent.futures, os, re, subprocess, sys, tempfile
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from proton_amd import _build as B
@@ -21,7 +23,24 @@ def one(cfg):
         rows.append((tuple(int(x) for x in t.groups()[:5]), kind, int(m.group(3)), int(m.group(4)), int(m.group(2))))
     return rows
 
+def unit(name):
+    with tempfile.TemporaryDirectory() as d:
+        out = os.path.join(d, "k.s")
+        subprocess.run([B.hipcc()] + B.FLAGS + ["--cuda-device-only", "-S", "-o", out, os.path.join(B.CSRC, name + ".hip")],
+                       check=True, capture_output=True)
+        txt = open(out).read()
+    for m in re.finditer(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)\n\s+\.vgpr_spill_count:\s+(\d+)", txt):
+        kernel = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()
+        kernel = kernel.replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0]
+        if "rocprim" not in kernel:
+            print("%-20s %-60s vgpr %3d spilled %3d scratch %4d" % (name, kernel, int(m.group(3)), int(m.group(4)), int(m.group(2))))
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1:
+        for name in sys.argv[1:]:
+            unit(name)
+        sys.exit(0)
     bad = 0
     with concurrent.futures.ThreadPoolExecutor(max_workers=8) as ex:
         for rows in ex.map(one, B.configs()):
