@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define PA_ABI_VERSION 4
+#define PA_ABI_VERSION 5
 
 /* status codes (reference: C++ exceptions / silent NaNs) */
 enum {
@@ -308,6 +308,23 @@ int pa_assembler_csr_query(pa_context *ctx, pa_degree_info di, pa_assembler_csr_
 int pa_assembler_csr_pattern(pa_context *ctx, pa_degree_info di, int64_t *d_rowptr, int32_t *d_colind);
 int pa_assembler_csr_fill(pa_context *ctx, pa_degree_info di, const double *d_lc, const double *d_rhs, const double *d_g,
                           double *d_values, double *d_RHS);
+
+/* make_hho_laplacian + stabilization + assembler::assemble + finalize in one pass per cell (hho.hpp:32-237, :344-406,
+ * :451-455): the reference turns a cell's local matrix into global entries in the loop iteration that formed it, and so does
+ * this entry -- the local-operator kernel writes d_values / d_RHS of the pattern pa_assembler_csr_query / _pattern describe
+ * straight from its on-chip image of lc; no ncells x msize^2 buffer exists unless d_lc asks for one (the layout of
+ * pa_local_ops_batch; callers need it again for the energy error, convergence_test.cpp:283-300).  All cells of the context
+ * (whole-mesh contexts only, refused as pa_assembler_csr_fill refuses a slab); the (degree pair, quadrature, stabilization)
+ * combinations and error codes of pa_condensed_ops_batch; in pieces under pa_context_set_record_cap as pa_local_ops_batch.
+ * d_rhs (ncells x cbs or NULL), d_g (pa_dirichlet_data_batch or NULL), d_RHS nrows (may be NULL), d_info ncells (may be NULL).
+ * Contract: d_values and d_RHS are BIT-IDENTICAL to pa_assembler_csr_fill fed with the d_lc this call returns and the same
+ * d_rhs / d_g, with or without d_lc and from call to call.  A face's own diagonal block and right-hand side take one addend
+ * per adjacent cell; they are added onto entries the call zeroes first, a two-term sum that does not depend on arrival order.
+ * Every other entry is written exactly once and nothing else of d_values is touched. */
+int pa_assembler_csr_assemble(pa_context *ctx, pa_degree_info di, int quad_kind, int stab_kind,
+                              const double *d_rhs, const double *d_g,
+                              double *d_values, double *d_RHS,
+                              double *d_lc /* may be NULL */, int32_t *d_info /* may be NULL */);
 
 /* assembler::take_local_data (hho.hpp:408-449) for cells [first, first+n): d_out n x msize =
  * the cell's dofs of `d_solution` (system_size values), Dirichlet faces filled from d_g

@@ -225,6 +225,28 @@ class BatchAssembler:
         self.ctx.assembler_csr_fill(di, lc.data_ptr(), _ptr(rhs), _ptr(g), values.data_ptr(), RHS.data_ptr())
         return values[:info.nnz], RHS[:info.nrows]
 
+    def assembler_csr_assemble(self, cd, fd, quad=capi.QUAD_TENSOR, stab=capi.STAB_FANCY, rhs=None, g=None, values=None, RHS=None,
+                               want=()):
+        """local operators + numeric phase fused: the local-operator kernel writes the CSR values of assembler_csr_pattern from its
+        on-chip image of lc (no [ncells, msize, msize] buffer unless "lc" is in `want`) -> dict(values [nnz], RHS [nrows]
+        [, lc [ncells, msize, msize]] [, info [ncells]]); bit-identical to assembler_csr_fill of that lc"""
+        di, _ = capi.degree_info(cd, fd)
+        sz = capi.sizes_for(di, quad)
+        info = self.ctx.assembler_csr_query(di)
+        if values is None:
+            values = torch.empty(max(info.nnz, 1), dtype=torch.float64, device=self.device)
+        if RHS is None:
+            RHS = torch.empty(max(info.nrows, 1), dtype=torch.float64, device=self.device)
+        lc = torch.empty((self.ncells, sz.msize, sz.msize), dtype=torch.float64, device=self.device) if "lc" in want else None
+        cinfo = torch.empty(self.ncells, dtype=torch.int32, device=self.device) if "info" in want else None
+        self.ctx.assembler_csr_assemble(di, quad, stab, _ptr(rhs), _ptr(g), values.data_ptr(), RHS.data_ptr(), _ptr(lc), _ptr(cinfo))
+        out = {"values": values[:info.nnz], "RHS": RHS[:info.nrows]}
+        if lc is not None:
+            out["lc"] = lc
+        if cinfo is not None:
+            out["info"] = cinfo
+        return out
+
     def csr_from_triplets(self, rows, cols, vals, nrows):
         """setFromTriplets on the device -> (rowptr int64 [nrows+1], colind int32 [nnz], values [nnz])."""
         rows, cols, vals = rows.reshape(-1), cols.reshape(-1), vals.reshape(-1)

@@ -37,7 +37,7 @@ EXPORTS = [
     "pa_interface_condensed_query", "pa_interface_condensed_ops_batch", "pa_interface_condensed_triplets_batch",
     "pa_interface_condensed_csr_pattern", "pa_interface_condensed_csr_fill", "pa_interface_condensed_recover",
     "pa_condensed_ops_batch", "pa_condensed_recover_batch", "pa_condensed_query", "pa_condensed_triplets_batch",
-    "pa_assembler_csr_query", "pa_assembler_csr_pattern", "pa_assembler_csr_fill",
+    "pa_assembler_csr_query", "pa_assembler_csr_pattern", "pa_assembler_csr_fill", "pa_assembler_csr_assemble",
     "pa_condensed_csr_pattern", "pa_condensed_csr_fill", "pa_condensed_halo_pack", "pa_condensed_take_faces",
     "pa_condensed_expand_solution", "pa_condensed_launch_info", "pa_condensed_partition_info",
     "pa_comm_unique_id", "pa_comm_create", "pa_comm_destroy", "pa_comm_info", "pa_comm_last_error",
@@ -218,6 +218,7 @@ def lib():
     L.pa_assembler_csr_query.argtypes = [vp, DegreeInfo, C.POINTER(AssemblerCsrInfo)]
     L.pa_assembler_csr_pattern.argtypes = [vp, DegreeInfo, dp, dp]
     L.pa_assembler_csr_fill.argtypes = [vp, DegreeInfo, dp, dp, dp, dp, dp]
+    L.pa_assembler_csr_assemble.argtypes = [vp, DegreeInfo, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp]
     L.pa_condensed_csr_pattern.argtypes = [vp, DegreeInfo, dp, dp]
     L.pa_condensed_csr_fill.argtypes = [vp, DegreeInfo, dp, dp, dp, dp, dp]
     L.pa_condensed_halo_pack.argtypes = [vp, DegreeInfo, dp, dp, dp]
@@ -620,6 +621,10 @@ class Context:
 
     def assembler_csr_fill(self, di, lc, rhs, g, values, RHS):
         self._ck(self._L.pa_assembler_csr_fill(self.h, di, lc, rhs, g, values, RHS), "pa_assembler_csr_fill")
+
+    def assembler_csr_assemble(self, di, quad, stab, rhs, g, values, RHS, lc=None, info=None):
+        """local operators and the assembler's CSR values / RHS in one pass per cell; lc only if a pointer is given"""
+        self._ck(self._L.pa_assembler_csr_assemble(self.h, di, quad, stab, rhs, g, values, RHS, lc, info), "pa_assembler_csr_assemble")
 
     def condensed_csr_pattern(self, di, rowptr, colind):
         self._ck(self._L.pa_condensed_csr_pattern(self.h, di, rowptr, colind), "pa_condensed_csr_pattern")

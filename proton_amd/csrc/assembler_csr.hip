@@ -403,4 +403,87 @@ hipError_t asm_fill(hipStream_t stream, const CondMesh &m, int cbs, int fbs, uin
     return hipErrorInvalidValue;
 }
 
+// ---- the fused path: pa_assembler_csr_assemble ---------------------------------------------------------------------------
+// hho_local_ops_kernel<Cfg, MODE_ASM> writes the values from its LDS image (hho_asm_scatter.hpp).  It works cell by cell, so it
+// needs the inverse of the face-indexed tables above: per cell, where the rows of its faces start and where its columns sit in
+// them.  One thread per cell, once per mesh.
+__global__ __launch_bounds__(256) void asm_scatter_table_kernel(uint32_t ncells, const uint32_t *cell_faces, const int32_t *face_compress,
+                                                                const uint32_t *cprefix, const CondFace *faces, const uint32_t *colprefix,
+                                                                const uint32_t *fprefix, AsmCellRec *out)
+{
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= ncells) return;
+    const CellFaces cf = cell_faces_sorted(cell_faces, face_compress, c);
+    const uint4 f4 = *reinterpret_cast<const uint4 *>(cell_faces + 4 * (size_t)c);
+    const uint32_t f[4] = {f4.x, f4.y, f4.z, f4.w};
+    AsmCellRec rec;
+    rec.cpre = cprefix[c];
+    rec.order = (uint32_t)cf.n << 8;
+    for (int s = 0; s < cf.n; ++s) rec.order |= (uint32_t)cf.lf[s] << (2 * s);
+    int32_t comp[4];
+    for (int lf = 0; lf < 4; ++lf) comp[lf] = face_compress[f[lf]];
+    for (int lf = 0; lf < 4; ++lf) {
+        rec.comp[lf] = comp[lf]; rec.face[lf] = f[lf];
+        rec.fpre[lf] = rec.colpre[lf] = 0; rec.pack[lf] = 0xfffu;
+        if (comp[lf] < 0) continue;
+        const CondFace &r = faces[comp[lf]];
+        const uint32_t ncell = (uint32_t)(r.cA >= 0) + (uint32_t)(r.cB >= 0);
+        const bool second = r.cA >= 0 && r.cA != (int32_t)c;       // the lower cell id comes first
+        uint32_t pk = (ncell << 12) | ((uint32_t)second << 14) | ((uint32_t)r.ncol << 16);
+        for (int m = 0; m < 4; ++m) {
+            uint32_t pos = 7u;
+            if (comp[m] >= 0)
+                for (int s = 0; s < (int)r.ncol; ++s)
+                    if (r.colcomp[s] == comp[m]) pos = (uint32_t)s;
+            pk |= pos << (3 * m);
+        }
+        rec.pack[lf] = pk; rec.fpre[lf] = fprefix[comp[lf]]; rec.colpre[lf] = colprefix[comp[lf]];
+    }
+    rec.pad_[0] = rec.pad_[1] = 0;
+    out[c] = rec;
+}
+
+hipError_t asm_build_scatter_table(hipStream_t stream, const CondMesh &m, uint32_t ncells, const CondFace *faces, const uint32_t *colprefix,
+                                   const uint32_t *cprefix, const uint32_t *fprefix, AsmCellRec *out)
+{
+    if (ncells == 0) return hipSuccess;
+    hipLaunchKernelGGL(asm_scatter_table_kernel, dim3(blocks_for(ncells)), dim3(256), 0, stream, ncells, m.cell_faces, m.face_compress,
+                       cprefix, faces, colprefix, fprefix, out);
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : hipStreamSynchronize(stream);
+}
+
+// The entries with more than one contributor -- a face's own fbs x fbs block and its right-hand side -- are accumulated by
+// the scatter and start from zero; everything else in `values` is overwritten by exactly one store and is left alone.
+// One thread per accumulated entry: (face q, row k, column kp), kp == fbs: the right-hand side of row k.
+__global__ __launch_bounds__(256) void asm_zero_accumulated_kernel(AsmDims d, const CondFace *faces, const uint32_t *colprefix,
+                                                                   const uint32_t *fprefix, double *values, double *RHS)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t per = (uint32_t)(d.fbs * (d.fbs + 1));
+    const uint64_t q = t / per;
+    if (q >= d.nown) return;
+    const uint32_t k = (uint32_t)(t % per) / (uint32_t)(d.fbs + 1), kp = (uint32_t)(t % per) % (uint32_t)(d.fbs + 1);
+    if (kp == (uint32_t)d.fbs) {
+        if (RHS != nullptr) RHS[(uint64_t)d.cbs * d.ncells + q * d.fbs + k] = 0.0;
+        return;
+    }
+    const CondFace &r = faces[q];
+    const uint32_t ncell = (uint32_t)(r.cA >= 0) + (uint32_t)(r.cB >= 0);
+    const uint32_t R = ncell * d.cbs + (uint32_t)r.ncol * d.fbs;
+    for (int s = 0; s < (int)r.ncol; ++s)
+        if (r.colcomp[s] == (int32_t)q)
+            values[face_block_start(d, fprefix[q], colprefix[q]) + (uint64_t)k * R + ncell * d.cbs + (uint32_t)s * d.fbs + kp] = 0.0;
+}
+
+hipError_t asm_zero_accumulated(hipStream_t stream, int cbs, int fbs, uint32_t ncells, uint32_t nown, uint64_t cell_nnz,
+                                const CondFace *faces, const uint32_t *colprefix, const uint32_t *fprefix, double *values, double *RHS)
+{
+    if (nown == 0) return hipSuccess;
+    const AsmDims d = {cbs, fbs, cbs + 4 * fbs, ncells, nown, cell_nnz};
+    hipLaunchKernelGGL(asm_zero_accumulated_kernel, dim3(blocks_for((size_t)nown * fbs * (fbs + 1))), dim3(256), 0, stream, d, faces,
+                       colprefix, fprefix, values, RHS);
+    return hipGetLastError();
+}
+
 }  // namespace pa

@@ -116,6 +116,7 @@ struct pa_context {
     uint64_t cond_total_cols = 0;             // sum of the column-face counts of the owned faces
     // direct CSR of the assembler's own system (assembler_csr.hip): non-Dirichlet faces per cell / cells per face and their prefixes
     uint32_t *d_asm_nfc = nullptr, *d_asm_cprefix = nullptr, *d_asm_nfcell = nullptr, *d_asm_fprefix = nullptr;
+    pa::AsmCellRec *d_asm_scatter = nullptr;   // per cell, where the fused assembly's scatter writes (hho_asm_scatter.hpp)
     bool asm_ready = false;
     uint64_t asm_cell_faces_total = 0, asm_face_cells_total = 0;
     // cutHHO state (host tags + device copies)
@@ -179,6 +180,8 @@ static void release_faces(pa_context *ctx)
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
+    if (ctx->d_asm_scatter) (void)hipFree(ctx->d_asm_scatter);
+    ctx->d_asm_scatter = nullptr;
     ctx->asm_ready = false; ctx->asm_cell_faces_total = ctx->asm_face_cells_total = 0;
     ctx->structured = false;
 }
@@ -845,6 +848,9 @@ struct LocalOpsOut {
     bool cond = false;
     const double *rhs = nullptr, *uF = nullptr;
     double *cond_out = nullptr, *uT = nullptr;
+    // the assembling mode (on the condensed mode's instances): rhs in, the CSR arrays of scatter out, lc only if not null
+    bool assemble = false;
+    pa::AsmScatterArgs scatter = {nullptr, nullptr, nullptr, nullptr, 0, 0};
 };
 
 static int run_local_ops(pa_context *ctx, pa_degree_info di, int quad_kind, int stab_kind, size_t first, size_t n,
@@ -861,6 +867,7 @@ static int run_local_ops(pa_context *ctx, pa_degree_info di, int quad_kind, int 
     int grid = 0;
     const int st = select_kernel(ctx, di, quad_kind, stab_kind, n, &e, &grid, o.cond);
     if (st != PA_OK) return st;
+    if (o.assemble && !e->launch_asm) return PA_ERR_INVALID_DEGREE;
     if (n == 0) return PA_OK;
     uint32_t ablate = 0;
 #ifdef PA_TUNING      // stage ablation produces garbage operators on purpose: never in the shipped library
@@ -946,6 +953,7 @@ static int run_local_ops(pa_context *ctx, pa_degree_info di, int quad_kind, int 
         a.uT = o.uT ? o.uT + off * (size_t)sz.cbs : nullptr;
         a.ablate = ablate;
         a.dbg = nullptr;
+        a.scatter = o.scatter;
 #ifdef PA_STAGE_CLOCK
         // diagnostic build: per-stage shader clocks of the cooperative kernel, averaged over blocks, to stderr
         static long long *d_dbg = nullptr;
@@ -954,7 +962,7 @@ static int run_local_ops(pa_context *ctx, pa_degree_info di, int quad_kind, int 
         (void)hipMemsetAsync(d_dbg, 0, ndbg * sizeof(long long), ctx->stream);
         a.dbg = d_dbg;
 #endif
-        PA_HIP(ctx, (o.cond ? e->launch_cond : split ? e->launch_split : e->launch)(a, g, ctx->stream));
+        PA_HIP(ctx, (o.assemble ? e->launch_asm : o.cond ? e->launch_cond : split ? e->launch_split : e->launch)(a, g, ctx->stream));
 #ifdef PA_STAGE_CLOCK
         {
             std::vector<long long> h(ndbg);
@@ -1378,6 +1386,17 @@ static int asm_prepare(pa_context *ctx)
     uint32_t a = 0, b = 0;
     PA_HIP(ctx, hipMemcpy(&a, ctx->d_asm_cprefix + nc, sizeof(uint32_t), hipMemcpyDeviceToHost));
     PA_HIP(ctx, hipMemcpy(&b, ctx->d_asm_fprefix + nown, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    // the per-cell scatter table of the fused path: held by the context only once it is complete
+    pa::AsmCellRec *scatter = nullptr;
+    PA_HIP(ctx, hipMalloc((void **)&scatter, (nc ? (size_t)nc : 1) * sizeof(pa::AsmCellRec)));
+    const hipError_t es = pa::asm_build_scatter_table(ctx->stream, cond_mesh(ctx), nc, ctx->d_cfaces, ctx->d_prefix, ctx->d_asm_cprefix,
+                                                      ctx->d_asm_fprefix, scatter);
+    if (es != hipSuccess) {
+        (void)hipFree(scatter);
+        PA_HIP(ctx, es);
+    }
+    if (ctx->d_asm_scatter) (void)hipFree(ctx->d_asm_scatter);
+    ctx->d_asm_scatter = scatter;
     ctx->asm_cell_faces_total = a; ctx->asm_face_cells_total = b;
     ctx->asm_ready = true;
     return PA_OK;
@@ -1430,6 +1449,37 @@ int pa_assembler_csr_fill(pa_context *ctx, pa_degree_info di, const double *d_lc
                              ctx->cond_nown, cell_nnz, ctx->d_cfaces_lean, ctx->d_prefix, ctx->d_asm_cprefix, ctx->d_asm_fprefix, d_lc, d_rhs,
                              d_g, d_values, d_RHS));
     return PA_OK;
+}
+
+int pa_assembler_csr_assemble(pa_context *ctx, pa_degree_info di, int quad_kind, int stab_kind, const double *d_rhs, const double *d_g,
+                              double *d_values, double *d_RHS, double *d_lc, int32_t *d_info)
+{
+    if (!ctx || !d_values) return PA_ERR_INVALID_ARG;
+    if (stab_kind == PA_STAB_NONE) return PA_ERR_INVALID_ARG;      // as pa_condensed_ops_batch: its instances carry a stabilization
+    (void)hipSetDevice(ctx->device);
+    if (!ctx->d_points) return PA_ERR_NO_MESH;
+    // the refusals of pa_condensed_ops_batch for the pair, before anything is built or written
+    const pa::KernelEntry *e = nullptr;
+    int grid = 0;
+    int st = select_kernel(ctx, di, quad_kind, stab_kind, ctx->ncells, &e, &grid, true);
+    if (st != PA_OK) return st;
+    if (!e->launch_asm) return PA_ERR_INVALID_DEGREE;
+    st = asm_prepare(ctx);
+    if (st != PA_OK) return st;
+    if (ctx->side_pending) {                              // cut-cell work still out on the side stream
+        PA_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_side, 0));
+        ctx->side_pending = false;
+    }
+    uint64_t cell_nnz, nnz, nrows;
+    asm_sizes(ctx, di, &cell_nnz, &nnz, &nrows);
+    const int cbs = (di.cell_deg + 2) * (di.cell_deg + 1) / 2, fbs = di.face_deg + 1;
+    PA_HIP(ctx, pa::asm_zero_accumulated(ctx->stream, cbs, fbs, (uint32_t)ctx->ncells, ctx->cond_nown, cell_nnz, ctx->d_cfaces, ctx->d_prefix,
+                                         ctx->d_asm_fprefix, d_values, d_RHS));
+    LocalOpsOut o;
+    o.cond = true; o.assemble = true; o.rhs = d_rhs; o.lc = d_lc; o.info = d_info;
+    o.scatter.tab = ctx->d_asm_scatter; o.scatter.g = d_g; o.scatter.values = d_values; o.scatter.RHS = d_RHS;
+    o.scatter.cell_nnz = cell_nnz; o.scatter.ncells = ctx->ncells;
+    return run_local_ops(ctx, di, quad_kind, stab_kind, 0, ctx->ncells, o);
 }
 
 int pa_condensed_halo_pack(pa_context *ctx, pa_degree_info di, const double *d_cond, const double *d_g, double *d_halo)

@@ -37,6 +37,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "hho_asm_scatter.hpp"
 
 // minimum waves per SIMD the register allocator must leave room for (2nd __launch_bounds__
 // argument); 0 = per configuration (Cfg::WAVES)
@@ -429,6 +430,9 @@ struct LocalOpsArgs {
     // With the branches compiled out the k = 2 kernel spills 26 more VGPRs and runs 7 % slower (measured).
     uint32_t ablate;
     long long *dbg;            // -DPA_STAGE_CLOCK builds only
+    // assembling mode (MODE_ASM): where the image goes in the CSR arrays of the assembler's own system (hho_asm_scatter.hpp);
+    // reads rhs as the condensed mode does, and writes lc as well when it is not null
+    AsmScatterArgs scatter;
 };
 
 // index of the monomial bx^p by^r in the graded ordering (total degree, then r)  bases.hpp:114-128
@@ -1002,7 +1006,10 @@ __device__ __forceinline__ uint32_t sel4u(uint32_t v0, uint32_t v1, uint32_t v2,
 // MODE_COND:  lc never leaves the chip: the product lands in an LDS image and the cell unknowns are eliminated there
 //             (partial Cholesky of [lc f_T; f_T^T 0] over the cbs cell pivots); the packed Schur complement and the
 //             condensed right-hand side are the only output -- or, given the face unknowns, the recovered cell unknowns.
-enum { MODE_LC = 0, MODE_SPLIT = 1, MODE_COND = 2 };
+// MODE_ASM:   the condensed mode's pass up to the completed image; instead of the elimination a scatter epilogue writes the
+//             image's entries to their places in the CSR values and right-hand side of the assembler's own system
+//             (hho_asm_scatter.hpp), and lc itself only when asked for.
+enum { MODE_LC = 0, MODE_SPLIT = 1, MODE_COND = 2, MODE_ASM = 3 };
 // hho_pre.hpp: the head of one cell in the registers of the calling lane, its record to `out` (pairs 16 doubles apart)
 struct PreArgs {
     const QuadTables *tab;
@@ -1016,7 +1023,7 @@ __device__ __forceinline__ void cell_pre_record(const PreArgs &a, size_t cell, d
 template <class C, int MODE>
 __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::WAVES) void hho_local_ops_kernel(LocalOpsArgs a)
 {
-    constexpr bool SPLIT = MODE == MODE_SPLIT, COND = MODE == MODE_COND;
+    constexpr bool SPLIT = MODE == MODE_SPLIT, ASM = MODE == MODE_ASM, COND = MODE == MODE_COND || ASM;
     static_assert(COND == C::COND, "the condensed mode runs on the Cfg instance that reserves its LDS image");
     static_assert(!COND || (C::CBS + C::NF + 1 <= C::G && C::HAS_STAB), "condensed mode: one lane per row of [lc f_T; f_T^T 0]");
     constexpr int G = C::G, RBS = C::RBS, CBS = C::CBS, FBS = C::FBS, MS = C::MS, NR = C::NR, NF = C::NF;
@@ -2229,7 +2236,16 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
                     S[C::oOUT + (16 + cjc) + (16 + cic) * OS] = corner;
                 }
             }
-            if (COND) {
+            if constexpr (ASM) {
+                // ================= S9' (assembling mode): the image to its places in the global CSR system ==================
+                PA_MARK("S9a");
+                wave_sync();      // the image is complete
+                asm_scatter_cell<G, CBS, FBS, C::LDI>(a.scatter, S + C::oOUT, l, cell, valid, fT_l,
+                                                      a.lc != nullptr ? a.lc + rel(MS * MS) : nullptr);
+                PA_TICK(13);
+                wave_sync();      // every read of the image is done
+                if (C::USE_PRE && !C::COND_OWN_P && (!SELF || ib + 1 < nbc)) { rec_deposit(); wave_sync(); }
+            } else if (COND) {
                 // ================= S9 (condensed mode): eliminate the cell unknowns in the LDS image ==================
                 // Row i of the symmetric (MS + 1) x (MS + 1) matrix  M = [A_TT A_TF f_T; A_FT A_FF 0; f_T^T 0 0]  belongs to
                 // lane i.  The first CBS steps of its Cholesky factorization, row by row (left-looking, Eigen's LLT order on

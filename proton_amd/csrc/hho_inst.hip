@@ -9,7 +9,7 @@
 #define PA_STR2(x) #x
 #define PA_STR(x) PA_STR2(x)
 #define PA_CAT5(a, b, c, d, e) pa_entries_##a##_##b##_##c
-#define PA_COND_NONE nullptr, nullptr, 0, nullptr, 0
+#define PA_COND_NONE nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr
 // (the condensed mode needs a lane per row of [lc f_T; f_T^T 0]: msize + 1 <= G)
 #define PA_COND_OF(STAB, G)                                                                         \
     (pa::Cfg<PA_CD, PA_FD, PA_QUAD, STAB, G>::MS + 1 <= G)                                          \
@@ -18,7 +18,13 @@
     (const void *)&pa::hho_local_ops_kernel<pa::Cfg<PA_CD, PA_FD, PA_QUAD, STAB, (pa::Cfg<PA_CD, PA_FD, PA_QUAD, STAB, G>::MS + 1 <= G ? G : 64), 1>, pa::MODE_COND>, \
     (int)(pa::Cfg<PA_CD, PA_FD, PA_QUAD, STAB, (pa::Cfg<PA_CD, PA_FD, PA_QUAD, STAB, G>::MS + 1 <= G ? G : 64), 1>::LDS_DOUBLES * sizeof(double)), \
     "hho_condensed_ops<cd=" PA_STR(PA_CD) ",fd=" PA_STR(PA_FD) ",quad=" PA_STR(PA_QUAD) ",stab=" #STAB ",G=" #G ">", \
-    pa::Cfg<PA_CD, PA_FD, PA_QUAD, STAB, (pa::Cfg<PA_CD, PA_FD, PA_QUAD, STAB, G>::MS + 1 <= G ? G : 64), 1>::WAVES
+    pa::Cfg<PA_CD, PA_FD, PA_QUAD, STAB, (pa::Cfg<PA_CD, PA_FD, PA_QUAD, STAB, G>::MS + 1 <= G ? G : 64), 1>::WAVES, \
+    /* the assembling mode: the same instance and LDS image, the scatter epilogue of hho_asm_scatter.hpp behind the product */ \
+    (pa::Cfg<PA_CD, PA_FD, PA_QUAD, STAB, G>::MS + 1 <= G)                                          \
+        ? &pa::launch_local_ops<pa::Cfg<PA_CD, PA_FD, PA_QUAD, STAB, (pa::Cfg<PA_CD, PA_FD, PA_QUAD, STAB, G>::MS + 1 <= G ? G : 64), 1>, pa::MODE_ASM> \
+        : nullptr,                                                                                  \
+    (const void *)&pa::hho_local_ops_kernel<pa::Cfg<PA_CD, PA_FD, PA_QUAD, STAB, (pa::Cfg<PA_CD, PA_FD, PA_QUAD, STAB, G>::MS + 1 <= G ? G : 64), 1>, pa::MODE_ASM>, \
+    "hho_assemble_ops<cd=" PA_STR(PA_CD) ",fd=" PA_STR(PA_FD) ",quad=" PA_STR(PA_QUAD) ",stab=" #STAB ",G=" #G ">"
 // the thread-per-cell kernel of the small pairs (msize <= 9: (0,0), (1,0), (0,1)); instantiated for those only
 #if (PA_CD + 2) * (PA_CD + 1) / 2 + 4 * (PA_FD + 1) <= 9
 #define PA_SMALL_OF(STAB, G) &pa::launch_small_ops<pa::Cfg<PA_CD, PA_FD, PA_QUAD, STAB, G>>

@@ -30,6 +30,10 @@ struct KernelEntry {
     int lds_bytes_cond;
     const char *name_cond;
     int waves_per_simd_cond;
+    // assembling mode (MODE_ASM): the condensed mode's instance, LDS size and occupancy with the scatter epilogue
+    local_ops_launcher launch_asm;
+    const void *func_asm;
+    const char *name_asm;
 };
 
 template <class C, int MODE>

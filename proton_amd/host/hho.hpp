@@ -1007,6 +1007,37 @@ class assembler {
         for (size_t k = 0; k < rr.size(); ++k)
             if (rr[k] >= 0) RHS[rr[k]] += rv[k];
     }
+
+    // The same loop with the assembly inside the local-operator pass, as the reference has it (hho.hpp:344-406 run in the
+    // iteration that formed the local matrix): Dirichlet data, cell right-hand sides and the CSR pattern, then
+    // pa_assembler_csr_assemble writes values and right-hand side from the kernel's on-chip image of lc.  No ncells x msize^2
+    // buffer, no triplets.  LHS and RHS are downloaded; finalize() is a no-op afterwards.
+    void assemble_all_fused(const Mesh &msh, int stab_kind, int rhs_fn, int dirichlet_fn)
+    {
+        auto &dev = proton_amd::device::instance();
+        proton_amd::batch_cache<Mesh>::instance().ensure_mesh(msh);
+        pa_sizes sz;
+        dev.check(pa_sizes_for(di.c_abi(), Mesh::pa_quadrature, &sz), "pa_sizes_for");
+        const size_t n = msh.cells.size();
+        pa_assembler_csr_info info;
+        dev.check(pa_assembler_csr_query(dev.ctx(), di.c_abi(), &info), "pa_assembler_csr_query");
+        if (info.nrows != RHS.size()) throw std::runtime_error("assemble_all_fused: the device numbers another system than this assembler");
+        const size_t nnz = info.nnz;
+        proton_amd::device_buffer<double> d_rhs(n * sz.cbs), d_g(msh.faces.size() * sz.fbs), d_values(nnz ? nnz : 1), d_RHS(RHS.size() ? RHS.size() : 1);
+        proton_amd::device_buffer<int64_t> d_rowptr(RHS.size() + 1);
+        proton_amd::device_buffer<int32_t> d_colind(nnz ? nnz : 1);
+        dev.check(pa_dirichlet_data_batch(dev.ctx(), (int)di.face_degree(), dirichlet_fn, nullptr, d_g.get()), "pa_dirichlet_data_batch");
+        dev.check(pa_cell_rhs_batch(dev.ctx(), (int)di.cell_degree(), 0, Mesh::pa_quadrature, rhs_fn, nullptr, 0, n, d_rhs.get()), "pa_cell_rhs_batch");
+        dev.check(pa_assembler_csr_pattern(dev.ctx(), di.c_abi(), d_rowptr.get(), d_colind.get()), "pa_assembler_csr_pattern");
+        dev.check(pa_assembler_csr_assemble(dev.ctx(), di.c_abi(), Mesh::pa_quadrature, stab_kind, d_rhs.get(), d_g.get(), d_values.get(),
+                                            d_RHS.get(), nullptr, nullptr), "pa_assembler_csr_assemble");
+        LHS.nrows = LHS.ncols = RHS.size();
+        LHS.rowptr.resize(RHS.size() + 1); LHS.colind.resize(nnz); LHS.values.resize(nnz);
+        d_rowptr.download(LHS.rowptr.data(), LHS.rowptr.size());
+        if (nnz) { d_colind.download(LHS.colind.data(), nnz); d_values.download(LHS.values.data(), nnz); }
+        if (!RHS.empty()) d_RHS.download(RHS.data(), RHS.size());
+        device_csr_ = true;
+    }
 };
 
 template <typename Mesh>
