@@ -569,6 +569,59 @@ int pa_interface_condensed_csr_fill(pa_context *ctx, int face_deg, const double 
 int pa_interface_condensed_recover(pa_context *ctx, int face_deg, const double *d_lc, const double *d_rhs, const double *d_lc_cut,
                                    const double *d_rhs_cut, const double *d_g, const double *d_xF, double *d_full);
 
+/* The face-only system of interface_assembler assembled and solved BY ROW SLABS (cuthho_square.cpp:1142-1178 the numbering,
+ * :1203-1354 the assembly, :1664-1743 the loop and the solve; the reference has one process).  The context is one of
+ * pa_cut_preprocess_rows -- rank r holds cell rows [row_begin, row_end) -- or of pa_cut_preprocess, the one-slab case.  Every rank
+ * runs the same whole-mesh host preprocessing, so the first block of any cell or face is a prefix count it can take itself (:1142-1163);
+ * no table moves between ranks.  Faces are ordered by (low point, high point): the faces whose low point lies in the slab's node
+ * rows -- the bottom and vertical faces of its cell rows -- are one contiguous range of face blocks, the OWNED rows
+ * [row_begin, row_end) of the system.  An owned bottom face takes addends from the cell below it, on the rank below: the one thing a
+ * step moves is the records of a slab's top cell row, one slab up (pa_comm_halo_exchange_start).  The slabs' rows stacked are
+ * pa_interface_condensed_csr_*'s system of the whole mesh BIT FOR BIT; so are the records and the recovered cell unknowns.
+ *   _partition_info: the info of a slab from the mesh parameters alone: host only, no context, no device.
+ *   _query: the same from the context (nnz_owned from its symbolic tables).
+ *   _ops_batch: pa_interface_condensed_ops_batch on the slab's cells: d_cond ncells x cond_doubles [S of every cell | g of every
+ *     cell], d_cond_cut ncut x cond_cut_doubles, of the outputs of pa_cut_interface_uncut_batch / pa_cut_interface_ops_batch on
+ *     the slab; the info conventions unchanged.
+ *   _halo_pack: what the slab above needs, halo_send_doubles doubles into d_halo, ordered on the context's stream: [S of the top
+ *     row's halo_send_cells cells | their g | S of its halo_send_cut cut cells | their g | halo_send_cells x nf boundary values:
+ *     d_g of each cell's four faces in local order, zero where a face is not Dirichlet (d_g NULL: all zero)].  Nothing on the top
+ *     slab.  d_g is indexed by the context's own faces (pa_dirichlet_data_batch on the slab).
+ *   _csr_pattern / _csr_fill: the owned rows in CSR: d_rowptr nrows_owned + 1 LOCAL (starts at 0), d_colind nnz_owned GLOBAL column
+ *     ids of the face-only system, ascending within a row (may be NULL) -- the form pa_conjugated_gradient_rows takes; d_values
+ *     nnz_owned; d_rhs nrows_owned (may be NULL).  d_halo_below: the _halo_pack output of the slab below (NULL on slab 0).  The
+ *     Dirichlet columns of an uncut cell go to the right-hand side (g_i - sum_j S_ij u_D,j), a halo cell's with the boundary values
+ *     of the halo: the same sum of the same numbers as on the whole mesh.
+ *   _recover: u_T = A_TT^-1 (f_T - A_TF u_F) of the slab's cells (pa_interface_condensed_recover's arithmetic).  d_xF: the face
+ *     solution over [row_begin, col_end), its tail beyond row_end received from the rank above
+ *     (pa_comm_neighbour_exchange_start); d_uT: the slab's cell blocks [cell_block_begin, cell_block_end), cbs doubles each,
+ *     contiguous in the full numbering.
+ * The refusals, in this order: face_deg outside 0..3 (PA_ERR_INVALID_DEGREE); no cut mesh (PA_ERR_NO_MESH); system_size >= 2^31;
+ * the cut-cell arrays missing while the slab has cut cells; d_halo_below missing while the slab has a row below.  Pending
+ * side-stream work (pa_context_set_cut_overlap) is joined first.  The pa_interface_* entry points above keep refusing a slab. */
+typedef struct {
+    uint64_t system_size;                        /* of the whole mesh's face-only system */
+    uint64_t row_begin, row_end, nnz_owned;      /* the owned rows and their entries */
+    uint64_t col_begin, col_end;                 /* the columns the owned rows read; _recover reads [row_begin, col_end) */
+    uint64_t cell_block_begin, cell_block_end;   /* the slab's cell blocks in interface_assembler's full numbering */
+    int32_t nf, NF;                              /* face unknowns of an uncut / cut cell */
+    int32_t cond_doubles, cond_cut_doubles;      /* doubles per uncut / cut record */
+    uint64_t halo_send_cells, halo_send_cut, halo_send_doubles;     /* sent up: 0 on the top slab */
+    uint64_t halo_recv_cells, halo_recv_cut, halo_recv_doubles;     /* received from below: 0 on slab 0 */
+} pa_interface_rows_info;
+int pa_interface_rows_partition_info(size_t Nx, size_t Ny, double min_x, double max_x, double min_y, double max_y, const pa_level_set *ls,
+                                     int refsteps, size_t row_begin, size_t row_end, int face_deg, pa_interface_rows_info *out);
+int pa_interface_rows_query(pa_context *ctx, int face_deg, pa_interface_rows_info *out);
+int pa_interface_rows_ops_batch(pa_context *ctx, int face_deg, const double *d_lc, const double *d_rhs, const double *d_lc_cut,
+                                const double *d_rhs_cut, double *d_cond, double *d_cond_cut, int32_t *d_info, int32_t *d_info_cut);
+int pa_interface_rows_halo_pack(pa_context *ctx, int face_deg, const double *d_cond, const double *d_cond_cut, const double *d_g,
+                                double *d_halo);
+int pa_interface_rows_csr_pattern(pa_context *ctx, int face_deg, int64_t *d_rowptr, int32_t *d_colind);
+int pa_interface_rows_csr_fill(pa_context *ctx, int face_deg, const double *d_cond, const double *d_cond_cut, const double *d_g,
+                               const double *d_halo_below, double *d_values, double *d_rhs);
+int pa_interface_rows_recover(pa_context *ctx, int face_deg, const double *d_lc, const double *d_rhs, const double *d_lc_cut,
+                              const double *d_rhs_cut, const double *d_g, const double *d_xF, double *d_uT);
+
 /* ---- multi-GPU exchange: one process per GPU, RCCL over xGMI ------------
  * The reference is a single process without any communication.  Cells shard by rows (pa_mesh_generate's
  * row_begin / row_end); every rank assembles the CSR rows of the faces it owns (pa_condensed_csr_fill), and the only

@@ -518,6 +518,63 @@ class BatchAssembler:
                                              _ptr(ops.get("rhs_cut")), _ptr(g), xF.data_ptr(), full.data_ptr())
         return full[:info.system_size]
 
+    # ---- the same by row slabs: a context of cut_preprocess(rows=...), or the whole mesh as one slab ----
+    def interface_rows_info(self, fd):
+        """pa_interface_rows_query: the slab's owned rows, column window, cell blocks and halo sizes"""
+        return self.ctx.interface_rows_query(fd)
+
+    def interface_rows_ops(self, fd, ops):
+        """interface_condensed_ops on the slab's cells (ops: interface_local_ops on the slab) -> the same dict"""
+        qi = self.ctx.interface_rows_query(fd)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        out = {"cond": torch.empty(max(self.ncells * qi.cond_doubles, 1), **f64),
+               "cond_cut": torch.empty(max(self.ncut * qi.cond_cut_doubles, 1), **f64),
+               "info": torch.empty(max(self.ncells, 1), **i32), "info_cut": torch.empty(max(self.ncut, 1), **i32)}
+        self.ctx.interface_rows_ops(fd, ops["lc"].data_ptr(), _ptr(ops.get("rhs")), _ptr(ops.get("lc_cut")), _ptr(ops.get("rhs_cut")),
+                                    out["cond"].data_ptr(), out["cond_cut"].data_ptr(), out["info"].data_ptr(), out["info_cut"].data_ptr())
+        out["cond"] = out["cond"][:self.ncells * qi.cond_doubles]
+        out["cond_cut"] = out["cond_cut"][:self.ncut * qi.cond_cut_doubles]
+        out["info"], out["info_cut"] = out["info"][:self.ncells], out["info_cut"][:self.ncut]
+        return out
+
+    def interface_rows_halo_pack(self, fd, rec, g=None, halo=None):
+        """the top cell row's records and boundary values for the slab above -> [halo_send_doubles] (empty on the top slab)"""
+        qi = self.ctx.interface_rows_query(fd)
+        if halo is None:
+            halo = torch.empty(max(qi.halo_send_doubles, 1), dtype=torch.float64, device=self.device)
+        self.ctx.interface_rows_halo_pack(fd, rec["cond"].data_ptr(), _ptr(rec.get("cond_cut")), _ptr(g), halo.data_ptr())
+        return halo[:qi.halo_send_doubles]
+
+    def interface_rows_csr_pattern(self, fd):
+        """the owned rows of the face-only system -> (rowptr int64 [nrows_owned+1] local, colind int32 [nnz_owned] global)"""
+        qi = self.ctx.interface_rows_query(fd)
+        rowptr = torch.empty(qi.row_end - qi.row_begin + 1, dtype=torch.int64, device=self.device)
+        colind = torch.empty(max(qi.nnz_owned, 1), dtype=torch.int32, device=self.device)
+        self.ctx.interface_rows_csr_pattern(fd, rowptr.data_ptr(), colind.data_ptr())
+        return rowptr, colind[:qi.nnz_owned]
+
+    def interface_rows_csr_fill(self, fd, rec, g=None, halo_below=None, values=None, RHS=None):
+        """numeric phase of the same from interface_rows_ops' dict and the halo of the slab below -> (values [nnz_owned], RHS [nrows_owned])"""
+        qi = self.ctx.interface_rows_query(fd)
+        n = qi.row_end - qi.row_begin
+        if values is None:
+            values = torch.empty(max(qi.nnz_owned, 1), dtype=torch.float64, device=self.device)
+        if RHS is None:
+            RHS = torch.empty(max(n, 1), dtype=torch.float64, device=self.device)
+        self.ctx.interface_rows_csr_fill(fd, rec["cond"].data_ptr(), _ptr(rec.get("cond_cut")), _ptr(g), _ptr(halo_below), values.data_ptr(),
+                                         RHS.data_ptr())
+        return values[:qi.nnz_owned], RHS[:n]
+
+    def interface_rows_recover(self, fd, ops, xF, g=None):
+        """the slab's cell unknowns from the face solution over [row_begin, col_end) -> [(cell_block_end - cell_block_begin) * cbs]"""
+        qi = self.ctx.interface_rows_query(fd)
+        n = (qi.cell_block_end - qi.cell_block_begin) * ((fd + 3) * (fd + 2) // 2)
+        uT = torch.empty(max(n, 1), dtype=torch.float64, device=self.device)
+        self.ctx.interface_rows_recover(fd, ops["lc"].data_ptr(), _ptr(ops.get("rhs")), _ptr(ops.get("lc_cut")), _ptr(ops.get("rhs_cut")),
+                                        _ptr(g), xF.data_ptr(), uT.data_ptr())
+        return uT[:n]
+
     def interface_cell_offsets(self, fd):
         out = torch.empty((self.ncells, 2), dtype=torch.int64, device=self.device)
         self.ctx.interface_cell_offsets(fd, out.data_ptr())

@@ -36,6 +36,8 @@ EXPORTS = [
     "pa_interface_csr_query", "pa_interface_csr_pattern", "pa_interface_csr_fill",
     "pa_interface_condensed_query", "pa_interface_condensed_ops_batch", "pa_interface_condensed_triplets_batch",
     "pa_interface_condensed_csr_pattern", "pa_interface_condensed_csr_fill", "pa_interface_condensed_recover",
+    "pa_interface_rows_partition_info", "pa_interface_rows_query", "pa_interface_rows_ops_batch", "pa_interface_rows_halo_pack",
+    "pa_interface_rows_csr_pattern", "pa_interface_rows_csr_fill", "pa_interface_rows_recover",
     "pa_condensed_ops_batch", "pa_condensed_recover_batch", "pa_condensed_query", "pa_condensed_triplets_batch",
     "pa_assembler_csr_query", "pa_assembler_csr_pattern", "pa_assembler_csr_fill", "pa_assembler_csr_assemble",
     "pa_condensed_csr_pattern", "pa_condensed_csr_fill", "pa_condensed_halo_pack", "pa_condensed_take_faces",
@@ -92,6 +94,14 @@ class AssemblerCsrInfo(C.Structure):
 class InterfaceCondensedInfo(C.Structure):
     _fields_ = [("system_size", C.c_uint64), ("nnz", C.c_uint64), ("nf", C.c_int32), ("NF", C.c_int32),
                 ("cond_doubles", C.c_int32), ("cond_cut_doubles", C.c_int32)]
+
+
+class InterfaceRowsInfo(C.Structure):
+    _fields_ = [("system_size", C.c_uint64), ("row_begin", C.c_uint64), ("row_end", C.c_uint64), ("nnz_owned", C.c_uint64),
+                ("col_begin", C.c_uint64), ("col_end", C.c_uint64), ("cell_block_begin", C.c_uint64), ("cell_block_end", C.c_uint64),
+                ("nf", C.c_int32), ("NF", C.c_int32), ("cond_doubles", C.c_int32), ("cond_cut_doubles", C.c_int32),
+                ("halo_send_cells", C.c_uint64), ("halo_send_cut", C.c_uint64), ("halo_send_doubles", C.c_uint64),
+                ("halo_recv_cells", C.c_uint64), ("halo_recv_cut", C.c_uint64), ("halo_recv_doubles", C.c_uint64)]
 
 
 class CondensedInfo(C.Structure):
@@ -211,6 +221,14 @@ def lib():
     L.pa_interface_condensed_csr_pattern.argtypes = [vp, C.c_int, dp, dp]
     L.pa_interface_condensed_csr_fill.argtypes = [vp, C.c_int] + [dp] * 5
     L.pa_interface_condensed_recover.argtypes = [vp, C.c_int] + [dp] * 7
+    L.pa_interface_rows_partition_info.argtypes = [sz, sz, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(LevelSet), C.c_int, sz, sz,
+                                                   C.c_int, C.POINTER(InterfaceRowsInfo)]
+    L.pa_interface_rows_query.argtypes = [vp, C.c_int, C.POINTER(InterfaceRowsInfo)]
+    L.pa_interface_rows_ops_batch.argtypes = [vp, C.c_int] + [dp] * 8
+    L.pa_interface_rows_halo_pack.argtypes = [vp, C.c_int] + [dp] * 4
+    L.pa_interface_rows_csr_pattern.argtypes = [vp, C.c_int, dp, dp]
+    L.pa_interface_rows_csr_fill.argtypes = [vp, C.c_int] + [dp] * 6
+    L.pa_interface_rows_recover.argtypes = [vp, C.c_int] + [dp] * 7
     L.pa_condensed_ops_batch.argtypes = [vp, DegreeInfo, C.c_int, C.c_int, sz, sz, dp, dp, dp]
     L.pa_condensed_recover_batch.argtypes = [vp, DegreeInfo, C.c_int, C.c_int, sz, sz, dp, dp, dp, dp]
     L.pa_condensed_query.argtypes = [vp, DegreeInfo, C.POINTER(CondensedInfo)]
@@ -252,6 +270,16 @@ def sizes_for(di, quad):
     if st != 0:
         raise ProtonAmdError(st, "pa_sizes_for")
     return s
+
+
+def interface_rows_partition_info(Nx, Ny, ls, refsteps, rows, face_deg, lo=(0.0, 0.0), hi=(1.0, 1.0)):
+    """the slab `rows` of the interface problem's face-only system from the mesh parameters alone (no context, no device)"""
+    out = InterfaceRowsInfo()
+    st = lib().pa_interface_rows_partition_info(Nx, Ny, lo[0], hi[0], lo[1], hi[1], C.byref(ls), refsteps, rows[0], rows[1], face_deg,
+                                                C.byref(out))
+    if st != 0:
+        raise ProtonAmdError(st, "pa_interface_rows_partition_info")
+    return out
 
 
 def condensed_partition_info(Nx, Ny, rows, di):
@@ -550,6 +578,27 @@ class Context:
     def interface_condensed_recover(self, face_deg, lc, rhs, lc_cut, rhs_cut, g, xF, full):
         self._ck(self._L.pa_interface_condensed_recover(self.h, face_deg, lc, rhs, lc_cut, rhs_cut, g, xF, full),
                  "pa_interface_condensed_recover")
+
+    def interface_rows_query(self, face_deg):
+        out = InterfaceRowsInfo()
+        self._ck(self._L.pa_interface_rows_query(self.h, face_deg, C.byref(out)), "pa_interface_rows_query")
+        return out
+
+    def interface_rows_ops(self, face_deg, lc, rhs, lc_cut, rhs_cut, cond, cond_cut, info, info_cut):
+        self._ck(self._L.pa_interface_rows_ops_batch(self.h, face_deg, lc, rhs, lc_cut, rhs_cut, cond, cond_cut, info, info_cut),
+                 "pa_interface_rows_ops_batch")
+
+    def interface_rows_halo_pack(self, face_deg, cond, cond_cut, g, halo):
+        self._ck(self._L.pa_interface_rows_halo_pack(self.h, face_deg, cond, cond_cut, g, halo), "pa_interface_rows_halo_pack")
+
+    def interface_rows_csr_pattern(self, face_deg, rowptr, colind):
+        self._ck(self._L.pa_interface_rows_csr_pattern(self.h, face_deg, rowptr, colind), "pa_interface_rows_csr_pattern")
+
+    def interface_rows_csr_fill(self, face_deg, cond, cond_cut, g, halo_below, values, rhs):
+        self._ck(self._L.pa_interface_rows_csr_fill(self.h, face_deg, cond, cond_cut, g, halo_below, values, rhs), "pa_interface_rows_csr_fill")
+
+    def interface_rows_recover(self, face_deg, lc, rhs, lc_cut, rhs_cut, g, xF, uT):
+        self._ck(self._L.pa_interface_rows_recover(self.h, face_deg, lc, rhs, lc_cut, rhs_cut, g, xF, uT), "pa_interface_rows_recover")
 
     def cut_preprocess(self, Nx, Ny, ls, refsteps, lo=(0.0, 0.0), hi=(1.0, 1.0), rows=None):
         if rows is None:

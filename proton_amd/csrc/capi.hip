@@ -16,6 +16,7 @@
 #include "condensed.hpp"
 #include "assembler_csr.hpp"
 #include "interface_csr.hpp"
+#include "interface_rows.hpp"
 #include "cut_host.hpp"
 #include "hho_assembly.hpp"
 #include "hho_aux.hpp"
@@ -137,6 +138,17 @@ struct pa_context {
     // direct CSR of the interface_assembler's system (interface_csr.hip): row groups and column units of one face degree, built on
     // first use, dropped with the cut mesh
     pa::IfCsrTables ifcsr;
+    // the numbering of the context's slab with the cell row below it (interface_rows.hpp) on the device and the symbolic tables
+    // over it (pa_interface_rows_*); fields of their own: d_if_cell_table stays a whole-mesh context's.  Built on first use.
+    struct IfRowsDev {
+        bool ready = false;
+        pa::IfRowsHost h;                         // the counts (its tables are dropped after the upload)
+        uint32_t *cell_faces = nullptr;
+        int8_t *cell_loc = nullptr, *face_loc = nullptr;
+        int32_t *cut_index = nullptr, *cell_table = nullptr, *face_table = nullptr, *cell_table_slab = nullptr, *face_table_slab = nullptr;
+        pa::IfCsrTables tables;
+        uint64_t v0 = 0, nnz = 0;                 // first entry of the owned rows in the tables' cvstart; entries of the owned rows
+    } ifrows;
     // scratch of pa_cut_interface_ops_batch ([data | stab- | stab+] of the cut cells), kept between calls
     double *d_if_scratch = nullptr;
     size_t if_scratch_cap = 0;                // doubles
@@ -211,6 +223,11 @@ static void release_cut(pa_context *ctx)
     ctx->d_if_cell_table = ctx->d_if_face_table = nullptr;
     ctx->if_num_all_cells = ctx->if_num_other_faces = 0;
     pa::ifcsr_release(&ctx->ifcsr);
+    pa::ifcsr_release(&ctx->ifrows.tables);
+    (void)hipFree(ctx->ifrows.cell_faces); (void)hipFree(ctx->ifrows.cell_loc); (void)hipFree(ctx->ifrows.face_loc);
+    (void)hipFree(ctx->ifrows.cut_index); (void)hipFree(ctx->ifrows.cell_table); (void)hipFree(ctx->ifrows.face_table);
+    (void)hipFree(ctx->ifrows.cell_table_slab); (void)hipFree(ctx->ifrows.face_table_slab);
+    ctx->ifrows = pa_context::IfRowsDev();
 }
 
 static void release_mesh(pa_context *ctx)
@@ -2147,6 +2164,9 @@ static pa::IfCondArgs ifcond_args(const pa_context *ctx, const double *d_cond, c
     return a;
 }
 
+static int interface_records(pa_context *ctx, int face_deg, const double *d_lc, const double *d_rhs, const double *d_lc_cut,
+                             const double *d_rhs_cut, double *d_cond, double *d_cond_cut, int32_t *d_info, int32_t *d_info_cut);
+
 int pa_interface_condensed_query(pa_context *ctx, int face_deg, pa_interface_condensed_info *out)
 {
     if (!ctx || !out) return PA_ERR_INVALID_ARG;
@@ -2168,18 +2188,7 @@ int pa_interface_condensed_ops_batch(pa_context *ctx, int face_deg, const double
     if (!ctx || !d_lc || !d_cond) return PA_ERR_INVALID_ARG;
     const int st = ifcsr_prepare(ctx, face_deg, d_lc_cut != nullptr && d_cond_cut != nullptr);
     if (st != PA_OK) return st;
-    const size_t n = ctx->ncells, ncut = ctx->cut->cut_cells.size();
-    const int nf = 4 * (face_deg + 1), ntri = nf * (nf + 1) / 2;
-    const pa_degree_info di = {face_deg + 1, face_deg, face_deg + 1};
-    // the uncut cells: the plain mesh's static condensation of every row of d_lc (rows of cut cells included, never read back)
-    const int sc = condense(ctx, di, n, d_lc, d_rhs, d_cond, d_cond + n * (size_t)ntri, nullptr, d_info, 1);
-    if (sc != PA_OK) return sc;
-    PA_HIP(ctx, pa::ifcond_info_remap(ctx->stream, n, d_info));
-    if (ncut) {
-        const size_t blocks = (size_t)ctx->num_cus * 8;
-        PA_HIP(ctx, pa::ifcond_cut_records(ctx->stream, face_deg, (int)blocks, (uint32_t)ncut, d_lc_cut, d_rhs_cut, d_cond_cut, d_info_cut));
-    }
-    return PA_OK;
+    return interface_records(ctx, face_deg, d_lc, d_rhs, d_lc_cut, d_rhs_cut, d_cond, d_cond_cut, d_info, d_info_cut);
 }
 
 int pa_interface_condensed_triplets_batch(pa_context *ctx, int face_deg, const double *d_cond, const double *d_cond_cut, const double *d_g,
@@ -2224,6 +2233,226 @@ int pa_interface_condensed_recover(pa_context *ctx, int face_deg, const double *
     if (st != PA_OK) return st;
     PA_HIP(ctx, pa::ifcond_recover(ctx->stream, ifcsr_mesh(ctx), face_deg, ctx->num_cus * 16, ifcond_args(ctx, nullptr, nullptr, d_g), d_lc,
                                    d_rhs, d_lc_cut, d_rhs_cut, d_xF, d_full));
+    return PA_OK;
+}
+
+// ---- the face-only system by row slabs (pa_interface_rows_*): a context of pa_cut_preprocess_rows, or of pa_cut_preprocess as
+// the one-slab case.  The numbering of the slab comes from the whole-mesh tags every rank holds (interface_rows.hpp). ----
+static void ifrows_info_fill(const pa::IfRowsHost &h, int face_deg, uint64_t nnz, pa_interface_rows_info *out)
+{
+    const uint64_t fbs = (uint64_t)face_deg + 1, nf = 4 * fbs, NF = 8 * fbs;
+    const uint64_t rec = nf * (nf + 1) / 2 + nf, rec_cut = NF * (NF + 1) / 2 + NF;
+    out->system_size = fbs * h.face_blocks;
+    out->row_begin = fbs * (h.fb0 + h.q0);
+    out->row_end = fbs * (h.fb0 + h.q1);
+    out->nnz_owned = nnz;
+    out->col_begin = fbs * h.col_block0;
+    out->col_end = fbs * h.col_block1;
+    out->cell_block_begin = h.cell_block0;
+    out->cell_block_end = h.cell_block1;
+    out->nf = (int32_t)nf; out->NF = (int32_t)NF;
+    out->cond_doubles = (int32_t)rec; out->cond_cut_doubles = (int32_t)rec_cut;
+    out->halo_send_cells = h.ns; out->halo_send_cut = h.nsc;
+    out->halo_send_doubles = h.ns * (rec + nf) + h.nsc * rec_cut;
+    out->halo_recv_cells = h.nh; out->halo_recv_cut = h.nhc;
+    out->halo_recv_doubles = h.nh * (rec + nf) + h.nhc * rec_cut;
+}
+
+int pa_interface_rows_partition_info(size_t Nx, size_t Ny, double min_x, double max_x, double min_y, double max_y, const pa_level_set *ls,
+                                     int refsteps, size_t row_begin, size_t row_end, int face_deg, pa_interface_rows_info *out)
+{
+    if (face_deg < 0 || face_deg > 3) return PA_ERR_INVALID_DEGREE;
+    if (!out || !ls || refsteps < 0 || refsteps > 10 || (ls->kind != 0 && ls->kind != 1)) return PA_ERR_INVALID_ARG;
+    if (Nx == 0 || Ny == 0 || row_begin >= row_end || row_end > Ny || (Nx + 1) * (Ny + 1) >= ((size_t)1 << 32)) return PA_ERR_INVALID_ARG;
+    pa::CutMeshHost cm;
+    pa::IfRowsHost h;
+    try {
+        pa::cut_preprocess(cm, (uint32_t)Nx, (uint32_t)Ny, min_x, max_x, min_y, max_y, {ls->kind, ls->radius, ls->alpha, ls->beta, ls->cut_y},
+                           refsteps, true);
+        pa::if_rows_numbering(cm, (uint32_t)row_begin, (uint32_t)row_end, false, h);
+    } catch (const std::exception &) {
+        return PA_ERR_INVALID_ARG;
+    }
+    const uint64_t fbs = (uint64_t)face_deg + 1;
+    ifrows_info_fill(h, face_deg, h.nnz_blocks * fbs * fbs, out);
+    return PA_OK;
+}
+
+static pa::IfCsrMesh ifrows_mesh(const pa_context *ctx)
+{
+    const auto &r = ctx->ifrows;
+    pa::IfCsrMesh m;
+    m.cell_faces = r.cell_faces; m.cell_loc = r.cell_loc; m.face_loc = r.face_loc; m.cut_index = r.cut_index;
+    m.cell_table = r.cell_table; m.face_table = r.face_table;
+    m.ncells = r.h.ne; m.nfaces = r.h.nfe;
+    m.num_all_cells = r.h.num_all_cells; m.num_other_faces = r.h.num_other_faces;
+    return m;
+}
+
+// the slab alone, by the context's own cell and face ids, blocks counted from the slab's first: what ifcond_recover walks (no face
+// blocks to copy)
+static pa::IfCsrMesh ifrows_slab_mesh(const pa_context *ctx)
+{
+    const auto &r = ctx->ifrows;
+    pa::IfCsrMesh m;
+    m.cell_faces = ctx->d_cell_faces; m.cell_loc = ctx->d_cell_loc; m.face_loc = r.face_loc + r.h.fshift; m.cut_index = ctx->d_cut_index;
+    m.cell_table = r.cell_table_slab; m.face_table = r.face_table_slab;
+    m.ncells = (uint32_t)ctx->ncells; m.nfaces = r.h.nfe - r.h.fshift;
+    m.num_all_cells = (uint32_t)(r.h.cell_block1 - r.h.cell_block0); m.num_other_faces = 0;
+    return m;
+}
+
+// The refusals every pa_interface_rows_* entry point shares, in this order: face degree, no cut mesh, a system of 2^31 unknowns or
+// more, the cut-cell arrays missing (cut_arrays: present or not needed) while the slab has cut cells, the halo missing (halo:
+// present or not needed) while the slab has a row below.  Then the side stream is joined, and the numbering and the symbolic tables
+// of face_deg are built if the context does not hold them.
+static int ifrows_prepare(pa_context *ctx, int face_deg, bool cut_arrays, bool halo)
+{
+    (void)hipSetDevice(ctx->device);
+    if (face_deg < 0 || face_deg > 3) return PA_ERR_INVALID_DEGREE;
+    if (!ctx->cut || !ctx->d_cell_faces) return PA_ERR_NO_MESH;
+    auto &r = ctx->ifrows;
+    if (r.h.ne == 0) {                                    // once: the counts stay, the tables go after the upload
+        try {
+            pa::if_rows_numbering(*ctx->cut, ctx->sm.row0, ctx->sm.row1, true, r.h);
+        } catch (const std::exception &e) {
+            ctx->last_error = std::string("pa_interface_rows: ") + e.what();
+            return PA_ERR_INVALID_ARG;
+        }
+    }
+    if ((uint64_t)(face_deg + 1) * r.h.face_blocks >= ((uint64_t)1 << 31)) {       // int32 column ids
+        ctx->last_error = "pa_interface_rows: the face-only system has 2^31 unknowns or more";
+        return PA_ERR_INVALID_ARG;
+    }
+    if (r.h.ncut && !cut_arrays) {
+        ctx->last_error = "pa_interface_rows: the slab has cut cells: the cut-cell arrays are required";
+        return PA_ERR_INVALID_ARG;
+    }
+    if (r.h.nh && !halo) {
+        ctx->last_error = "pa_interface_rows: this slab has a slab below: d_halo_below (pa_interface_rows_halo_pack of that slab) is required";
+        return PA_ERR_INVALID_ARG;
+    }
+    if (ctx->side_pending) {                              // cut-cell work still out on the side stream
+        PA_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_side, 0));
+        ctx->side_pending = false;
+    }
+    if (!r.ready) {
+        hipError_t e = upload_vec(r.h.cell_faces, &r.cell_faces, ctx->stream);
+        if (e == hipSuccess) e = upload_vec(r.h.cell_loc, &r.cell_loc, ctx->stream);
+        if (e == hipSuccess) e = upload_vec(r.h.face_loc, &r.face_loc, ctx->stream);
+        if (e == hipSuccess) e = upload_vec(r.h.cut_index, &r.cut_index, ctx->stream);
+        if (e == hipSuccess) e = upload_vec(r.h.cell_table, &r.cell_table, ctx->stream);
+        if (e == hipSuccess) e = upload_vec(r.h.face_table, &r.face_table, ctx->stream);
+        if (e == hipSuccess) e = upload_vec(r.h.cell_table_slab, &r.cell_table_slab, ctx->stream);
+        if (e == hipSuccess) e = upload_vec(r.h.face_table_slab, &r.face_table_slab, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);       // the host vectors are dropped
+        PA_HIP(ctx, e);
+        for (auto *v : {&r.h.cut_index, &r.h.cell_table, &r.h.face_table, &r.h.cell_table_slab, &r.h.face_table_slab}) std::vector<int32_t>().swap(*v);
+        std::vector<uint32_t>().swap(r.h.cell_faces);
+        std::vector<int8_t>().swap(r.h.cell_loc); std::vector<int8_t>().swap(r.h.face_loc);
+        r.ready = true;
+    }
+    if (r.tables.groups == nullptr || r.tables.face_deg != face_deg) {
+        PA_HIP(ctx, pa::ifcsr_build(ctx->stream, ifrows_mesh(ctx), face_deg, &r.tables));
+        uint64_t v[2] = {0, 0};
+        PA_HIP(ctx, hipMemcpy(&v[0], r.tables.cvstart + r.h.q0, sizeof(uint64_t), hipMemcpyDeviceToHost));
+        PA_HIP(ctx, hipMemcpy(&v[1], r.tables.cvstart + r.h.q1, sizeof(uint64_t), hipMemcpyDeviceToHost));
+        r.v0 = v[0]; r.nnz = v[1] - v[0];
+    }
+    return PA_OK;
+}
+
+static pa::IfRowsArgs ifrows_args(const pa_context *ctx, int face_deg, const double *d_cond, const double *d_cond_cut, const double *d_g,
+                                  const double *d_halo_below)
+{
+    const auto &r = ctx->ifrows;
+    pa::IfRowsArgs a;
+    a.cond = d_cond; a.cond_cut = d_cond_cut; a.g = d_g; a.halo = d_halo_below;
+    a.ncells = r.h.ncells; a.ncut = r.h.ncut; a.nh = r.h.nh; a.nhc = r.h.nhc; a.fshift = r.h.fshift;
+    a.q0 = r.h.q0; a.nq = r.h.q1 - r.h.q0;
+    a.col0 = (int32_t)((uint64_t)(face_deg + 1) * (r.h.fb0 + r.h.q0));
+    a.v0 = r.v0; a.nnz = r.nnz;
+    return a;
+}
+
+int pa_interface_rows_query(pa_context *ctx, int face_deg, pa_interface_rows_info *out)
+{
+    if (!ctx || !out) return PA_ERR_INVALID_ARG;
+    const int st = ifrows_prepare(ctx, face_deg, true, true);
+    if (st != PA_OK) return st;
+    ifrows_info_fill(ctx->ifrows.h, face_deg, ctx->ifrows.nnz, out);
+    return PA_OK;
+}
+
+// the records of the context's cells: the uncut formulas through the plain mesh's static condensation, the cut cells in
+// double-double (after `prepare` has let the call through)
+static int interface_records(pa_context *ctx, int face_deg, const double *d_lc, const double *d_rhs, const double *d_lc_cut,
+                             const double *d_rhs_cut, double *d_cond, double *d_cond_cut, int32_t *d_info, int32_t *d_info_cut)
+{
+    const size_t n = ctx->ncells, ncut = ctx->cut->cut_cells.size();
+    const int nf = 4 * (face_deg + 1), ntri = nf * (nf + 1) / 2;
+    const pa_degree_info di = {face_deg + 1, face_deg, face_deg + 1};
+    // the uncut cells: the plain mesh's static condensation of every row of d_lc (rows of cut cells included, never read back)
+    const int sc = condense(ctx, di, n, d_lc, d_rhs, d_cond, d_cond + n * (size_t)ntri, nullptr, d_info, 1);
+    if (sc != PA_OK) return sc;
+    PA_HIP(ctx, pa::ifcond_info_remap(ctx->stream, n, d_info));
+    if (ncut) {
+        const size_t blocks = (size_t)ctx->num_cus * 8;
+        PA_HIP(ctx, pa::ifcond_cut_records(ctx->stream, face_deg, (int)blocks, (uint32_t)ncut, d_lc_cut, d_rhs_cut, d_cond_cut, d_info_cut));
+    }
+    return PA_OK;
+}
+
+int pa_interface_rows_ops_batch(pa_context *ctx, int face_deg, const double *d_lc, const double *d_rhs, const double *d_lc_cut,
+                                const double *d_rhs_cut, double *d_cond, double *d_cond_cut, int32_t *d_info, int32_t *d_info_cut)
+{
+    if (!ctx || !d_lc || !d_cond) return PA_ERR_INVALID_ARG;
+    const int st = ifrows_prepare(ctx, face_deg, d_lc_cut != nullptr && d_cond_cut != nullptr, true);
+    if (st != PA_OK) return st;
+    return interface_records(ctx, face_deg, d_lc, d_rhs, d_lc_cut, d_rhs_cut, d_cond, d_cond_cut, d_info, d_info_cut);
+}
+
+int pa_interface_rows_halo_pack(pa_context *ctx, int face_deg, const double *d_cond, const double *d_cond_cut, const double *d_g,
+                                double *d_halo)
+{
+    if (!ctx || !d_cond || !d_halo) return PA_ERR_INVALID_ARG;
+    const int st = ifrows_prepare(ctx, face_deg, d_cond_cut != nullptr, true);
+    if (st != PA_OK) return st;
+    const pa::IfRowsHost &h = ctx->ifrows.h;
+    PA_HIP(ctx, pa::ifrows_halo_pack(ctx->stream, face_deg, ctx->d_cell_faces, ctx->d_face_dir, h.ncells, h.ncut, h.ns, h.nsc, d_cond,
+                                     d_cond_cut, d_g, d_halo));
+    return PA_OK;
+}
+
+int pa_interface_rows_csr_pattern(pa_context *ctx, int face_deg, int64_t *d_rowptr, int32_t *d_colind)
+{
+    if (!ctx || !d_rowptr) return PA_ERR_INVALID_ARG;
+    const int st = ifrows_prepare(ctx, face_deg, true, true);
+    if (st != PA_OK) return st;
+    PA_HIP(ctx, pa::ifrows_pattern(ctx->stream, ifrows_mesh(ctx), ctx->ifrows.tables, ifrows_args(ctx, face_deg, nullptr, nullptr, nullptr, nullptr),
+                                   d_rowptr, d_colind));
+    return PA_OK;
+}
+
+int pa_interface_rows_csr_fill(pa_context *ctx, int face_deg, const double *d_cond, const double *d_cond_cut, const double *d_g,
+                               const double *d_halo_below, double *d_values, double *d_rhs)
+{
+    if (!ctx || !d_cond || !d_values) return PA_ERR_INVALID_ARG;
+    const int st = ifrows_prepare(ctx, face_deg, d_cond_cut != nullptr, d_halo_below != nullptr);
+    if (st != PA_OK) return st;
+    PA_HIP(ctx, pa::ifrows_fill(ctx->stream, ifrows_mesh(ctx), ctx->ifrows.tables,
+                                ifrows_args(ctx, face_deg, d_cond, d_cond_cut, d_g, d_halo_below), d_values, d_rhs));
+    return PA_OK;
+}
+
+int pa_interface_rows_recover(pa_context *ctx, int face_deg, const double *d_lc, const double *d_rhs, const double *d_lc_cut,
+                              const double *d_rhs_cut, const double *d_g, const double *d_xF, double *d_uT)
+{
+    if (!ctx || !d_lc || !d_xF || !d_uT) return PA_ERR_INVALID_ARG;
+    const int st = ifrows_prepare(ctx, face_deg, d_lc_cut != nullptr, true);
+    if (st != PA_OK) return st;
+    PA_HIP(ctx, pa::ifcond_recover(ctx->stream, ifrows_slab_mesh(ctx), face_deg, ctx->num_cus * 16, ifcond_args(ctx, nullptr, nullptr, d_g),
+                                   d_lc, d_rhs, d_lc_cut, d_rhs_cut, d_xF, d_uT));
     return PA_OK;
 }
 

@@ -16,14 +16,17 @@
 // entries), summing its addends cell by cell, local row outer, local column inner -- the push order -- from the first addend, as
 // csr_reduce_kernel (csr.hip) does.  The right-hand side is the triplet path's per-row sums added in cell order.
 //
-// One gather, two sources.  The face-only system after static condensation (interface_condensed.hip forms its records) is the same
+// One gather, three sources.  The face-only system after static condensation (interface_condensed.hip forms its records) is the same
 // numbering without its cell blocks: a face group's row is its cell units followed by its face units (IfGroup::fu0, fpos), and the
 // condensed row keeps the face units.  if_pattern_kernel and if_fill_kernel are written once over a Source, which answers what
 // differs: the groups and units that take part, where an addend is read (IfFullSource: the column-major local matrices;
 // IfCondSource: the packed records), one cell's right-hand-side contribution, and where the row lands.  The push order is
-// implemented in if_fill_kernel and nowhere else.  Structure and values of either system are bit-identical to
-// pa_csr_from_triplets of its triplet kernel's slots taken in cell order (tests/test_gpu_interface_csr.py,
-// tests/test_gpu_interface_condensed.py).
+// implemented in if_fill_kernel and nowhere else.  The third source (IfRowsSource) is the face-only system of one slab of cell
+// rows: the tables are built over the slab's extended cell range as over a small mesh, the owned face groups take part, a halo
+// cell's addends come from the halo the slab below sent, rows start at the slab's first row and columns are global
+// (tests/test_gpu_interface_rows.py: the slabs stacked are the whole-mesh face-only system).  Structure and values of the first
+// two are bit-identical to pa_csr_from_triplets of their triplet kernel's slots taken in cell order
+// (tests/test_gpu_interface_csr.py, tests/test_gpu_interface_condensed.py).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -196,12 +199,13 @@ __global__ __launch_bounds__(256) void ifc_write_kernel(IfCsrMesh m, IfDims d, c
     for (int s = 0; s < G.nunits; ++s) units[G.ustart + s] = u[s];
 }
 
-// ---- the two sources -------------------------------------------------------------------------------------------------
+// ---- the three sources -----------------------------------------------------------------------------------------------
 // A Source says which groups take part (first_group, ngroups), which part of a group's row (first_unit, first_pos: the units
 // from first_unit on, positions counted from first_pos), how many leading unknowns of the numbering are left out (skipped: rows
 // and columns shift by it), where the rows of group number w of the source start in values (vstart), what a cell's slot holds
 // (cell), addend (row, col) of a cell by its local indices in the full local matrix (load), the cell's contribution to the
-// right-hand side of local row li (rhs), and where values and right-hand side go.
+// right-hand side of local row li (rhs), what is added to a column to make it global (col0), and where values and right-hand
+// side go.
 
 // the full system: every group, the whole row; addends from the column-major local matrices
 struct IfFullSource {
@@ -217,6 +221,7 @@ struct IfFullSource {
     __device__ static uint32_t first_unit(const IfGroup &) { return 0u; }
     __device__ static uint32_t first_pos(const IfGroup &) { return 0u; }
     __device__ static uint64_t skipped(const IfCsrMesh &, IfDims) { return 0u; }
+    __device__ static int32_t col0() { return 0; }
     __device__ uint64_t vstart(const IfGroup &G, uint32_t) const { return G.vstart; }
     __device__ Cell cell(const IfCsrMesh &m, IfDims d, int32_t X) const
     {
@@ -259,6 +264,7 @@ struct IfCondSource {
     __device__ static uint32_t first_unit(const IfGroup &G) { return G.fu0; }
     __device__ static uint32_t first_pos(const IfGroup &G) { return G.fpos; }
     __device__ static uint64_t skipped(const IfCsrMesh &m, IfDims d) { return (uint64_t)m.num_all_cells * d.cbs; }
+    __device__ static int32_t col0() { return 0; }
     __device__ uint64_t vstart(const IfGroup &, uint32_t w) const { return cvstart[w]; }
     __device__ Cell cell(const IfCsrMesh &m, IfDims d, int32_t X) const
     {
@@ -297,6 +303,63 @@ struct IfCondSource {
     }
 };
 
+// the face-only system of one slab: the owned face groups of the extended range, the face units of their rows; a cell's addends
+// from the slab's records or, for a halo cell, from the received halo, whose last part is the boundary data of its faces
+struct IfRowsSource {
+    IfRowsArgs a;
+    const uint64_t *cvstart;
+    double *values, *RHS;
+    struct Cell {
+        const double *S, *g;    // the cell's packed S and its g
+        const double *bd;       // a halo cell: the boundary data of its 4 faces (nf doubles); null: the context's, by face id
+        int off;
+        bool cut;
+    };
+    __device__ uint32_t first_group(const IfCsrMesh &m) const { return m.num_all_cells + a.q0; }
+    __device__ uint32_t ngroups(const IfCsrMesh &) const { return a.nq; }
+    __device__ static uint32_t first_unit(const IfGroup &G) { return G.fu0; }
+    __device__ static uint32_t first_pos(const IfGroup &G) { return G.fpos; }
+    __device__ uint64_t skipped(const IfCsrMesh &m, IfDims d) const { return (uint64_t)m.num_all_cells * d.cbs + (uint64_t)a.q0 * d.fbs; }
+    __device__ int32_t col0() const { return a.col0; }
+    __device__ uint64_t vstart(const IfGroup &, uint32_t w) const { return cvstart[a.q0 + w] - a.v0; }
+    __device__ Cell cell(const IfCsrMesh &m, IfDims d, int32_t X) const
+    {
+        if (X < 0) return {a.cond, a.cond, nullptr, 0, false};
+        const bool halo = (uint32_t)X < a.nh;
+        const int nf = 4 * d.fbs, ntri = nf * (nf + 1) / 2, NF = 8 * d.fbs, NTRI = NF * (NF + 1) / 2;
+        const double *hcut = a.halo + (size_t)a.nh * (ntri + nf), *hbd = hcut + (size_t)a.nhc * (NTRI + NF);
+        const double *bd = halo ? hbd + (size_t)X * nf : nullptr;
+        if (m.cell_loc[X] == IF_LOC_CUT) {
+            const size_t cc = (size_t)m.cut_index[X], n = halo ? a.nhc : a.ncut;
+            const double *rec = halo ? hcut : a.cond_cut;
+            return {rec + cc * NTRI, rec + n * NTRI + cc * NF, bd, 2 * d.cbs, true};
+        }
+        const size_t x = halo ? (size_t)X : (size_t)X - a.nh, n = halo ? a.nh : a.ncells;
+        const double *rec = halo ? a.halo : a.cond;
+        return {rec + x * ntri, rec + n * ntri + x * nf, bd, d.cbs, false};
+    }
+    __device__ static double load(const Cell &c, uint32_t row, uint32_t col)
+    {
+        return IfCondSource::packed(c.S, (int)row - c.off, (int)col - c.off);
+    }
+    // IfCondSource::rhs with the boundary data of a halo cell's faces taken from the halo
+    __device__ double rhs(const IfCsrMesh &m, IfDims d, int32_t X, const Cell &c, int li) const
+    {
+        const int row = li - c.off;
+        double s = c.g[row];
+        if (c.cut) return s;
+        for (int lf = 0; lf < 4; ++lf) {
+            const uint32_t f = m.cell_faces[4 * (size_t)X + lf];
+            if (m.face_table[f] >= 0) continue;
+            for (int kp = 0; kp < d.fbs; ++kp) {
+                const double dd_ = c.bd != nullptr ? c.bd[lf * d.fbs + kp] : (a.g != nullptr ? a.g[(size_t)(f - a.fshift) * d.fbs + kp] : 0.0);
+                s -= IfCondSource::packed(c.S, row, lf * d.fbs + kp) * dd_;
+            }
+        }
+        return s;
+    }
+};
+
 // ---- pattern: one thread per row -------------------------------------------------------------------------------------
 template <class Source>
 __global__ __launch_bounds__(256) void if_pattern_kernel(IfCsrMesh m, IfDims d, uint64_t nrows, uint64_t nnz, const IfGroup *groups,
@@ -305,16 +368,16 @@ __global__ __launch_bounds__(256) void if_pattern_kernel(IfCsrMesh m, IfDims d, 
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t > nrows) return;
     if (t == nrows) { rowptr[t] = (int64_t)nnz; return; }
-    const uint32_t g0 = Source::first_group(m);
-    const uint64_t cell_rows = (uint64_t)(m.num_all_cells - g0) * d.cbs;        // the source's rows that are rows of cell groups
-    const uint32_t g = t < cell_rows ? g0 + (uint32_t)(t / d.cbs) : m.num_all_cells + (uint32_t)((t - cell_rows) / d.fbs);
+    const uint32_t g0 = src.first_group(m), gf = g0 > m.num_all_cells ? g0 : m.num_all_cells;      // the source's first face group
+    const uint64_t cell_rows = (uint64_t)(gf - g0) * d.cbs;                     // the source's rows that are rows of cell groups
+    const uint32_t g = t < cell_rows ? g0 + (uint32_t)(t / d.cbs) : gf + (uint32_t)((t - cell_rows) / d.fbs);
     const uint32_t i = t < cell_rows ? (uint32_t)(t % d.cbs) : (uint32_t)((t - cell_rows) % d.fbs);
     const IfGroup G = groups[g];
     const uint32_t poff = Source::first_pos(G);
     const uint64_t start = src.vstart(G, g - g0) + (uint64_t)i * (G.R - poff);
     rowptr[t] = (int64_t)start;
     if (colind == nullptr) return;
-    const int32_t skip = (int32_t)Source::skipped(m, d);
+    const int32_t skip = (int32_t)src.skipped(m, d) - src.col0();
     for (int s = (int)Source::first_unit(G); s < G.nunits; ++s) {
         const IfUnit U = units[G.ustart + s];
         for (int k = 0; k < U.width; ++k) colind[start + (U.pos - poff) + k] = U.gcol - skip + k;
@@ -328,8 +391,8 @@ __global__ __launch_bounds__(256) void if_fill_kernel(IfCsrMesh m, IfDims d, con
 {
     const uint32_t lane = threadIdx.x % 64u;
     const uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + threadIdx.x / 64u);
-    if (w >= Source::ngroups(m)) return;
-    const uint32_t grp = Source::first_group(m) + w;
+    if (w >= src.ngroups(m)) return;
+    const uint32_t grp = src.first_group(m) + w;
     const IfGroup G = groups[grp];
     const uint32_t nrows = grp < m.num_all_cells ? (uint32_t)d.cbs : (uint32_t)d.fbs;
     typename Source::Cell C[2];
@@ -388,7 +451,7 @@ __global__ __launch_bounds__(256) void if_fill_kernel(IfCsrMesh m, IfDims d, con
             }
         const uint64_t row = grp < m.num_all_cells ? (uint64_t)grp * d.cbs
                                                    : (uint64_t)m.num_all_cells * d.cbs + (uint64_t)(grp - m.num_all_cells) * d.fbs;
-        src.RHS[row - Source::skipped(m, d) + lane] = acc;
+        src.RHS[row - src.skipped(m, d) + lane] = acc;
     }
 }
 
@@ -597,6 +660,56 @@ hipError_t ifcond_triplets(hipStream_t stream, const IfCsrMesh &m, int face_deg,
     if (m.ncells == 0) return hipSuccess;
     const dim3 grid(m.ncells < (uint32_t)max_blocks ? m.ncells : (uint32_t)max_blocks);
     hipLaunchKernelGGL(ifd_triplets_kernel, grid, dim3(256), 0, stream, m, if_dims(face_deg), IfCondSource{a, nullptr, nullptr, nullptr}, o);
+    return hipGetLastError();
+}
+
+// ---- one slab of cell rows -------------------------------------------------------------------------------------------
+namespace {
+
+// the Dirichlet data of the faces of cells [first, first + n), nf per cell in local face order; zero where a face is not Dirichlet
+__global__ __launch_bounds__(256) void ifrows_halo_bd_kernel(const uint32_t *cell_faces, const uint8_t *face_dir, uint32_t first, uint32_t n,
+                                                             int fbs, const double *g, double *out)
+{
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, nf = 4u * (uint32_t)fbs;
+    if (t >= n * nf) return;
+    const uint32_t X = first + t / nf, lf = (t % nf) / (uint32_t)fbs, k = t % (uint32_t)fbs;
+    const uint32_t f = cell_faces[4 * (size_t)X + lf];
+    out[t] = (g != nullptr && face_dir[f]) ? g[(size_t)f * fbs + k] : 0.0;
+}
+
+}  // namespace
+
+hipError_t ifrows_pattern(hipStream_t stream, const IfCsrMesh &m, const IfCsrTables &t, const IfRowsArgs &a, int64_t *rowptr, int32_t *colind)
+{
+    return if_pattern(stream, m, t, (uint64_t)a.nq * (t.face_deg + 1), a.nnz, IfRowsSource{a, t.cvstart, nullptr, nullptr}, rowptr, colind);
+}
+
+hipError_t ifrows_fill(hipStream_t stream, const IfCsrMesh &m, const IfCsrTables &t, const IfRowsArgs &a, double *values, double *RHS)
+{
+    return if_fill(stream, m, t, a.nq, IfRowsSource{a, t.cvstart, values, RHS});
+}
+
+hipError_t ifrows_halo_pack(hipStream_t stream, int face_deg, const uint32_t *cell_faces, const uint8_t *face_dir, uint32_t ncells,
+                            uint32_t ncut, uint32_t ns, uint32_t nsc, const double *cond, const double *cond_cut, const double *g,
+                            double *halo)
+{
+    if (ns == 0) return hipSuccess;
+    const size_t fbs = face_deg + 1, nf = 4 * fbs, ntri = nf * (nf + 1) / 2, NF = 8 * fbs, NTRI = NF * (NF + 1) / 2;
+    // the top row's records are the tails of [S | g] and of the cut cells' [S | g]
+    const struct { const double *src; size_t n; } part[4] = {{cond + (size_t)(ncells - ns) * ntri, ns * ntri},
+                                                             {cond + (size_t)ncells * ntri + (size_t)(ncells - ns) * nf, ns * nf},
+                                                             {cond_cut + (size_t)(ncut - nsc) * NTRI, nsc * NTRI},
+                                                             {cond_cut + (size_t)ncut * NTRI + (size_t)(ncut - nsc) * NF, nsc * NF}};
+    double *out = halo;
+    for (const auto &p : part) {
+        if (p.n) {
+            const hipError_t e = hipMemcpyAsync(out, p.src, p.n * sizeof(double), hipMemcpyDeviceToDevice, stream);
+            if (e != hipSuccess) return e;
+        }
+        out += p.n;
+    }
+    hipLaunchKernelGGL(ifrows_halo_bd_kernel, dim3(blocks_for(ns * nf)), dim3(256), 0, stream, cell_faces, face_dir, ncells - ns, ns,
+                       (int)fbs, g, out);
     return hipGetLastError();
 }
 

@@ -102,6 +102,22 @@ struct IfCondArgs {
     const uint32_t *cut_cells;          // ncut cell ids
     uint32_t ncut;
 };
+// The face-only system of ONE SLAB of cell rows (pa_interface_rows_*).  The mesh is the slab's extended range (interface_rows.hpp:
+// the halo row below, then the slab's cells, numbered from the range's first blocks); the rows are those of the owned face
+// blocks [q0, q0 + nq), shifted to start at 0; the columns are global.  A cell of the slab reads the slab's records, a halo cell
+// the received halo [S of the nh halo cells | their g | S of their nhc cut cells | their g | nh x nf boundary values: the
+// Dirichlet data of each halo cell's faces, zero where a face is not Dirichlet].
+struct IfRowsArgs {
+    const double *cond, *cond_cut;      // the slab's records
+    const double *g;                    // Dirichlet data by the context's own face ids, or null
+    const double *halo;                 // the halo received from the slab below; null on slab 0
+    uint32_t ncells, ncut;              // the slab's cells and cut cells
+    uint32_t nh, nhc;                   // halo cells and the cut cells among them
+    uint32_t fshift;                    // extended id of the context's face 0
+    uint32_t q0, nq;                    // the owned face blocks
+    int32_t col0;                       // global column of the first owned row
+    uint64_t v0, nnz;                   // cvstart of block q0; entries of the owned rows
+};
 // triplets in the reference's push order, n = msize (full) or nf (face-only) unknowns per uncut cell, N = 2 msize or NF per cut
 // cell: uncut slots ncells x n^2 (cut cells: all -1), cut slots ncut x N^2; right-hand side slots ncells x n / ncut x N
 struct IfTriplets {
@@ -122,6 +138,14 @@ hipError_t ifcsr_triplets(hipStream_t stream, const IfCsrMesh &m, int face_deg, 
 hipError_t ifcond_pattern(hipStream_t stream, const IfCsrMesh &m, const IfCsrTables &t, int64_t *rowptr, int32_t *colind);
 hipError_t ifcond_fill(hipStream_t stream, const IfCsrMesh &m, const IfCsrTables &t, const IfCondArgs &a, double *values, double *RHS);
 hipError_t ifcond_triplets(hipStream_t stream, const IfCsrMesh &m, int face_deg, int max_blocks, const IfCondArgs &a, const IfTriplets &o);
+// the face-only system of a slab: the same gather again, rows local, columns global (interface_csr.hip)
+hipError_t ifrows_pattern(hipStream_t stream, const IfCsrMesh &m, const IfCsrTables &t, const IfRowsArgs &a, int64_t *rowptr, int32_t *colind);
+hipError_t ifrows_fill(hipStream_t stream, const IfCsrMesh &m, const IfCsrTables &t, const IfRowsArgs &a, double *values, double *RHS);
+// what a slab sends up: the records of its last ns cells (nsc of them cut, the last of its cut records) and the Dirichlet data
+// of their faces, in the layout IfRowsArgs::halo describes; cell_faces / face_dir: the context's
+hipError_t ifrows_halo_pack(hipStream_t stream, int face_deg, const uint32_t *cell_faces, const uint8_t *face_dir, uint32_t ncells,
+                            uint32_t ncut, uint32_t ns, uint32_t nsc, const double *cond, const double *cond_cut, const double *g,
+                            double *halo);
 
 // ---- the dense per-cell work of the condensation (interface_condensed.hip) ------------------------------------------------
 // the cut cells' records in double-double (one wavefront per cut cell); info[cc] = 200 + j + 1 for a failed pivot j, else 0
