@@ -470,6 +470,31 @@ int pa_cut_merge(pa_context *ctx, int face_deg, int where, const double *d_cut_l
  * matrices and right-hand sides (pa_cut_local_ops_batch), d_cut_Sp ncut x nf(nf+1)/2 and d_cut_g ncut x nf -- replace the
  * cut cells' records in d_cond (pa_condensed_ops_batch over all cells with the uncut formulas, n x (nf(nf+1)/2 + nf)). */
 int pa_cut_merge_condensed(pa_context *ctx, int face_deg, const double *d_cut_Sp, const double *d_cut_g, double *d_cond);
+/* The "Matrix assembly" span of the fictitious-domain driver (apps/cuthho/cuthho_square.cpp:881-905) in one pass: the system is
+ * the plain assembler<Mesh>'s over ALL cells (assemble hho.hpp:344-406, finalize hho.hpp:451-455), so the pattern is the one
+ * pa_assembler_csr_query / _pattern describe for hho_degree_info(face_deg + 1, face_deg) (cuthho_square.cpp:871) on the same
+ * pa_cut_preprocess context.  The uncut cells go through pa_assembler_csr_assemble's pass (PA_QUAD_FAN, PA_STAB_NAIVE,
+ * cuthho_square.cpp:316-317, 572-573; in pieces under pa_context_set_record_cap) with the cells tagged PA_LOC_ON_INTERFACE left
+ * out of its scatter; their operators -- d_cut_lc, ncut x msize^2 column-major as pa_cut_local_ops_batch writes d_lc, and
+ * d_cut_rhs, ncut x cbs or NULL = 0 -- go through the same scatter from a second, small kernel.  No ncells x msize^2 buffer
+ * exists unless d_lc asks for one.  A cut kernel still out on the side stream (pa_context_set_cut_overlap) is joined first.
+ * d_rhs ncells x cbs or NULL = 0 (pa_cut_uncut_rhs_batch; an uncut cell outside `where` takes a zero right-hand side whatever
+ * d_rhs holds there, pa_cut_merge's rule, cuthho_square.cpp:659-664), d_g pa_dirichlet_data_batch or NULL, d_RHS nrows (may be
+ * NULL), d_info ncells (may be NULL: the flags of the uncut formulas, for every cell).
+ * Contract: d_values and d_RHS are BIT-IDENTICAL to pa_assembler_csr_fill fed with the merged local matrices -- the d_lc this
+ * call returns: the assembling instance's image in the uncut rows, a bit copy of d_cut_lc in the cut rows -- the merged
+ * right-hand sides (d_rhs with the rule above in the uncut rows, d_cut_rhs in the cut rows) and the same d_g; with or without
+ * d_lc, from call to call and whatever the buffers held before.  A face's own diagonal block and right-hand side take one
+ * addend per adjacent cell, cut or not; they are added onto entries the call zeroes first, a two-term sum that does not depend
+ * on arrival order.  Every other entry is written exactly once.  With no cut cell the result is pa_assembler_csr_assemble's.
+ * Refused before any buffer is touched: NULL ctx / d_values, `where` not PA_LOC_NEGATIVE / PA_LOC_POSITIVE, cut cells without
+ * d_cut_lc: PA_ERR_INVALID_ARG; no cut preprocessing: PA_ERR_NO_MESH; a slab (pa_cut_preprocess_rows): as pa_assembler_csr_fill;
+ * face_deg > 2: PA_ERR_QUADRATURE, as the cut entries. */
+int pa_fictdom_csr_assemble(pa_context *ctx, int face_deg, int where,
+                            const double *d_rhs, const double *d_g,
+                            const double *d_cut_lc, const double *d_cut_rhs,
+                            double *d_values, double *d_RHS,
+                            double *d_lc /* may be NULL */, int32_t *d_info /* may be NULL */);
 
 /* ---- cutHHO two-sided interface problem (`cuthho_square -i`, run_cuthho_interface
  * cuthho_square.cpp:1625-1846).  hho_degree_info(face_deg + 1, face_deg) (:1662). */

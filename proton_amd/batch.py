@@ -378,6 +378,55 @@ class BatchAssembler:
             self.ctx.set_cut_overlap(False)
         return out["lc"], rhs
 
+    def fictdom_csr_scatter(self, fd, where=capi.LOC_NEGATIVE, rhs=None, g=None, cut_lc=None, cut_rhs=None, values=None, RHS=None,
+                            want=()):
+        """pa_fictdom_csr_assemble on caller tensors: rhs [ncells, cbs] (uncut cells; those outside `where` count as zero),
+        cut_lc [ncut, msize, msize] / cut_rhs [ncut, cbs] (cut cells), g the boundary data -> dict(values [nnz], RHS [nrows]
+        [, lc [ncells, msize, msize]] [, info [ncells]]) on the pattern of assembler_csr_pattern(fd + 1, fd)"""
+        cd = fd + 1
+        di, _ = capi.degree_info(cd, fd)
+        ms = (cd + 1) * (cd + 2) // 2 + 4 * (fd + 1)
+        info = self.ctx.assembler_csr_query(di)
+        if values is None:
+            values = torch.empty(max(info.nnz, 1), dtype=torch.float64, device=self.device)
+        if RHS is None:
+            RHS = torch.empty(max(info.nrows, 1), dtype=torch.float64, device=self.device)
+        lc = torch.empty((self.ncells, ms, ms), dtype=torch.float64, device=self.device) if "lc" in want else None
+        cinfo = torch.empty(self.ncells, dtype=torch.int32, device=self.device) if "info" in want else None
+        self.ctx.fictdom_csr_assemble(fd, where, _ptr(rhs), _ptr(g), _ptr(cut_lc), _ptr(cut_rhs), values.data_ptr(), RHS.data_ptr(),
+                                      _ptr(lc), _ptr(cinfo))
+        out = {"values": values[:info.nnz], "RHS": RHS[:info.nrows]}
+        if lc is not None:
+            out["lc"] = lc
+        if cinfo is not None:
+            out["info"] = cinfo
+        return out
+
+    def fictdom_csr_assemble(self, fd, where=capi.LOC_NEGATIVE, rhs_fn=capi.FN_SIN_SIN_RHS, bcs_fn=capi.FN_SIN_SIN_SOL, g=None,
+                             values=None, RHS=None, want=(), overlap=False):
+        """The assembly loop of cuthho_square.cpp:881-905 without the [ncells, msize, msize] buffer: the uncut cells' right-hand
+        sides (pa_cut_uncut_rhs_batch), the cut cells' operators (pa_cut_local_ops_batch; overlap: on the context's side stream)
+        and pa_fictdom_csr_assemble -> fictdom_csr_scatter's dict, plus "rhs" [ncells, cbs] and "cut_lc" / "cut_rhs" (None
+        without cut cells)"""
+        cd = fd + 1
+        cut = None
+        if overlap:
+            self.ctx.set_cut_overlap(True)
+        try:
+            if self.ncut:
+                cut = self.cut_local_ops(fd, where, rhs_fn, bcs_fn, want=("lc", "rhs"))
+            rhs = torch.empty((self.ncells, (cd + 1) * (cd + 2) // 2), dtype=torch.float64, device=self.device)
+            self.ctx.cut_uncut_rhs(cd, where, rhs_fn, rhs.data_ptr())
+            out = self.fictdom_csr_scatter(fd, where, rhs, g, None if cut is None else cut["lc"], None if cut is None else cut["rhs"],
+                                           values, RHS, want)
+        finally:
+            if overlap:
+                self.ctx.set_cut_overlap(False)
+        out["rhs"] = rhs
+        out["cut_lc"] = None if cut is None else cut["lc"]
+        out["cut_rhs"] = None if cut is None else cut["rhs"]
+        return out
+
     def fictdom_condensed_ops(self, fd, where=capi.LOC_NEGATIVE, rhs_fn=capi.FN_SIN_SIN_RHS, bcs_fn=capi.FN_SIN_SIN_SOL):
         """The same loop body in condensed mode: packed records [n, nf(nf+1)/2 + nf] of every cell of the context -- the fused
         pass with the uncut formulas (fan quadrature, naive stabilization), the cut cells' records from the stand-alone

@@ -486,4 +486,53 @@ hipError_t asm_zero_accumulated(hipStream_t stream, int cbs, int fbs, uint32_t n
     return hipGetLastError();
 }
 
+// ---- the fictitious-domain problem: pa_fictdom_csr_assemble ---------------------------------------------------------------
+// The operator pass leaves the cut cells out (AsmScatterArgs::cell_loc); their operators come from the cut kernel in HBM
+// (pa_cut_local_ops_batch: ncut x msize^2, column-major) and go through the SAME scatter.  One group of G lanes per cut cell,
+// 64 / G cells per wavefront-sized block; G and LDI are those of the assembling instance of the pair.  A group fills its own
+// image, the block meets at the barrier (the image is complete before the first read of the scatter), and no image is used
+// twice: a block handles one round of cells.
+template <int CBS, int FBS>
+__global__ __launch_bounds__(64) void asm_cut_scatter_kernel(AsmScatterArgs s, uint32_t ncut, const uint32_t *__restrict__ cut_cells,
+                                                             const double *__restrict__ cut_lc, const double *__restrict__ cut_rhs,
+                                                             double *lc_out)
+{
+    constexpr int MS = CBS + 4 * FBS, G = asm_group_lanes(MS), LDI = asm_image_stride(MS), CPW = 64 / G;
+    __shared__ double smem[CPW * MS * LDI];
+    const int g = (int)threadIdx.x / G, l = (int)threadIdx.x % G;
+    const uint64_t cc0 = (uint64_t)blockIdx.x * CPW + (uint32_t)g;
+    const bool valid = cc0 < ncut;
+    const size_t cc = valid ? (size_t)cc0 : (size_t)ncut - 1;      // (ncut > 0: the grid has no block otherwise)
+    const size_t cell = cut_cells[cc];
+    const double *src = cut_lc + cc * (size_t)(MS * MS);
+    double *img = smem + g * (MS * LDI);
+    for (int e = l; e < MS * MS; e += G) {
+        const int j = e / MS, i = e - j * MS;
+        img[i + j * LDI] = src[e];
+    }
+    const double fT = (cut_rhs != nullptr && l < CBS) ? cut_rhs[cc * (size_t)CBS + l] : 0.0;
+    __syncthreads();
+    asm_scatter_cell<G, CBS, FBS, LDI>(s, img, l, cell, valid, fT, lc_out != nullptr ? lc_out + cell * (size_t)(MS * MS) : nullptr);
+}
+
+hipError_t asm_cut_scatter(hipStream_t stream, int face_deg, const AsmScatterArgs &s, uint32_t ncut, const uint32_t *cut_cells,
+                           const double *cut_lc, const double *cut_rhs, double *lc_out)
+{
+    if (ncut == 0) return hipSuccess;
+#define PA_CUT_CASE(K, C, F)                                                                                                   \
+    case K: {                                                                                                                  \
+        constexpr uint32_t CPW = 64 / asm_group_lanes(C + 4 * F);                                                              \
+        hipLaunchKernelGGL((asm_cut_scatter_kernel<C, F>), dim3((ncut + CPW - 1) / CPW), dim3(64), 0, stream, s, ncut, cut_cells, \
+                           cut_lc, cut_rhs, lc_out);                                                                           \
+    } break
+    switch (face_deg) {
+    PA_CUT_CASE(0, 3, 1);
+    PA_CUT_CASE(1, 6, 2);
+    PA_CUT_CASE(2, 10, 3);
+    default: return hipErrorInvalidValue;
+    }
+#undef PA_CUT_CASE
+    return hipGetLastError();
+}
+
 }  // namespace pa

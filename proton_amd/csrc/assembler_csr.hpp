@@ -26,5 +26,10 @@ hipError_t asm_build_scatter_table(hipStream_t stream, const CondMesh &m, uint32
                                    const uint32_t *cprefix, const uint32_t *fprefix, AsmCellRec *out);
 hipError_t asm_zero_accumulated(hipStream_t stream, int cbs, int fbs, uint32_t ncells, uint32_t nown, uint64_t cell_nnz,
                                 const CondFace *faces, const uint32_t *colprefix, const uint32_t *fprefix, double *values, double *RHS);
+// the fictitious-domain path (pa_fictdom_csr_assemble): the cut cells' operators (cut_lc ncut x msize^2 column-major, cut_rhs ncut x cbs
+// or null = 0; cut_cells: their indices in the context) through asm_scatter_cell, for the pairs (face_deg + 1, face_deg), face_deg <= 2;
+// lc_out (ncells x msize^2 or null) receives the cut cells' rows
+hipError_t asm_cut_scatter(hipStream_t stream, int face_deg, const AsmScatterArgs &s, uint32_t ncut, const uint32_t *cut_cells,
+                           const double *cut_lc, const double *cut_rhs, double *lc_out);
 
 }  // namespace pa

@@ -867,7 +867,7 @@ struct LocalOpsOut {
     double *cond_out = nullptr, *uT = nullptr;
     // the assembling mode (on the condensed mode's instances): rhs in, the CSR arrays of scatter out, lc only if not null
     bool assemble = false;
-    pa::AsmScatterArgs scatter = {nullptr, nullptr, nullptr, nullptr, 0, 0};
+    pa::AsmScatterArgs scatter = {nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, 0};
 };
 
 static int run_local_ops(pa_context *ctx, pa_degree_info di, int quad_kind, int stab_kind, size_t first, size_t n,
@@ -1912,6 +1912,51 @@ int pa_cut_merge_condensed(pa_context *ctx, int face_deg, const double *d_cut_Sp
     hipLaunchKernelGGL(pa::cut_merge_condensed_kernel, dim3(ncut), dim3(64), 0, ctx->stream, ncut, ctx->d_cut_cells, ntri, nf, d_cut_Sp, d_cut_g,
                        d_cond);
     PA_HIP(ctx, hipGetLastError());
+    return PA_OK;
+}
+
+// The fictitious-domain system in one pass: the assembling pass over all cells with the cut cells masked out of its scatter, then
+// the cut cells' operators through the same scatter (asm_cut_scatter, assembler_csr.hip).
+int pa_fictdom_csr_assemble(pa_context *ctx, int face_deg, int where, const double *d_rhs, const double *d_g, const double *d_cut_lc,
+                            const double *d_cut_rhs, double *d_values, double *d_RHS, double *d_lc, int32_t *d_info)
+{
+    // ---- the refusals, before anything is built or written
+    if (!ctx || !d_values || (where != PA_LOC_NEGATIVE && where != PA_LOC_POSITIVE)) return PA_ERR_INVALID_ARG;
+    (void)hipSetDevice(ctx->device);
+    if (!ctx->cut || !ctx->d_points || !ctx->d_cell_loc) return PA_ERR_NO_MESH;
+    if (face_deg < 0) return PA_ERR_INVALID_DEGREE;
+    if (face_deg > 2) return PA_ERR_QUADRATURE;            // as the cut entries: 2*recdeg = 8 selects the empty rules[8]
+    if (ctx->structured && (ctx->sm.row0 != 0 || ctx->sm.row1 != ctx->sm.Ny)) {      // asm_prepare's refusal, ahead of its tables
+        ctx->last_error = "pa_fictdom_csr_assemble: whole-mesh contexts only (pa_cut_preprocess, not pa_cut_preprocess_rows)";
+        return PA_ERR_INVALID_ARG;
+    }
+    const uint32_t ncut = (uint32_t)ctx->cut->cut_cells.size();
+    if (ncut > 0 && !d_cut_lc) return PA_ERR_INVALID_ARG;
+    const pa_degree_info di = {face_deg + 1, face_deg, face_deg + 1};                  // cuthho_square.cpp:871
+    const pa::KernelEntry *e = nullptr;
+    int grid = 0;
+    int st = select_kernel(ctx, di, PA_QUAD_FAN, PA_STAB_NAIVE, ctx->ncells, &e, &grid, true);
+    if (st != PA_OK) return st;
+    if (!e->launch_asm) return PA_ERR_INVALID_DEGREE;
+    st = asm_prepare(ctx);
+    if (st != PA_OK) return st;
+    if (ctx->side_pending) {                              // d_cut_lc may come from the cut kernel on the side stream
+        PA_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_side, 0));
+        ctx->side_pending = false;
+    }
+    uint64_t cell_nnz, nnz, nrows;
+    asm_sizes(ctx, di, &cell_nnz, &nnz, &nrows);
+    const int cbs = pa::P2(face_deg + 1), fbs = face_deg + 1;
+    PA_HIP(ctx, pa::asm_zero_accumulated(ctx->stream, cbs, fbs, (uint32_t)ctx->ncells, ctx->cond_nown, cell_nnz, ctx->d_cfaces, ctx->d_prefix,
+                                         ctx->d_asm_fprefix, d_values, d_RHS));
+    LocalOpsOut o;
+    o.cond = true; o.assemble = true; o.rhs = d_rhs; o.lc = d_lc; o.info = d_info;
+    o.scatter.tab = ctx->d_asm_scatter; o.scatter.g = d_g; o.scatter.values = d_values; o.scatter.RHS = d_RHS;
+    o.scatter.cell_nnz = cell_nnz; o.scatter.ncells = ctx->ncells;
+    o.scatter.cell_loc = ctx->d_cell_loc; o.scatter.where = where;
+    st = run_local_ops(ctx, di, PA_QUAD_FAN, PA_STAB_NAIVE, 0, ctx->ncells, o);
+    if (st != PA_OK) return st;
+    PA_HIP(ctx, pa::asm_cut_scatter(ctx->stream, face_deg, o.scatter, ncut, ctx->d_cut_cells, d_cut_lc, d_cut_rhs, d_lc));
     return PA_OK;
 }
 

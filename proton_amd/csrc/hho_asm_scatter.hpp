@@ -4,6 +4,8 @@
 // assembler<Mesh>::assemble (src/methods/hho_bits/hho.hpp:344-406) turns a cell's local matrix into global entries in the loop
 // iteration that formed it; here the cooperative kernel does the same with the image it holds.  The fills of
 // assembler_csr.hip are gathers and their tables are indexed by face; the scatter needs the inverse, one record per cell.
+// asm_scatter_cell has a second caller, asm_cut_scatter_kernel (assembler_csr.hip), which feeds it the cut cells' operators of the
+// fictitious-domain problem from an image it copies out of HBM.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -33,7 +35,28 @@ struct AsmScatterArgs {
     double *values, *RHS;    // CSR values; right-hand side (may be null)
     uint64_t cell_nnz;       // entries of all cell rows
     uint64_t ncells;
+    // fictitious-domain assembly (pa_fictdom_csr_assemble): the tags of the context's cells, null everywhere else.  A cell tagged
+    // ASM_LOC_CUT is left to asm_cut_scatter_kernel (nothing of it is scattered here); an uncut cell whose tag is not `where`
+    // takes a zero right-hand side (cuthho_square.cpp:659-664)
+    const int8_t *cell_loc;
+    int32_t where;
 };
+
+constexpr int8_t ASM_LOC_CUT = 2;                // LOC_CUT of cut_host.hpp, PA_LOC_ON_INTERFACE
+
+// The assembling instances' group size and image stride as functions of msize alone (Cfg::G of the instance pa_configs.def
+// selects for the pair, Cfg::LDI), for the second caller of asm_scatter_cell that holds no Cfg: asm_cut_scatter_kernel
+constexpr int asm_group_lanes(int ms) { return ms + 1 <= 16 ? 16 : ms + 1 <= 32 ? 32 : 64; }
+constexpr int asm_image_stride(int ms) { return ((ms + 1) & ~1) % 4 == 2 ? ((ms + 1) & ~1) : ((ms + 1) & ~1) + 2; }
+
+// what the operator pass does with a cell under the tags above: scatter it or not, and with which right-hand side
+__device__ __forceinline__ void asm_apply_tags(const AsmScatterArgs &s, size_t cell, bool &valid, double &fT)
+{
+    if (s.cell_loc == nullptr) return;
+    const int loc = s.cell_loc[cell];
+    valid = valid && loc != ASM_LOC_CUT;
+    if (loc != s.where) fT = 0.0;
+}
 
 // One group of G lanes (lane l) per cell.  img: the cell's image, entry (i, j) of lc at img[i + j * LDI] (what the fills read
 // at lc[j * MS + i]).  fT: lane l < CBS holds the cell's right-hand side l (0 without one).

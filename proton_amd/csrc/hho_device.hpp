@@ -2240,7 +2240,10 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
                 // ================= S9' (assembling mode): the image to its places in the global CSR system ==================
                 PA_MARK("S9a");
                 wave_sync();      // the image is complete
-                asm_scatter_cell<G, CBS, FBS, C::LDI>(a.scatter, S + C::oOUT, l, cell, valid, fT_l,
+                static_assert(C::LDI == asm_image_stride(MS), "asm_cut_scatter_kernel lays its image out as this one");
+                bool scatter_ok = valid;
+                asm_apply_tags(a.scatter, cell, scatter_ok, fT_l);      // (fictitious domain: cut cells are not this pass's)
+                asm_scatter_cell<G, CBS, FBS, C::LDI>(a.scatter, S + C::oOUT, l, cell, scatter_ok, fT_l,
                                                       a.lc != nullptr ? a.lc + rel(MS * MS) : nullptr);
                 PA_TICK(13);
                 wave_sync();      // every read of the image is done

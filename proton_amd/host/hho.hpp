@@ -1038,6 +1038,46 @@ class assembler {
         if (!RHS.empty()) d_RHS.download(RHS.data(), RHS.size());
         device_csr_ = true;
     }
+
+    // The fictitious-domain twin (the loop of cuthho_square.cpp:881-905 on a preprocessed cuthho_poly_mesh, host/cuthho.hpp): the
+    // uncut cells' right-hand sides, the cut cells' operators (pa_cut_local_ops_batch) and pa_fictdom_csr_assemble, which writes
+    // values and right-hand side of the same pattern -- uncut cells from the operator kernel's on-chip image, cut cells from the
+    // cut kernel's matrices.  `where` is the element_location of the domain; the level set is the one the mesh was preprocessed
+    // with.  LHS and RHS are left as assemble_all_fused leaves them.
+    template <typename LevelSet, typename Location>
+    void assemble_all_fictdom(const Mesh &msh, const LevelSet & /*level_set_function*/, Location where, int rhs_fn, int dirichlet_fn)
+    {
+        if (!msh.preprocessed) throw std::logic_error("cutHHO mesh not preprocessed");
+        auto &dev = proton_amd::device::instance();
+        pa_sizes sz;
+        dev.check(pa_sizes_for(di.c_abi(), PA_QUAD_FAN, &sz), "pa_sizes_for");
+        const int fd = (int)di.face_degree();
+        if (di.cell_degree() != di.face_degree() + 1) throw std::invalid_argument("assemble_all_fictdom: hho_degree_info(k + 1, k) expected");
+        const size_t n = msh.cells.size(), ncut = msh.num_cut_cells, mm = (size_t)sz.msize * sz.msize;
+        pa_assembler_csr_info info;
+        dev.check(pa_assembler_csr_query(dev.ctx(), di.c_abi(), &info), "pa_assembler_csr_query");
+        if (info.nrows != RHS.size()) throw std::runtime_error("assemble_all_fictdom: the device numbers another system than this assembler");
+        const size_t nnz = info.nnz;
+        proton_amd::device_buffer<double> d_rhs(n * sz.cbs), d_g(msh.faces.size() * sz.fbs), d_values(nnz ? nnz : 1), d_RHS(RHS.size() ? RHS.size() : 1),
+            d_cut_lc(ncut * mm + 1), d_cut_rhs(ncut * sz.cbs + 1);
+        proton_amd::device_buffer<int64_t> d_rowptr(RHS.size() + 1);
+        proton_amd::device_buffer<int32_t> d_colind(nnz ? nnz : 1);
+        dev.check(pa_dirichlet_data_batch(dev.ctx(), fd, dirichlet_fn, nullptr, d_g.get()), "pa_dirichlet_data_batch");
+        dev.check(pa_cut_uncut_rhs_batch(dev.ctx(), (int)di.cell_degree(), (int)where, rhs_fn, d_rhs.get()), "pa_cut_uncut_rhs_batch");
+        if (ncut)
+            dev.check(pa_cut_local_ops_batch(dev.ctx(), fd, &msh.level_set, (int)where, rhs_fn, dirichlet_fn, nullptr, nullptr, nullptr,
+                                             d_cut_lc.get(), d_cut_rhs.get(), nullptr), "pa_cut_local_ops_batch");
+        dev.check(pa_assembler_csr_pattern(dev.ctx(), di.c_abi(), d_rowptr.get(), d_colind.get()), "pa_assembler_csr_pattern");
+        dev.check(pa_fictdom_csr_assemble(dev.ctx(), fd, (int)where, d_rhs.get(), d_g.get(), ncut ? d_cut_lc.get() : nullptr,
+                                          ncut ? d_cut_rhs.get() : nullptr, d_values.get(), d_RHS.get(), nullptr, nullptr),
+                  "pa_fictdom_csr_assemble");
+        LHS.nrows = LHS.ncols = RHS.size();
+        LHS.rowptr.resize(RHS.size() + 1); LHS.colind.resize(nnz); LHS.values.resize(nnz);
+        d_rowptr.download(LHS.rowptr.data(), LHS.rowptr.size());
+        if (nnz) { d_colind.download(LHS.colind.data(), nnz); d_values.download(LHS.values.data(), nnz); }
+        if (!RHS.empty()) d_RHS.download(RHS.data(), RHS.size());
+        device_csr_ = true;
+    }
 };
 
 template <typename Mesh>
