@@ -5,6 +5,9 @@ csrc/pa_configs.def, compiled in parallel, plus csrc/capi.hip, csrc/csr.hip, csr
 csrc/condensed.hip, csrc/assembler_csr.hip, csrc/interface_csr.hip, csrc/interface_condensed.hip and
 csrc/comm.hip; linked into
 proton_amd/lib/libproton_amd.so.  hipcc cross-compiles without a GPU.
+
+build_probe(): tests/hip/dd_probe.hip, the test probe of csrc/dd_arith.hpp, with the same flags into
+proton_amd/lib/probe/libpa_dd_probe.so (a library of its own: libproton_amd.so gains no symbol).
 """
 import concurrent.futures
 import os
@@ -21,6 +24,9 @@ _TAG = os.environ.get("PA_BUILD_TAG")
 _OUT = os.path.join(HERE, "lib", "variants", _TAG) if _TAG else os.path.join(HERE, "lib")
 OBJ_DIR = os.path.join(_OUT, "obj")
 LIB_PATH = os.path.join(_OUT, "libproton_amd.so")
+# the test probe of csrc/dd_arith.hpp (tests/test_gpu_dd_primitives.py): a library of its own, outside csrc/ and build_stamp()
+PROBE_SRC = os.path.join(HERE, "..", "tests", "hip", "dd_probe.hip")
+PROBE_LIB_PATH = os.path.join(_OUT, "probe", "libpa_dd_probe.so")
 ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 if _TAG:                                    # tuning builds read the profiling knobs (PA_ABLATE, PA_BLOCKS_PER_CU, PA_LANES_PER_CELL)
@@ -153,7 +159,29 @@ def build(force=False, verbose=False, jobs=None):
             raise RuntimeError("link failed: %s\n%s" % (" ".join(cmd), r.stderr[-4000:]))
         if verbose:
             print("proton_amd: linked", LIB_PATH, flush=True)
+    build_probe(force=force, verbose=verbose)
     return LIB_PATH
+
+
+def build_probe(force=False, verbose=False):
+    """tests/hip/dd_probe.hip -> lib/probe/libpa_dd_probe.so: the primitives of csrc/dd_arith.hpp behind a C entry point each,
+    compiled with exactly FLAGS -- the test is about what the shipped flags make of the header -- and linked apart from
+    libproton_amd.so, which gains no symbol.  Built here so that the GPU tests compile nothing."""
+    out = os.path.dirname(PROBE_LIB_PATH)
+    os.makedirs(out, exist_ok=True)
+    obj = os.path.join(out, "dd_probe.o")
+    newest = max(_deps_mtime(), os.path.getmtime(PROBE_SRC))
+    rebuilt = force or _stale(obj, [], newest)
+    if rebuilt:
+        _compile((PROBE_SRC, obj, []))
+    if rebuilt or not os.path.exists(PROBE_LIB_PATH) or os.path.getmtime(PROBE_LIB_PATH) < os.path.getmtime(obj):
+        cmd = [hipcc(), "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", PROBE_LIB_PATH, obj]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError("link failed: %s\n%s" % (" ".join(cmd), r.stderr[-4000:]))
+        if verbose:
+            print("proton_amd: linked", PROBE_LIB_PATH, flush=True)
+    return PROBE_LIB_PATH
 
 
 if __name__ == "__main__":
