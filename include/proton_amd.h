@@ -375,6 +375,25 @@ int pa_obstacle_expand_solution(pa_context *ctx, pa_degree_info di, const double
 int pa_obstacle_take_local_data_batch(pa_context *ctx, pa_degree_info di, size_t first, size_t n,
                                       const double *d_expanded, double *d_out);
 
+/* obstacle_assembler::assemble + finalize (hho.hpp:609-695, :746-750) for ALL cells of a whole-mesh context -- the cell loop
+ * of the active-set iteration, obstacle.cpp:147-158 -- built DIRECTLY in CSR: no triplets, no sort, no host scatter.  Cell
+ * degree 0 only (cbs = 1, what obstacle.cpp:51 uses): there the system is the plain assembler's system of the pair (0, face_deg)
+ * with its columns renumbered by the active set, an order-preserving compaction of the pattern of pa_assembler_csr_pattern.
+ * Inputs as pa_obstacle_triplets_batch with first = 0, n = ncells (d_rhs ncells or NULL, d_g pa_dirichlet_data_batch or NULL;
+ * d_in_A / d_A_ct / d_B_ct / num_I of pa_obstacle_tables).  Outputs sized by pa_assembler_csr_query(ctx, di): d_rowptr
+ * nrows + 1 (int64), d_colind / d_values with room for its nnz (the count reached when the active set is empty), d_RHS nrows
+ * (may be NULL); *nnz (host) receives the stored count = that nnz - fbs * #{(non-Dirichlet face, active adjacent cell)} after a
+ * stream synchronise, as in pa_csr_from_triplets.  Nothing at or beyond *nnz is written.
+ * Contract: d_rowptr, d_colind[:*nnz], d_values[:*nnz] and *nnz are BIT-IDENTICAL to pa_csr_from_triplets of
+ * pa_obstacle_triplets_batch with the same arguments; d_RHS equals the scatter-add of that call's d_rhs_vals in cell order onto
+ * zeros.  Refusals, before any output buffer is touched: a NULL pointer other than d_rhs / d_g / d_RHS, num_I > ncells, 2^31
+ * rows and more, a row slab ("whole mesh" in pa_last_error): PA_ERR_INVALID_ARG; a degree outside the tables or
+ * cell_deg != 0 (the overlapping cell rows of hho.hpp:631 for cbs > 1 stay with the triplet route): PA_ERR_INVALID_DEGREE. */
+int pa_obstacle_csr_assemble(pa_context *ctx, pa_degree_info di,
+                             const double *d_lc, const double *d_rhs /* or NULL */, const double *d_g /* or NULL */,
+                             const double *d_gamma, const uint8_t *d_in_A, const int32_t *d_A_ct, const int32_t *d_B_ct, size_t num_I,
+                             int64_t *d_rowptr, int32_t *d_colind, double *d_values, double *d_RHS /* or NULL */, size_t *nnz);
+
 /* SparseMatrix::setFromTriplets (hho.hpp:451-455, :746-750; cuthho_square.cpp:1437-1441) on the
  * device: nslots triplet slots (a negative row or column = a slot the assembler did not push) ->
  * CSR with duplicates summed in push order.  d_rowptr nrows+1 (int64), d_colind / d_values with room

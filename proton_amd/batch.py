@@ -331,6 +331,20 @@ class BatchAssembler:
         self.ctx.obstacle_take_local_data(di, first, n, expanded.data_ptr(), out.data_ptr())
         return out
 
+    def obstacle_csr_assemble(self, fd, lc, rhs, g, gamma, in_A, A_ct, B_ct, num_I):
+        """obstacle_assembler::assemble + finalize for cell degree 0, directly in CSR (pa_obstacle_csr_assemble): bit-identical to
+        csr_from_triplets(obstacle_triplets(0, fd, ..)) -> (rowptr int64 [nrows+1], colind int32 [nnz], values [nnz], RHS [nrows])"""
+        di = capi.DegreeInfo(0, fd, fd + 1)      # cell degree 0 as it is: degree_info(0, fd) reverts to equal order for fd > 1
+        info = self.ctx.assembler_csr_query(di)
+        rowptr = torch.empty(info.nrows + 1, dtype=torch.int64, device=self.device)
+        colind = torch.empty(max(info.nnz, 1), dtype=torch.int32, device=self.device)
+        values = torch.empty(max(info.nnz, 1), dtype=torch.float64, device=self.device)
+        RHS = torch.empty(max(info.nrows, 1), dtype=torch.float64, device=self.device)
+        nnz = self.ctx.obstacle_csr_assemble(di, lc.data_ptr(), _ptr(rhs), _ptr(g), gamma.data_ptr(), in_A.data_ptr(), A_ct.data_ptr(),
+                                             B_ct.data_ptr(), num_I, rowptr.data_ptr(), colind.data_ptr(), values.data_ptr(),
+                                             RHS.data_ptr())
+        return rowptr, colind[:nnz], values[:nnz], RHS[:info.nrows]
+
     # ---- cutHHO fictitious domain (cuthho_square -f) ------------------------------------
     def cut_preprocess(self, N, radius=0.35, center=(0.5, 0.5), refsteps=4, rows=None, line_y=None):
         """cuthho_square.cpp:2026-2052: mesh, circle level set (or, line_y given, line_level_set y - line_y, :91-124), default (-D)

@@ -28,7 +28,7 @@ EXPORTS = [
     "pa_mesh_set_faces", "pa_assembler_query", "pa_dirichlet_data_batch", "pa_face_quadrature_points",
     "pa_triplets_batch", "pa_csr_from_triplets", "pa_conjugated_gradient", "pa_take_local_data_batch", "pa_project_function_batch", "pa_energy_form_batch",
     "pa_obstacle_tables", "pa_obstacle_triplets_batch", "pa_obstacle_expand_solution",
-    "pa_obstacle_take_local_data_batch",
+    "pa_obstacle_take_local_data_batch", "pa_obstacle_csr_assemble",
     "pa_cut_preprocess", "pa_cut_query", "pa_cut_local_ops_batch", "pa_cut_merge",
     "pa_cut_preprocess_agglomeration", "pa_cut_agglo_query", "pa_cut_query_tags", "pa_cut_quadrature_points", "pa_cut_rhs_sampled_batch",
     "pa_cut_interface_ops_batch", "pa_cut_interface_uncut_batch", "pa_interface_assembler_query",
@@ -194,6 +194,7 @@ def lib():
     L.pa_obstacle_triplets_batch.argtypes = [vp, DegreeInfo, sz, sz, dp, dp, dp, dp, vp, vp, vp, sz, dp, dp, dp, dp, dp]
     L.pa_obstacle_expand_solution.argtypes = [vp, DegreeInfo, dp, dp, dp, vp, vp, vp, sz, dp, dp]
     L.pa_obstacle_take_local_data_batch.argtypes = [vp, DegreeInfo, sz, sz, dp, dp]
+    L.pa_obstacle_csr_assemble.argtypes = [vp, DegreeInfo, dp, dp, dp, dp, vp, vp, vp, sz, dp, dp, dp, dp, C.POINTER(sz)]
     L.pa_cut_preprocess.argtypes = [vp, sz, sz, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(LevelSet), C.c_int]
     L.pa_cut_preprocess_rows.argtypes = [vp, sz, sz, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(LevelSet), C.c_int, sz, sz]
     L.pa_cut_merge_condensed.argtypes = [vp, C.c_int, dp, dp, dp]
@@ -512,6 +513,12 @@ class Context:
     def obstacle_take_local_data(self, di, first, n, expanded, out):
         self._ck(self._L.pa_obstacle_take_local_data_batch(self.h, di, first, n, expanded, out),
                  "pa_obstacle_take_local_data_batch")
+
+    def obstacle_csr_assemble(self, di, lc, rhs, g, gamma, in_A, A_ct, B_ct, num_I, rowptr, colind, values, RHS):
+        nnz = C.c_size_t(0)
+        self._ck(self._L.pa_obstacle_csr_assemble(self.h, di, lc, rhs, g, gamma, in_A, A_ct, B_ct, num_I, rowptr, colind, values, RHS,
+                                                  C.byref(nnz)), "pa_obstacle_csr_assemble")
+        return nnz.value
 
     def cut_quadrature_points(self, face_deg, where, which):
         """-> (offsets[ncut+1] uint32, xyw[count, 3]) host arrays"""

@@ -17,6 +17,7 @@
 #include "assembler_csr.hpp"
 #include "interface_csr.hpp"
 #include "interface_rows.hpp"
+#include "obstacle_csr.hpp"
 #include "cut_host.hpp"
 #include "hho_assembly.hpp"
 #include "hho_aux.hpp"
@@ -1497,6 +1498,48 @@ int pa_assembler_csr_assemble(pa_context *ctx, pa_degree_info di, int quad_kind,
     o.scatter.tab = ctx->d_asm_scatter; o.scatter.g = d_g; o.scatter.values = d_values; o.scatter.RHS = d_RHS;
     o.scatter.cell_nnz = cell_nnz; o.scatter.ncells = ctx->ncells;
     return run_local_ops(ctx, di, quad_kind, stab_kind, 0, ctx->ncells, o);
+}
+
+// ---- obstacle_assembler's system (cell degree 0) directly in CSR: obstacle_csr.hip -----------------------------------
+int pa_obstacle_csr_assemble(pa_context *ctx, pa_degree_info di, const double *d_lc, const double *d_rhs, const double *d_g,
+                             const double *d_gamma, const uint8_t *d_in_A, const int32_t *d_A_ct, const int32_t *d_B_ct, size_t num_I,
+                             int64_t *d_rowptr, int32_t *d_colind, double *d_values, double *d_RHS, size_t *nnz)
+{
+    if (!ctx) return PA_ERR_INVALID_ARG;
+    // every refusal comes before the first launch that touches an output buffer
+    if (!d_lc || !d_gamma || !d_in_A || !d_A_ct || !d_B_ct || !d_rowptr || !d_colind || !d_values || !nnz) {
+        ctx->last_error = "pa_obstacle_csr_assemble: only d_rhs, d_g and d_RHS may be NULL";
+        return PA_ERR_INVALID_ARG;
+    }
+    (void)hipSetDevice(ctx->device);
+    if (di.cell_deg < 0 || di.face_deg < 0 || di.face_deg > 3 || di.cell_deg > 4) return PA_ERR_INVALID_DEGREE;
+    if (di.cell_deg != 0) {
+        ctx->last_error = "pa_obstacle_csr_assemble: the direct path covers cell degree 0 (cbs = 1, obstacle.cpp:51); the overlapping "
+                          "cell rows of hho.hpp:631 for cbs > 1 stay with pa_obstacle_triplets_batch + pa_csr_from_triplets";
+        return PA_ERR_INVALID_DEGREE;
+    }
+    if (!ctx->d_cell_faces) return PA_ERR_NO_MESH;
+    if (!whole_mesh(ctx)) { ctx->last_error = "obstacle assembler needs the whole mesh on the context"; return PA_ERR_INVALID_ARG; }
+    const int fbs = di.face_deg + 1;
+    if (num_I > ctx->ncells || ctx->ncells + (uint64_t)fbs * ctx->num_other_faces >= ((uint64_t)1 << 31)) {      // int32 column ids
+        ctx->last_error = "pa_obstacle_csr_assemble: num_I beyond the cells of the mesh, or 2^31 rows and more";
+        return PA_ERR_INVALID_ARG;
+    }
+    const int st = asm_prepare(ctx);
+    if (st != PA_OK) return st;
+    uint64_t cell_nnz, nnz_plain, nrows;
+    asm_sizes(ctx, di, &cell_nnz, &nnz_plain, &nrows);
+    pa::ObstacleCsrArgs a;
+    a.cell_faces = ctx->d_cell_faces; a.face_compress = ctx->d_face_compress; a.faces = ctx->d_cfaces; a.lean = ctx->d_cfaces_lean;
+    a.colprefix = ctx->d_prefix; a.cprefix = ctx->d_asm_cprefix; a.fprefix = ctx->d_asm_fprefix;
+    a.ncells = (uint32_t)ctx->ncells; a.nown = ctx->cond_nown; a.cell_nnz = cell_nnz;
+    a.in_A = d_in_A; a.A_ct = d_A_ct; a.B_ct = d_B_ct; a.num_I = num_I; a.num_other = ctx->num_other_faces;
+    a.lc = d_lc; a.rhs = d_rhs; a.g = d_g; a.gamma = d_gamma;
+    a.rowptr = d_rowptr; a.colind = d_colind; a.values = d_values; a.RHS = d_RHS;
+    uint32_t removed = 0;
+    PA_HIP(ctx, pa::obstacle_csr_assemble(ctx->stream, fbs, a, &removed));
+    *nnz = (size_t)(nnz_plain - (uint64_t)fbs * removed);
+    return PA_OK;
 }
 
 int pa_condensed_halo_pack(pa_context *ctx, pa_degree_info di, const double *d_cond, const double *d_g, double *d_halo)

@@ -10,6 +10,7 @@
 
 #include "hho_aux.hpp"
 #include "hho_device.hpp"
+#include "obstacle_rhs.hpp"
 #include "scan.hpp"
 #include "structured_mesh.hpp"
 
@@ -346,11 +347,8 @@ __global__ __launch_bounds__(256) void obstacle_triplets_kernel(ObstacleArgs o)
             }
         }
         for (int i = threadIdx.x; i < msize; i += blockDim.x) {
-            double s = 0.0;
-            if (row[i] >= 0)
-                for (int j = 0; j < msize; ++j)
-                    if (col[j] < 0) s -= A[i + j * msize] * (j < a.cbs ? gam : dd[j]);    // :676-679
-            if (i < a.cbs && a.rhs != nullptr) s += a.rhs[c * a.cbs + i];                 // :686
+            const double s = obstacle_rhs_row(A, msize, a.cbs, i, row[i] >= 0, col, dd, gam,
+                                              a.rhs != nullptr ? a.rhs + c * a.cbs : nullptr);
             a.rhs_rows[c * msize + i] = row[i];
             a.rhs_vals[c * msize + i] = row[i] >= 0 ? s : 0.0;
         }

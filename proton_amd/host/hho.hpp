@@ -1270,6 +1270,42 @@ class obstacle_assembler {
         for (size_t k = 0; k < rr.size(); ++k)
             if (rr[k] >= 0) RHS[rr[k]] += rv[k];
     }
+
+    // The same span (obstacle.cpp:147-158 and finalize, hho.hpp:609-695, :746-750) without triplets, sort or host scatter
+    // (pa_obstacle_tables + pa_obstacle_csr_assemble): LHS and RHS are copies of the device arrays, bit-identical to what
+    // assemble_all + finalize leave.  Cell degree 0 only (obstacle.cpp:51); finalize() is a no-op for this assembly.
+    void assemble_all_csr(const Mesh &msh, const double *d_lc, const double *d_rhs, const double *d_g, const std::vector<T> &gamma)
+    {
+        auto &dev = proton_amd::device::instance();
+        proton_amd::batch_cache<Mesh>::instance().ensure_mesh(msh);
+        const size_t n = num_all_cells;
+        std::vector<uint8_t> flags(n);
+        for (size_t c = 0; c < n; ++c) flags[c] = is_in_set_A[c] ? 1 : 0;
+        proton_amd::device_buffer<uint8_t> d_in(n);
+        proton_amd::device_buffer<int32_t> d_a(n), d_b(n);
+        proton_amd::device_buffer<double> d_gamma(n);
+        d_in.upload(flags.data(), n);
+        d_gamma.upload(gamma.data(), n);
+        size_t ni = 0, na = 0;
+        dev.check(pa_obstacle_tables(dev.ctx(), d_in.get(), d_a.get(), d_b.get(), &ni, &na), "pa_obstacle_tables");
+        pa_assembler_csr_info info;
+        dev.check(pa_assembler_csr_query(dev.ctx(), di.c_abi(), &info), "pa_assembler_csr_query");
+        if (info.nrows != RHS.size()) throw std::runtime_error("obstacle_assembler::assemble_all_csr: system size");
+        proton_amd::device_buffer<int64_t> d_rowptr(info.nrows + 1);
+        proton_amd::device_buffer<int32_t> d_colind(info.nnz ? info.nnz : 1);
+        proton_amd::device_buffer<double> d_values(info.nnz ? info.nnz : 1), d_RHS(info.nrows ? info.nrows : 1);
+        size_t nnz = 0;
+        dev.check(pa_obstacle_csr_assemble(dev.ctx(), di.c_abi(), d_lc, d_rhs, d_g, d_gamma.get(), d_in.get(), d_a.get(), d_b.get(), ni,
+                                           d_rowptr.get(), d_colind.get(), d_values.get(), d_RHS.get(), &nnz),
+                  "pa_obstacle_csr_assemble");
+        LHS.nrows = LHS.ncols = RHS.size();
+        LHS.rowptr.resize(RHS.size() + 1); LHS.colind.resize(nnz); LHS.values.resize(nnz);
+        d_rowptr.download(LHS.rowptr.data(), LHS.rowptr.size());
+        if (nnz) { d_colind.download(LHS.colind.data(), nnz); d_values.download(LHS.values.data(), nnz); }
+        if (!RHS.empty()) d_RHS.download(RHS.data(), RHS.size());
+        triplets.clear();
+        device_csr_ = true;
+    }
 };
 
 // hho.hpp:753-782
