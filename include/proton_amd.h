@@ -394,6 +394,80 @@ int pa_obstacle_csr_assemble(pa_context *ctx, pa_degree_info di,
                              const double *d_gamma, const uint8_t *d_in_A, const int32_t *d_A_ct, const int32_t *d_B_ct, size_t num_I,
                              int64_t *d_rowptr, int32_t *d_colind, double *d_values, double *d_RHS /* or NULL */, size_t *nnz);
 
+/* The solve of that system -- obstacle.cpp:170-175, Eigen::SparseLU in the reference -- on the device, in place on the arrays
+ * pa_obstacle_csr_assemble wrote.  The system of obstacle_assembler::assemble (hho.hpp:609-695) keeps its rows where the plain
+ * assembler has them (cell rows at the cell index, face rows behind them) and compacts its columns: inactive cells at [0, num_I),
+ * face unknowns up to nk = nrows - num_A, multipliers at [nk, nrows).  An active cell's row holds its multiplier with
+ * coefficient 1 and no other row holds one (hho.hpp:688-693).  Hence the kept rows (inactive cells in d_A_ct order, then all face
+ * rows) against the columns below nk are a symmetric positive definite block K, and each remaining row defines one multiplier.
+ * K goes to the reference's conjugate gradient (pa_conjugated_gradient, which stands in for the SparseLU) through a row map --
+ * no copy of d_colind / d_values is made --, then x[column of the multiplier] = b_i - sum_j A_ij x_j for every active row i.
+ * Inputs: the arrays and d_RHS of pa_obstacle_csr_assemble for (ctx, di), the tables and num_I of pa_obstacle_tables, the solver
+ * parameters of pa_conjugated_gradient.  Output: d_x, nrows values in the reference's solution layout, what
+ * pa_obstacle_expand_solution reads; the three results of pa_conjugated_gradient (host, each may be NULL).
+ * Contract: d_x[:nk], *exit_reason, *iterations and *relative_residual are BIT-IDENTICAL to pa_conjugated_gradient on K
+ * extracted into arrays of its own; a multiplier differs from its evaluation in another order by rounding only.  nk = 0 (every
+ * cell active, every face Dirichlet) returns converged after 0 iterations.  A solve that does not converge is not an error: the
+ * status is PA_OK, *exit_reason says why, d_x holds the last iterate and its multipliers.
+ * Refusals, before anything is written: a NULL pointer other than the three results, num_I > ncells, a row slab ("whole mesh" in
+ * pa_last_error): PA_ERR_INVALID_ARG; a degree outside the tables or cell_deg != 0: PA_ERR_INVALID_DEGREE.
+ * Returns after the stream has drained. */
+int pa_obstacle_block_solve(pa_context *ctx, pa_degree_info di,
+                            const int64_t *d_rowptr, const int32_t *d_colind, const double *d_values, const double *d_RHS,
+                            const uint8_t *d_in_A, const int32_t *d_A_ct, const int32_t *d_B_ct, size_t num_I,
+                            double convergence_threshold, double divergence_threshold, size_t max_iter, int apply_preconditioner,
+                            double *d_x, int32_t *exit_reason, size_t *iterations, double *relative_residual);
+
+/* The active set of the next iteration and the stopping norm of this one (obstacle.cpp:133-142 and :193) in one pass:
+ *   d_in_A[i] = (d_beta[i] + c * (d_alpha[i] - d_gamma[i])) < 0    for the ncells cells (cell degree 0: one value per cell),
+ * the difference, the product and the sum each rounded on its own as the reference's expression is (no fused multiply-add: it
+ * can flip the flag of a cell whose exact value is a rounding error away from zero; a value of exactly zero is inactive);
+ * *num_A = active cells; *changed = cells whose flag differs from d_in_A_prev (NULL: from the empty set; may be d_in_A itself);
+ * *step_norm = || d_alpha_prev - d_alpha ||_2 over all ncells + fbs * nfaces values (d_alpha_prev NULL: zeros), summed by a
+ * block-tree reduction in a fixed order: the same bits from run to run.  The three results are host pointers, each may be NULL.
+ * Whole-mesh contexts, cell degree 0, as pa_obstacle_csr_assemble.  Returns after the stream has drained. */
+int pa_obstacle_active_set_update(pa_context *ctx, pa_degree_info di, double c,
+                                  const double *d_alpha, const double *d_beta, const double *d_gamma,
+                                  const double *d_alpha_prev /* or NULL */, const uint8_t *d_in_A_prev /* or NULL */,
+                                  uint8_t *d_in_A, size_t *num_A, size_t *changed, double *step_norm);
+
+/* The primal-dual active set loop of run_hho_obstacle (obstacle.cpp:117-197) in one call, on the reference's own system (not a
+ * condensed one), every array on the device; the host reads a few scalars per outer iteration.  From alpha = 0, beta = 1
+ * (obstacle.cpp:98-99), until max_outer systems have been solved: pa_obstacle_active_set_update, pa_obstacle_tables,
+ * pa_obstacle_csr_assemble, pa_obstacle_block_solve, pa_obstacle_expand_solution, and the step norm of :193 (formed by the
+ * update that also yields the next active set); the loop ends converged when that norm is below outer_tol.
+ * The CSR arrays (pa_assembler_csr_query's sizes), the solver's vectors, the row map and the solution buffers are allocated
+ * once per call and freed on every path out.
+ * Inputs: d_lc (pa_local_ops_batch for the pair (0, face_deg)), d_rhs (ncells or NULL), d_g (pa_dirichlet_data_batch or NULL),
+ * d_gamma (ncells: the obstacle at the barycentres).  Outputs: d_alpha (ncells + fbs * nfaces), d_beta (ncells), d_in_A (ncells:
+ * the active set of the last system solved), *info, and two optional host arrays of max_outer entries, filled up to
+ * info->outer_iterations: the number of active cells and the conjugate gradient's iterations of every system.
+ * A conjugate gradient that does not converge ends the loop: the status is PA_OK, info->converged = 0, info->cg_exit_reason
+ * holds pa_conjugated_gradient's code (1 diverged, 2 max_iter), d_alpha / d_beta are those of the last completed iteration
+ * (alpha = 0, beta = 1 if the first solve failed) and d_in_A is the active set they give, the one whose system was not solved.
+ * Refusals, before anything is written: NULL d_lc / d_gamma / params / d_alpha / d_beta / d_in_A / info, max_outer = 0, a row
+ * slab: PA_ERR_INVALID_ARG; a degree outside the tables or cell_deg != 0: PA_ERR_INVALID_DEGREE. */
+typedef struct {
+    double c;                          /* obstacle.cpp:101: 1.0 */
+    size_t max_outer;                  /* systems solved at most; the reference's loop: 50 (obstacle.cpp:119) */
+    double outer_tol;                  /* the reference's 1e-7 (obstacle.cpp:193) */
+    double cg_convergence_threshold, cg_divergence_threshold;
+    size_t cg_max_iter;                /* 0 = 20 * nk of the system at hand */
+    int32_t apply_preconditioner;      /* Jacobi */
+} pa_obstacle_solve_params;
+typedef struct {
+    uint64_t outer_iterations;         /* systems solved */
+    uint64_t cg_iterations;            /* over all of them */
+    double last_step_norm;             /* || alpha_prev - alpha ||_2 of the last completed iteration */
+    int32_t converged;                 /* last_step_norm < outer_tol */
+    int32_t cg_exit_reason;            /* of the last solve */
+} pa_obstacle_solve_info;
+int pa_obstacle_solve(pa_context *ctx, pa_degree_info di,
+                      const double *d_lc, const double *d_rhs /* or NULL */, const double *d_g /* or NULL */, const double *d_gamma,
+                      const pa_obstacle_solve_params *params,
+                      double *d_alpha, double *d_beta, uint8_t *d_in_A, pa_obstacle_solve_info *info,
+                      size_t *num_A_history /* or NULL */, size_t *cg_iterations_history /* or NULL */);
+
 /* SparseMatrix::setFromTriplets (hho.hpp:451-455, :746-750; cuthho_square.cpp:1437-1441) on the
  * device: nslots triplet slots (a negative row or column = a slot the assembler did not push) ->
  * CSR with duplicates summed in push order.  d_rowptr nrows+1 (int64), d_colind / d_values with room

@@ -3,7 +3,7 @@
 One translation unit per (cell degree, face degree, quadrature kind) listed in
 csrc/pa_configs.def, compiled in parallel, plus csrc/capi.hip, csrc/csr.hip, csrc/solver.hip,
 csrc/condensed.hip, csrc/assembler_csr.hip, csrc/interface_csr.hip, csrc/interface_condensed.hip,
-csrc/obstacle_csr.hip and csrc/comm.hip; linked into
+csrc/obstacle_csr.hip, csrc/obstacle_solve.hip and csrc/comm.hip; linked into
 proton_amd/lib/libproton_amd.so.  hipcc cross-compiles without a GPU.
 
 build_probe(): tests/hip/dd_probe.hip, the test probe of csrc/dd_arith.hpp, with the same flags into
@@ -139,7 +139,7 @@ def build(force=False, verbose=False, jobs=None):
              else PER_CONFIG_FLAGS.get((cd, fd, q), []))
         if force or _stale(obj, defs, newest):
             todo.append((os.path.join(CSRC, "hho_inst.hip"), obj, defs))
-    for unit in ("capi", "csr", "solver", "condensed", "assembler_csr", "interface_csr", "interface_condensed", "obstacle_csr", "comm"):
+    for unit in ("capi", "csr", "solver", "condensed", "assembler_csr", "interface_csr", "interface_condensed", "obstacle_csr", "obstacle_solve", "comm"):
         unit_obj = os.path.join(OBJ_DIR, unit + ".o")
         objs.append(unit_obj)
         if force or _stale(unit_obj, [], newest):

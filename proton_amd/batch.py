@@ -345,6 +345,46 @@ class BatchAssembler:
                                              RHS.data_ptr())
         return rowptr, colind[:nnz], values[:nnz], RHS[:info.nrows]
 
+    def obstacle_block_solve(self, fd, rowptr, colind, values, RHS, in_A, A_ct, B_ct, num_I, tol=1e-13, div=100.0, max_iter=None,
+                             precond=True):
+        """the solve of obstacle_csr_assemble's system (obstacle.cpp:170-175) in place: conjugated_gradient on the SPD block of the
+        inactive cells and the faces through a row map, then the multipliers from the active cells' rows (pa_obstacle_block_solve)
+        -> (x [nrows] in the layout obstacle_expand_solution reads, exit_reason, iterations, relative residual)"""
+        di = capi.DegreeInfo(0, fd, fd + 1)
+        nrows = rowptr.numel() - 1
+        if max_iter is None:
+            max_iter = 20 * (nrows - (self.ncells - num_I))
+        x = torch.empty(max(nrows, 1), dtype=torch.float64, device=self.device)
+        reason, iters, rr = self.ctx.obstacle_block_solve(di, rowptr.data_ptr(), colind.data_ptr(), values.data_ptr(), RHS.data_ptr(),
+                                                          in_A.data_ptr(), A_ct.data_ptr(), B_ct.data_ptr(), num_I, x.data_ptr(), tol, div,
+                                                          max_iter, precond)
+        return x[:nrows], reason, iters, rr
+
+    def obstacle_active_set_update(self, fd, alpha, beta, gamma, c=1.0, alpha_prev=None, in_A_prev=None, in_A=None):
+        """obstacle.cpp:133-142 and :193 in one pass (pa_obstacle_active_set_update): in_A = beta + c (alpha - gamma) < 0, unfused
+        -> (in_A uint8 [ncells], num_A, cells whose flag differs from in_A_prev, || alpha_prev - alpha ||_2)"""
+        di = capi.DegreeInfo(0, fd, fd + 1)
+        if in_A is None:
+            in_A = torch.empty(self.ncells, dtype=torch.uint8, device=self.device)
+        num_A, changed, norm = self.ctx.obstacle_active_set_update(di, c, alpha.data_ptr(), beta.data_ptr(), gamma.data_ptr(),
+                                                                   _ptr(alpha_prev), _ptr(in_A_prev), in_A.data_ptr())
+        return in_A, num_A, changed, norm
+
+    def obstacle_solve(self, fd, lc, rhs, g, gamma, c=1.0, max_outer=50, outer_tol=1e-7, tol=1e-13, div=100.0, cg_max_iter=0,
+                       precond=True):
+        """the primal-dual active set loop of obstacle.cpp:117-197 on the device (pa_obstacle_solve)
+        -> dict(alpha [ncells + fbs nfaces], beta [ncells], in_A uint8 [ncells], info = capi.ObstacleSolveInfo, num_A = [per system],
+        cg_iterations = [per system])"""
+        di = capi.DegreeInfo(0, fd, fd + 1)
+        nfaces = self.ctx.assembler_query(di).nfaces_local
+        alpha = torch.empty(self.ncells + (fd + 1) * nfaces, dtype=torch.float64, device=self.device)
+        beta = torch.empty(self.ncells, dtype=torch.float64, device=self.device)
+        in_A = torch.empty(self.ncells, dtype=torch.uint8, device=self.device)
+        params = capi.ObstacleSolveParams(c, max_outer, outer_tol, tol, div, cg_max_iter, precond)
+        info, hist_a, hist_cg = self.ctx.obstacle_solve(di, lc.data_ptr(), _ptr(rhs), _ptr(g), gamma.data_ptr(), params, alpha.data_ptr(),
+                                                        beta.data_ptr(), in_A.data_ptr())
+        return {"alpha": alpha, "beta": beta, "in_A": in_A, "info": info, "num_A": hist_a, "cg_iterations": hist_cg}
+
     # ---- cutHHO fictitious domain (cuthho_square -f) ------------------------------------
     def cut_preprocess(self, N, radius=0.35, center=(0.5, 0.5), refsteps=4, rows=None, line_y=None):
         """cuthho_square.cpp:2026-2052: mesh, circle level set (or, line_y given, line_level_set y - line_y, :91-124), default (-D)

@@ -29,6 +29,7 @@ EXPORTS = [
     "pa_triplets_batch", "pa_csr_from_triplets", "pa_conjugated_gradient", "pa_take_local_data_batch", "pa_project_function_batch", "pa_energy_form_batch",
     "pa_obstacle_tables", "pa_obstacle_triplets_batch", "pa_obstacle_expand_solution",
     "pa_obstacle_take_local_data_batch", "pa_obstacle_csr_assemble",
+    "pa_obstacle_block_solve", "pa_obstacle_active_set_update", "pa_obstacle_solve",
     "pa_cut_preprocess", "pa_cut_query", "pa_cut_local_ops_batch", "pa_cut_merge",
     "pa_cut_preprocess_agglomeration", "pa_cut_agglo_query", "pa_cut_query_tags", "pa_cut_quadrature_points", "pa_cut_rhs_sampled_batch",
     "pa_cut_interface_ops_batch", "pa_cut_interface_uncut_batch", "pa_interface_assembler_query",
@@ -89,6 +90,22 @@ class AssemblerInfo(C.Structure):
 
 class AssemblerCsrInfo(C.Structure):
     _fields_ = [("nrows", C.c_uint64), ("nnz", C.c_uint64)]
+
+
+class ObstacleSolveParams(C.Structure):
+    """pa_obstacle_solve_params; the defaults are the reference's (obstacle.cpp:101, :119, :193) and the drivers' solver settings"""
+    _fields_ = [("c", C.c_double), ("max_outer", C.c_size_t), ("outer_tol", C.c_double), ("cg_convergence_threshold", C.c_double),
+                ("cg_divergence_threshold", C.c_double), ("cg_max_iter", C.c_size_t), ("apply_preconditioner", C.c_int32)]
+
+    def __init__(self, c=1.0, max_outer=50, outer_tol=1e-7, cg_convergence_threshold=1e-13, cg_divergence_threshold=100.0,
+                 cg_max_iter=0, apply_preconditioner=1):
+        super().__init__(c, max_outer, outer_tol, cg_convergence_threshold, cg_divergence_threshold, cg_max_iter,
+                         int(apply_preconditioner))
+
+
+class ObstacleSolveInfo(C.Structure):
+    _fields_ = [("outer_iterations", C.c_uint64), ("cg_iterations", C.c_uint64), ("last_step_norm", C.c_double),
+                ("converged", C.c_int32), ("cg_exit_reason", C.c_int32)]
 
 
 class InterfaceCondensedInfo(C.Structure):
@@ -195,6 +212,12 @@ def lib():
     L.pa_obstacle_expand_solution.argtypes = [vp, DegreeInfo, dp, dp, dp, vp, vp, vp, sz, dp, dp]
     L.pa_obstacle_take_local_data_batch.argtypes = [vp, DegreeInfo, sz, sz, dp, dp]
     L.pa_obstacle_csr_assemble.argtypes = [vp, DegreeInfo, dp, dp, dp, dp, vp, vp, vp, sz, dp, dp, dp, dp, C.POINTER(sz)]
+    L.pa_obstacle_block_solve.argtypes = [vp, DegreeInfo, dp, dp, dp, dp, vp, vp, vp, sz, C.c_double, C.c_double, sz, C.c_int, dp,
+                                          C.POINTER(C.c_int32), C.POINTER(sz), C.POINTER(C.c_double)]
+    L.pa_obstacle_active_set_update.argtypes = [vp, DegreeInfo, C.c_double, dp, dp, dp, dp, vp, vp, C.POINTER(sz), C.POINTER(sz),
+                                                C.POINTER(C.c_double)]
+    L.pa_obstacle_solve.argtypes = [vp, DegreeInfo, dp, dp, dp, dp, C.POINTER(ObstacleSolveParams), dp, dp, vp,
+                                    C.POINTER(ObstacleSolveInfo), C.POINTER(sz), C.POINTER(sz)]
     L.pa_cut_preprocess.argtypes = [vp, sz, sz, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(LevelSet), C.c_int]
     L.pa_cut_preprocess_rows.argtypes = [vp, sz, sz, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(LevelSet), C.c_int, sz, sz]
     L.pa_cut_merge_condensed.argtypes = [vp, C.c_int, dp, dp, dp]
@@ -519,6 +542,30 @@ class Context:
         self._ck(self._L.pa_obstacle_csr_assemble(self.h, di, lc, rhs, g, gamma, in_A, A_ct, B_ct, num_I, rowptr, colind, values, RHS,
                                                   C.byref(nnz)), "pa_obstacle_csr_assemble")
         return nnz.value
+
+    def obstacle_block_solve(self, di, rowptr, colind, values, RHS, in_A, A_ct, B_ct, num_I, x, tol=1e-13, div=100.0, max_iter=1000,
+                             precond=True):
+        reason, iters, rr = C.c_int32(0), C.c_size_t(0), C.c_double(0.0)
+        self._ck(self._L.pa_obstacle_block_solve(self.h, di, rowptr, colind, values, RHS, in_A, A_ct, B_ct, num_I, tol, div, max_iter,
+                                                 int(precond), x, C.byref(reason), C.byref(iters), C.byref(rr)),
+                 "pa_obstacle_block_solve")
+        return reason.value, iters.value, rr.value
+
+    def obstacle_active_set_update(self, di, c, alpha, beta, gamma, alpha_prev, in_A_prev, in_A):
+        """-> (num_A, changed, step norm)"""
+        na, ch, nrm = C.c_size_t(0), C.c_size_t(0), C.c_double(0.0)
+        self._ck(self._L.pa_obstacle_active_set_update(self.h, di, c, alpha, beta, gamma, alpha_prev, in_A_prev, in_A, C.byref(na),
+                                                       C.byref(ch), C.byref(nrm)), "pa_obstacle_active_set_update")
+        return na.value, ch.value, nrm.value
+
+    def obstacle_solve(self, di, lc, rhs, g, gamma, params, alpha, beta, in_A):
+        """-> (ObstacleSolveInfo, num_A per system, conjugate-gradient iterations per system)"""
+        info = ObstacleSolveInfo()
+        hist_a, hist_cg = (C.c_size_t * params.max_outer)(), (C.c_size_t * params.max_outer)()
+        self._ck(self._L.pa_obstacle_solve(self.h, di, lc, rhs, g, gamma, C.byref(params), alpha, beta, in_A, C.byref(info), hist_a,
+                                           hist_cg), "pa_obstacle_solve")
+        n = info.outer_iterations
+        return info, list(hist_a[:n]), list(hist_cg[:n])
 
     def cut_quadrature_points(self, face_deg, where, which):
         """-> (offsets[ncut+1] uint32, xyw[count, 3]) host arrays"""

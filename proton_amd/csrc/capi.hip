@@ -18,6 +18,7 @@
 #include "interface_csr.hpp"
 #include "interface_rows.hpp"
 #include "obstacle_csr.hpp"
+#include "obstacle_solve.hpp"
 #include "cut_host.hpp"
 #include "hho_assembly.hpp"
 #include "hho_aux.hpp"
@@ -1539,6 +1540,193 @@ int pa_obstacle_csr_assemble(pa_context *ctx, pa_degree_info di, const double *d
     uint32_t removed = 0;
     PA_HIP(ctx, pa::obstacle_csr_assemble(ctx->stream, fbs, a, &removed));
     *nnz = (size_t)(nnz_plain - (uint64_t)fbs * removed);
+    return PA_OK;
+}
+
+// ---- the solve of that system and the active-set loop around it: obstacle_solve.hip -----------------------------------------
+// the refusals the three entry points share with pa_obstacle_csr_assemble; PA_OK = go on
+static int obstacle_solve_refusals(pa_context *ctx, pa_degree_info di, const char *who)
+{
+    if (di.cell_deg < 0 || di.face_deg < 0 || di.face_deg > 3 || di.cell_deg > 4) return PA_ERR_INVALID_DEGREE;
+    if (di.cell_deg != 0) {
+        ctx->last_error = std::string(who) + ": cell degree 0 only (cbs = 1, obstacle.cpp:51), as pa_obstacle_csr_assemble";
+        return PA_ERR_INVALID_DEGREE;
+    }
+    if (!ctx->d_cell_faces) return PA_ERR_NO_MESH;
+    if (!whole_mesh(ctx)) { ctx->last_error = "obstacle assembler needs the whole mesh on the context"; return PA_ERR_INVALID_ARG; }
+    if (ctx->ncells + (uint64_t)(di.face_deg + 1) * ctx->num_other_faces >= ((uint64_t)1 << 31)) {
+        ctx->last_error = std::string(who) + ": 2^31 rows and more";
+        return PA_ERR_INVALID_ARG;
+    }
+    return PA_OK;
+}
+
+static pa::ObstacleBlockArgs obstacle_block_args(const pa_context *ctx, pa_degree_info di, const int64_t *d_rowptr, const int32_t *d_colind,
+                                                 const double *d_values, const double *d_RHS, const uint8_t *d_in_A, const int32_t *d_A_ct,
+                                                 const int32_t *d_B_ct, size_t num_I, double *d_x)
+{
+    pa::ObstacleBlockArgs a;
+    a.ncells = (uint32_t)ctx->ncells; a.nrows = ctx->ncells + (uint64_t)(di.face_deg + 1) * ctx->num_other_faces; a.num_I = num_I;
+    a.rowptr = d_rowptr; a.colind = d_colind; a.values = d_values; a.RHS = d_RHS;
+    a.in_A = d_in_A; a.A_ct = d_A_ct; a.B_ct = d_B_ct; a.x = d_x;
+    return a;
+}
+
+int pa_obstacle_block_solve(pa_context *ctx, pa_degree_info di, const int64_t *d_rowptr, const int32_t *d_colind, const double *d_values,
+                            const double *d_RHS, const uint8_t *d_in_A, const int32_t *d_A_ct, const int32_t *d_B_ct, size_t num_I,
+                            double convergence_threshold, double divergence_threshold, size_t max_iter, int apply_preconditioner,
+                            double *d_x, int32_t *exit_reason, size_t *iterations, double *relative_residual)
+{
+    if (!ctx) return PA_ERR_INVALID_ARG;
+    if (!d_rowptr || !d_colind || !d_values || !d_RHS || !d_in_A || !d_A_ct || !d_B_ct || !d_x) {
+        ctx->last_error = "pa_obstacle_block_solve: only exit_reason, iterations and relative_residual may be NULL";
+        return PA_ERR_INVALID_ARG;
+    }
+    (void)hipSetDevice(ctx->device);
+    const int st = obstacle_solve_refusals(ctx, di, "pa_obstacle_block_solve");
+    if (st != PA_OK) return st;
+    if (num_I > ctx->ncells) { ctx->last_error = "pa_obstacle_block_solve: num_I beyond the cells of the mesh"; return PA_ERR_INVALID_ARG; }
+    int reason = 0;
+    PA_HIP(ctx, pa::obstacle_block_solve(ctx->stream, obstacle_block_args(ctx, di, d_rowptr, d_colind, d_values, d_RHS, d_in_A, d_A_ct, d_B_ct,
+                                                                          num_I, d_x),
+                                         nullptr, convergence_threshold, divergence_threshold, max_iter, apply_preconditioner, &reason,
+                                         iterations, relative_residual));
+    if (exit_reason) *exit_reason = reason;
+    return PA_OK;
+}
+
+static pa::ObstacleUpdateArgs obstacle_update_args(const pa_context *ctx, pa_degree_info di, double c, const double *d_alpha,
+                                                   const double *d_beta, const double *d_gamma, const double *d_alpha_prev,
+                                                   const uint8_t *d_in_A_prev, uint8_t *d_in_A)
+{
+    pa::ObstacleUpdateArgs a;
+    a.ncells = (uint32_t)ctx->ncells; a.nalpha = ctx->ncells + (uint64_t)(di.face_deg + 1) * ctx->nfaces_local; a.c = c;
+    a.alpha = d_alpha; a.beta = d_beta; a.gamma = d_gamma; a.alpha_prev = d_alpha_prev; a.in_A_prev = d_in_A_prev; a.in_A = d_in_A;
+    return a;
+}
+
+int pa_obstacle_active_set_update(pa_context *ctx, pa_degree_info di, double c, const double *d_alpha, const double *d_beta,
+                                  const double *d_gamma, const double *d_alpha_prev, const uint8_t *d_in_A_prev, uint8_t *d_in_A,
+                                  size_t *num_A, size_t *changed, double *step_norm)
+{
+    if (!ctx) return PA_ERR_INVALID_ARG;
+    if (!d_alpha || !d_beta || !d_gamma || !d_in_A) {
+        ctx->last_error = "pa_obstacle_active_set_update: d_alpha, d_beta, d_gamma and d_in_A are required";
+        return PA_ERR_INVALID_ARG;
+    }
+    (void)hipSetDevice(ctx->device);
+    const int st = obstacle_solve_refusals(ctx, di, "pa_obstacle_active_set_update");
+    if (st != PA_OK) return st;
+    pa::ObstacleUpdateResult r{0.0, 0, 0};
+    PA_HIP(ctx, pa::obstacle_active_set_update(ctx->stream, obstacle_update_args(ctx, di, c, d_alpha, d_beta, d_gamma, d_alpha_prev,
+                                                                                d_in_A_prev, d_in_A), nullptr, &r));
+    if (num_A) *num_A = (size_t)r.num_A;
+    if (changed) *changed = (size_t)r.changed;
+    if (step_norm) *step_norm = sqrt(r.step2);
+    return PA_OK;
+}
+
+namespace {
+// everything pa_obstacle_solve allocates: freed with the scope, after the stream has drained
+struct ObstacleLoopBuffers {
+    hipStream_t stream;
+    std::vector<void *> held;
+    pa::ObstacleSolveWorkspace ws;
+    explicit ObstacleLoopBuffers(hipStream_t s) : stream(s) {}
+    ObstacleLoopBuffers(const ObstacleLoopBuffers &) = delete;
+    ObstacleLoopBuffers &operator=(const ObstacleLoopBuffers &) = delete;
+    ~ObstacleLoopBuffers()
+    {
+        (void)hipStreamSynchronize(stream);
+        for (void *p : held) (void)hipFree(p);
+        pa::obstacle_workspace_release(&ws);
+    }
+    // *p = room for count (at least one) items of `size` bytes
+    hipError_t alloc(void *p, size_t count, size_t size)
+    {
+        void *q = nullptr;
+        const hipError_t e = hipMalloc(&q, (count ? count : 1) * size);
+        if (e != hipSuccess) return e;
+        held.push_back(q);
+        *(void **)p = q;
+        return hipSuccess;
+    }
+};
+}  // namespace
+
+int pa_obstacle_solve(pa_context *ctx, pa_degree_info di, const double *d_lc, const double *d_rhs, const double *d_g, const double *d_gamma,
+                      const pa_obstacle_solve_params *params, double *d_alpha, double *d_beta, uint8_t *d_in_A, pa_obstacle_solve_info *info,
+                      size_t *num_A_history, size_t *cg_iterations_history)
+{
+    if (!ctx) return PA_ERR_INVALID_ARG;
+    // every refusal comes before the first launch that touches an output buffer
+    if (!d_lc || !d_gamma || !params || !d_alpha || !d_beta || !d_in_A || !info) {
+        ctx->last_error = "pa_obstacle_solve: only d_rhs, d_g and the two history arrays may be NULL";
+        return PA_ERR_INVALID_ARG;
+    }
+    if (params->max_outer == 0) { ctx->last_error = "pa_obstacle_solve: max_outer = 0 solves nothing"; return PA_ERR_INVALID_ARG; }
+    (void)hipSetDevice(ctx->device);
+    int st = obstacle_solve_refusals(ctx, di, "pa_obstacle_solve");
+    if (st != PA_OK) return st;
+    pa_assembler_csr_info csr;
+    st = pa_assembler_csr_query(ctx, di, &csr);
+    if (st != PA_OK) return st;
+    const size_t nc = ctx->ncells, fbs = (size_t)di.face_deg + 1, nrows = (size_t)csr.nrows, nalpha = nc + fbs * ctx->nfaces_local;
+
+    ObstacleLoopBuffers buf(ctx->stream);
+    int64_t *rowptr = nullptr;
+    int32_t *colind = nullptr, *A_ct = nullptr, *B_ct = nullptr;
+    double *values = nullptr, *RHS = nullptr, *x = nullptr, *alpha[2] = {nullptr, nullptr}, *beta[2] = {nullptr, nullptr};
+    uint8_t *flags[2] = {nullptr, nullptr};
+    PA_HIP(ctx, buf.alloc(&rowptr, nrows + 1, 8)); PA_HIP(ctx, buf.alloc(&colind, (size_t)csr.nnz, 4)); PA_HIP(ctx, buf.alloc(&values, (size_t)csr.nnz, 8));
+    PA_HIP(ctx, buf.alloc(&RHS, nrows, 8)); PA_HIP(ctx, buf.alloc(&x, nrows, 8)); PA_HIP(ctx, buf.alloc(&A_ct, nc, 4)); PA_HIP(ctx, buf.alloc(&B_ct, nc, 4));
+    for (int i = 0; i < 2; ++i) {
+        PA_HIP(ctx, buf.alloc(&alpha[i], nalpha, 8)); PA_HIP(ctx, buf.alloc(&beta[i], nc, 8)); PA_HIP(ctx, buf.alloc(&flags[i], nc, 1));
+    }
+    PA_HIP(ctx, pa::obstacle_workspace_reserve(&buf.ws, nrows, nalpha));
+
+    // alpha = 0, beta = 1 (obstacle.cpp:98-99) and the first active set (:133-142)
+    PA_HIP(ctx, hipMemsetAsync(alpha[0], 0, nalpha * sizeof(double), ctx->stream));
+    PA_HIP(ctx, pa::obstacle_fill(ctx->stream, beta[0], nc, 1.0));
+    pa::ObstacleUpdateResult upd{0.0, 0, 0};
+    PA_HIP(ctx, pa::obstacle_active_set_update(ctx->stream, obstacle_update_args(ctx, di, params->c, alpha[0], beta[0], d_gamma, nullptr,
+                                                                                nullptr, flags[0]), &buf.ws, &upd));
+    pa_obstacle_solve_info out{0, 0, 0.0, 0, 0};
+    int cur = 0, fl = 0;                                   // alpha[cur] / beta[cur]: the last completed iteration; flags[fl]: its system's
+    while (out.outer_iterations < params->max_outer) {
+        size_t num_I = 0, num_A = 0, nnz = 0;
+        st = pa_obstacle_tables(ctx, flags[fl], A_ct, B_ct, &num_I, &num_A);
+        if (st != PA_OK) return st;
+        st = pa_obstacle_csr_assemble(ctx, di, d_lc, d_rhs, d_g, d_gamma, flags[fl], A_ct, B_ct, num_I, rowptr, colind, values, RHS, &nnz);
+        if (st != PA_OK) return st;
+        const size_t nk = nrows - num_A;
+        int reason = 0;
+        size_t iters = 0;
+        PA_HIP(ctx, pa::obstacle_block_solve(ctx->stream, obstacle_block_args(ctx, di, rowptr, colind, values, RHS, flags[fl], A_ct, B_ct, num_I, x),
+                                             &buf.ws, params->cg_convergence_threshold, params->cg_divergence_threshold,
+                                             params->cg_max_iter ? params->cg_max_iter : 20 * nk, params->apply_preconditioner, &reason,
+                                             &iters, nullptr));
+        if (num_A_history) num_A_history[out.outer_iterations] = num_A;
+        if (cg_iterations_history) cg_iterations_history[out.outer_iterations] = iters;
+        out.outer_iterations++;
+        out.cg_iterations += iters;
+        out.cg_exit_reason = reason;
+        if (reason != 0) break;                            // alpha[cur] / beta[cur] stay those of the last completed iteration
+        st = pa_obstacle_expand_solution(ctx, di, x, d_g, d_gamma, flags[fl], A_ct, B_ct, num_I, alpha[1 - cur], beta[1 - cur]);
+        if (st != PA_OK) return st;
+        // the step of this iteration (:193) and the active set of the next (:133-142) in one pass
+        PA_HIP(ctx, pa::obstacle_active_set_update(ctx->stream, obstacle_update_args(ctx, di, params->c, alpha[1 - cur], beta[1 - cur], d_gamma,
+                                                                                    alpha[cur], flags[fl], flags[1 - fl]), &buf.ws, &upd));
+        cur = 1 - cur;
+        out.last_step_norm = sqrt(upd.step2);
+        if (out.last_step_norm < params->outer_tol) { out.converged = 1; break; }
+        if (out.outer_iterations < params->max_outer) fl = 1 - fl;      // (after the last system its own flags are the result)
+    }
+    PA_HIP(ctx, hipMemcpyAsync(d_alpha, alpha[cur], nalpha * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    PA_HIP(ctx, hipMemcpyAsync(d_beta, beta[cur], nc * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    PA_HIP(ctx, hipMemcpyAsync(d_in_A, flags[fl], nc * sizeof(uint8_t), hipMemcpyDeviceToDevice, ctx->stream));
+    PA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *info = out;
     return PA_OK;
 }
 

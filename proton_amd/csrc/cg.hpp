@@ -1,0 +1,56 @@
+// cg.hpp -- what another translation unit needs to run solver.hip's conjugate gradient on a matrix it does not hold as a plain
+// CSR: the two launches that read the matrix (inverse diagonal, product with the search direction) behind two callbacks, and
+// the solver's device vectors as a workspace that outlives one solve.  Everything else -- the vector kernels, the reductions,
+// the exit tests and their order (solver_cg.hpp:63-144) -- is solver.hip's and runs unchanged.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+namespace pa {
+
+constexpr int RB = 256;            // threads per block of the vector kernels
+constexpr int ROW_LANES = 16;      // lanes that share a row in the SpMV (HHO rows hold 20-130 entries)
+
+// sum of v over the block (RB threads), the same value in every thread; sh holds RB / 64 doubles
+__device__ inline double block_sum(double v, double *sh)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) sh[wave] = v;
+    __syncthreads();
+    double s = 0.0;
+#pragma unroll
+    for (int w = 0; w < RB / 64; ++w) s += sh[w];
+    __syncthreads();
+    return s;
+}
+
+// The matrix of a solve.  inv_diag: iA[i] = 1 / A_ii, i < n, one thread per row.  spmv: y = A d and part_dy[blk] = the sum of
+// d[row] y[row] over the rows of block blk, for the grid of cg_spmv_kernel -- (n ROW_LANES + RB - 1) / RB blocks of RB threads,
+// ROW_LANES consecutive lanes per row, block_sum over the block -- so that the iterates do not depend on who formed the product.
+struct CgMatrixOps {
+    void *user;
+    void (*inv_diag)(void *user, hipStream_t stream, size_t n, double *iA);
+    void (*spmv)(void *user, hipStream_t stream, size_t n, const double *d, double *y, double *part_dy);
+};
+
+// The device vectors of a solve of up to `rows` unknowns.  cg_workspace_reserve leaves the workspace empty when it fails.
+struct CgWorkspace {
+    size_t rows = 0;
+    double *r = nullptr, *d = nullptr, *y = nullptr, *iA = nullptr, *part_a = nullptr, *part_b = nullptr;
+    void *scalars = nullptr;
+};
+hipError_t cg_workspace_reserve(CgWorkspace *ws, size_t rows);
+void cg_workspace_release(CgWorkspace *ws);
+
+// conjugated_gradient on the matrix `ops` describes.  ws: NULL = vectors of this call's own, gone on every path out; otherwise
+// a workspace reserved for n rows at least, which the call leaves as it found it.
+hipError_t conjugated_gradient_ops(hipStream_t stream, size_t n, const CgMatrixOps &ops, CgWorkspace *ws, const double *b, double *x,
+                                   double convergence_threshold, double divergence_threshold, size_t max_iter, int precond,
+                                   int *exit_reason, size_t *iterations, double *relative_residual);
+
+}  // namespace pa

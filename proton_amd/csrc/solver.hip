@@ -7,28 +7,13 @@
 
 #include <cstdint>
 
-namespace pa {
+#include "cg.hpp"
 
-constexpr int RB = 256;            // threads per block of the vector kernels
-constexpr int ROW_LANES = 16;      // lanes that share a row in the SpMV (HHO rows hold 20-130 entries)
+namespace pa {
 
 struct CgScalars {                 // device-resident scalars of the iteration
     double rho, dy, nr2, rho_new, alpha, beta;
 };
-
-__device__ inline double block_sum(double v, double *sh)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) sh[wave] = v;
-    __syncthreads();
-    double s = 0.0;
-#pragma unroll
-    for (int w = 0; w < RB / 64; ++w) s += sh[w];
-    __syncthreads();
-    return s;
-}
 
 // iA = 1 / diag(A)   (solver_cg.hpp:77-80)
 __global__ __launch_bounds__(RB) void cg_inv_diag_kernel(size_t n, const int64_t *rowptr, const int32_t *colind, const double *values,
@@ -124,31 +109,57 @@ __global__ __launch_bounds__(RB) void cg_reduce_kernel(int mode, size_t nparts, 
     }
 }
 
+hipError_t cg_workspace_reserve(CgWorkspace *ws, size_t rows)
+{
+    cg_workspace_release(ws);
+    const size_t nn = rows ? rows : 1;
+    const size_t gv = (nn + RB - 1) / RB, gs = (nn * ROW_LANES + RB - 1) / RB;
+    const size_t nparts = gs > gv ? gs : gv;
+    hipError_t e = hipMalloc((void **)&ws->r, nn * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&ws->d, nn * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&ws->y, nn * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&ws->iA, nn * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&ws->part_a, nparts * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&ws->part_b, nparts * 8);
+    if (e == hipSuccess) e = hipMalloc(&ws->scalars, sizeof(CgScalars));
+    if (e != hipSuccess) { cg_workspace_release(ws); return e; }
+    ws->rows = nn;
+    return hipSuccess;
+}
+
+void cg_workspace_release(CgWorkspace *ws)
+{
+    (void)hipFree(ws->r); (void)hipFree(ws->d); (void)hipFree(ws->y); (void)hipFree(ws->iA); (void)hipFree(ws->part_a);
+    (void)hipFree(ws->part_b); (void)hipFree(ws->scalars);
+    *ws = CgWorkspace();
+}
+
 // exit_reason: 0 converged, 1 diverged, 2 max_iter reached (cg_exit_reason, solver_cg.hpp:38-43)
-hipError_t conjugated_gradient(hipStream_t stream, size_t n, const int64_t *rowptr, const int32_t *colind, const double *values,
-                               const double *b, double *x, double convergence_threshold, double divergence_threshold,
-                               size_t max_iter, int precond, int *exit_reason, size_t *iterations, double *relative_residual)
+hipError_t conjugated_gradient_ops(hipStream_t stream, size_t n, const CgMatrixOps &ops, CgWorkspace *ws, const double *b, double *x,
+                                   double convergence_threshold, double divergence_threshold, size_t max_iter, int precond,
+                                   int *exit_reason, size_t *iterations, double *relative_residual)
 {
     hipError_t e = hipSuccess;
-    double *r = nullptr, *d = nullptr, *y = nullptr, *iA = nullptr, *pa_ = nullptr, *pb_ = nullptr;
-    CgScalars *sc = nullptr;
     const size_t nn = n ? n : 1;
     const unsigned gv = (unsigned)((nn + RB - 1) / RB);
     const unsigned gs = (unsigned)((nn * ROW_LANES + RB - 1) / RB);
-    const size_t nparts = gs > gv ? gs : gv;
-    auto cleanup = [&]() {
-        (void)hipFree(r); (void)hipFree(d); (void)hipFree(y); (void)hipFree(iA); (void)hipFree(pa_); (void)hipFree(pb_); (void)hipFree(sc);
-    };
+    CgWorkspace own;
+    if (ws != nullptr && ws->rows < nn) return hipErrorInvalidValue;
+    auto cleanup = [&]() { cg_workspace_release(&own); };
+    if (ws == nullptr) {
+        e = cg_workspace_reserve(&own, nn);
+        if (e != hipSuccess) return e;
+        ws = &own;
+    }
 #define CG_TRY(call) do { e = (call); if (e != hipSuccess) { cleanup(); return e; } } while (0)
-    CG_TRY(hipMalloc((void **)&r, nn * 8)); CG_TRY(hipMalloc((void **)&d, nn * 8)); CG_TRY(hipMalloc((void **)&y, nn * 8));
-    CG_TRY(hipMalloc((void **)&iA, nn * 8)); CG_TRY(hipMalloc((void **)&pa_, nparts * 8)); CG_TRY(hipMalloc((void **)&pb_, nparts * 8));
-    CG_TRY(hipMalloc((void **)&sc, sizeof(CgScalars)));
+    double *r = ws->r, *d = ws->d, *y = ws->y, *iA = ws->iA, *pa_ = ws->part_a, *pb_ = ws->part_b;
+    CgScalars *sc = (CgScalars *)ws->scalars;
     CgScalars h{};
     size_t iter = 0;
     int reason = 2;
     double rr = 0.0;
     if (n) {
-        hipLaunchKernelGGL(cg_inv_diag_kernel, dim3(gv), dim3(RB), 0, stream, n, rowptr, colind, values, iA);
+        ops.inv_diag(ops.user, stream, n, iA);
         hipLaunchKernelGGL(cg_init_kernel, dim3(gv), dim3(RB), 0, stream, n, b, iA, precond, x, r, d, pa_, pb_);      // :82-84
         hipLaunchKernelGGL(cg_reduce_kernel, dim3(1), dim3(RB), 0, stream, 0, (size_t)gv, pa_, pb_, sc);
         CG_TRY(hipMemcpyAsync(&h, sc, sizeof(h), hipMemcpyDeviceToHost, stream));
@@ -157,7 +168,7 @@ hipError_t conjugated_gradient(hipStream_t stream, size_t n, const int64_t *rowp
         if (!(nr0 > 0.0)) { reason = 0; }                   // b = 0: x = 0 is the solution (the reference would divide by zero)
         else
             for (;;) {
-                hipLaunchKernelGGL(cg_spmv_kernel, dim3(gs), dim3(RB), 0, stream, n, rowptr, colind, values, d, y, pa_);   // :99
+                ops.spmv(ops.user, stream, n, d, y, pa_);                                                                     // :99
                 hipLaunchKernelGGL(cg_reduce_kernel, dim3(1), dim3(RB), 0, stream, 1, (size_t)gs, pa_, (const double *)nullptr, sc);   // :101-102
                 hipLaunchKernelGGL(cg_update_kernel, dim3(gv), dim3(RB), 0, stream, n, sc, iA, precond, d, y, x, r, pa_, pb_);       // :103-105
                 hipLaunchKernelGGL(cg_reduce_kernel, dim3(1), dim3(RB), 0, stream, 2, (size_t)gv, pa_, pb_, sc);
@@ -179,6 +190,32 @@ hipError_t conjugated_gradient(hipStream_t stream, size_t n, const int64_t *rowp
     if (iterations) *iterations = iter;
     if (relative_residual) *relative_residual = rr;
     return hipSuccess;
+}
+
+// the plain CSR matrix pa_csr_from_triplets builds
+namespace {
+struct CsrMatrix { const int64_t *rowptr; const int32_t *colind; const double *values; };
+void csr_inv_diag(void *user, hipStream_t stream, size_t n, double *iA)
+{
+    const CsrMatrix *m = (const CsrMatrix *)user;
+    hipLaunchKernelGGL(cg_inv_diag_kernel, dim3((unsigned)((n + RB - 1) / RB)), dim3(RB), 0, stream, n, m->rowptr, m->colind, m->values, iA);
+}
+void csr_spmv(void *user, hipStream_t stream, size_t n, const double *d, double *y, double *part_dy)
+{
+    const CsrMatrix *m = (const CsrMatrix *)user;
+    hipLaunchKernelGGL(cg_spmv_kernel, dim3((unsigned)((n * ROW_LANES + RB - 1) / RB)), dim3(RB), 0, stream, n, m->rowptr, m->colind,
+                       m->values, d, y, part_dy);
+}
+}  // namespace
+
+hipError_t conjugated_gradient(hipStream_t stream, size_t n, const int64_t *rowptr, const int32_t *colind, const double *values,
+                               const double *b, double *x, double convergence_threshold, double divergence_threshold,
+                               size_t max_iter, int precond, int *exit_reason, size_t *iterations, double *relative_residual)
+{
+    CsrMatrix m{rowptr, colind, values};
+    const CgMatrixOps ops{&m, csr_inv_diag, csr_spmv};
+    return conjugated_gradient_ops(stream, n, ops, nullptr, b, x, convergence_threshold, divergence_threshold, max_iter, precond,
+                                   exit_reason, iterations, relative_residual);
 }
 
 // ---- the same solver on a ROW-PARTITIONED system (several GPUs: the face-only condensed system is assembled by rows,

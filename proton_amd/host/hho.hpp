@@ -1328,3 +1328,39 @@ auto make_obstacle_assembler(const Mesh &msh, const std::vector<bool> &in_A, hho
 {
     return obstacle_assembler<Mesh>(msh, in_A, hdi);
 }
+
+// The loop of run_hho_obstacle (obstacle.cpp:117-197) -- active set, obstacle_assembler, the solve of :170-175, expand_solution,
+// the stopping test of :193 -- in one call on the device (pa_obstacle_solve).  d_lc / d_rhs / d_g: the device arrays of
+// pa_local_ops_batch, pa_cell_rhs_batch (or NULL) and pa_dirichlet_data_batch (or NULL) for the mesh, as the batched branch of
+// the drivers holds them; gamma: the obstacle at the barycentres.  alpha (cells, then all faces) and beta come back on the host.
+// The reference's SparseLU is replaced by its own conjugate gradient on the symmetric positive definite block of the system
+// (cg_* of the parameters); a solve that does not converge ends the loop with info.converged = 0 and info.cg_exit_reason set.
+inline pa_obstacle_solve_params obstacle_solve_defaults()
+{
+    pa_obstacle_solve_params p;
+    p.c = 1.0; p.max_outer = 50; p.outer_tol = 1e-7;                  // obstacle.cpp:101, :119, :193
+    p.cg_convergence_threshold = 1e-13; p.cg_divergence_threshold = 100; p.cg_max_iter = 0; p.apply_preconditioner = 1;
+    return p;
+}
+
+template <typename Mesh, typename T>
+pa_obstacle_solve_info solve_obstacle(const Mesh &msh, hho_degree_info hdi, const double *d_lc, const double *d_rhs, const double *d_g,
+                                      const std::vector<T> &gamma, const pa_obstacle_solve_params &params, std::vector<T> &alpha,
+                                      std::vector<T> &beta)
+{
+    static_assert(std::is_same<T, double>::value, "the device path is double precision");
+    auto &dev = proton_amd::device::instance();
+    proton_amd::batch_cache<Mesh>::instance().ensure_mesh(msh);
+    const size_t nc = msh.cells.size(), fbs = hdi.face_degree() + 1, na = nc + fbs * msh.faces.size();
+    if (gamma.size() != nc) throw std::invalid_argument("solve_obstacle: gamma holds one value per cell");
+    proton_amd::device_buffer<double> d_gamma(nc), d_alpha(na), d_beta(nc);
+    proton_amd::device_buffer<uint8_t> d_in(nc);
+    d_gamma.upload(gamma.data(), nc);
+    pa_obstacle_solve_info info;
+    dev.check(pa_obstacle_solve(dev.ctx(), hdi.c_abi(), d_lc, d_rhs, d_g, d_gamma.get(), &params, d_alpha.get(), d_beta.get(), d_in.get(),
+                                &info, nullptr, nullptr), "pa_obstacle_solve");
+    alpha.resize(na); beta.resize(nc);
+    d_alpha.download(alpha.data(), na);
+    d_beta.download(beta.data(), nc);
+    return info;
+}
