@@ -77,6 +77,17 @@ __device__ __forceinline__ void load_cell_geom(const double *points, const uint3
     c.hT = h;
 }
 
+// The bilinear map of quadratures.hpp:331-340, sum_k N_k(xi, eta) p_k, taken from vertex 0: p_0 + sum_k N_k (p_k - p_0).  The
+// differences are exact for a cell far from the origin, so the point is off by half an ulp of the offset at the most; the
+// plain sum of four terms of the size of the offset loses an ulp or two (one ulp of 1000 is 2e-10 of a cell of side 1e-3:
+// the centre of such a cell came out one ulp off, 2.3e-10 in the right-hand side of cell degree 0).
+__device__ __forceinline__ void bilinear_point(const CellGeom &c, double xi, double eta, double &x, double &y)
+{
+    const double n1 = 0.25 * (1 + xi) * (1 - eta), n2 = 0.25 * (1 + xi) * (1 + eta), n3 = 0.25 * (1 - xi) * (1 + eta);
+    x = c.px[0] + __builtin_fma(n3, c.px[3] - c.px[0], __builtin_fma(n2, c.px[2] - c.px[0], n1 * (c.px[1] - c.px[0])));
+    y = c.py[0] + __builtin_fma(n3, c.py[3] - c.py[0], __builtin_fma(n2, c.py[2] - c.py[0], n1 * (c.py[1] - c.py[0])));
+}
+
 // q-th point of integrate(msh, cl, degree): tensor Gauss (quadratures.hpp:311-375) or fan (:377-402)
 template <int QUAD>
 __device__ __forceinline__ void cell_qp(const QuadTables *tab, const CellGeom &c, int degree, int q,
@@ -86,10 +97,7 @@ __device__ __forceinline__ void cell_qp(const QuadTables *tab, const CellGeom &c
         const int n = gauss_nodes(degree);
         const int i = q % n, j = q / n;
         const double xi = tab->gauss_x[n][i], eta = tab->gauss_x[n][j];
-        x = 0.25 * c.px[0] * (1 - xi) * (1 - eta) + 0.25 * c.px[1] * (1 + xi) * (1 - eta) +
-            0.25 * c.px[2] * (1 + xi) * (1 + eta) + 0.25 * c.px[3] * (1 - xi) * (1 + eta);
-        y = 0.25 * c.py[0] * (1 - xi) * (1 - eta) + 0.25 * c.py[1] * (1 + xi) * (1 - eta) +
-            0.25 * c.py[2] * (1 + xi) * (1 + eta) + 0.25 * c.py[3] * (1 - xi) * (1 + eta);
+        bilinear_point(c, xi, eta, x, y);
         const double j11 = 0.25 * ((c.px[1] - c.px[0]) * (1 - eta) + (c.px[2] - c.px[3]) * (1 + eta));
         const double j12 = 0.25 * ((c.py[1] - c.py[0]) * (1 - eta) + (c.py[2] - c.py[3]) * (1 + eta));
         const double j21 = 0.25 * ((c.px[3] - c.px[0]) * (1 - xi) + (c.px[2] - c.px[1]) * (1 + xi));
@@ -199,10 +207,8 @@ __global__ __launch_bounds__(256) void cell_rhs_kernel(const QuadTables *tab, co
             const double eta = tab->gauss_x[ng][j], wj = tab->gauss_w[ng][j];
             for (int i = 0; i < ng; ++i, ++q) {
                 const double xi = tab->gauss_x[ng][i];
-                const double x = 0.25 * c.px[0] * (1 - xi) * (1 - eta) + 0.25 * c.px[1] * (1 + xi) * (1 - eta) +
-                                 0.25 * c.px[2] * (1 + xi) * (1 + eta) + 0.25 * c.px[3] * (1 - xi) * (1 + eta);
-                const double y = 0.25 * c.py[0] * (1 - xi) * (1 - eta) + 0.25 * c.py[1] * (1 + xi) * (1 - eta) +
-                                 0.25 * c.py[2] * (1 + xi) * (1 + eta) + 0.25 * c.py[3] * (1 - xi) * (1 + eta);
+                double x, y;
+                bilinear_point(c, xi, eta, x, y);
                 const double j11 = 0.25 * ((c.px[1] - c.px[0]) * (1 - eta) + (c.px[2] - c.px[3]) * (1 + eta));
                 const double j12 = 0.25 * ((c.py[1] - c.py[0]) * (1 - eta) + (c.py[2] - c.py[3]) * (1 + eta));
                 const double j21 = 0.25 * ((c.px[3] - c.px[0]) * (1 - xi) + (c.px[2] - c.px[1]) * (1 + xi));

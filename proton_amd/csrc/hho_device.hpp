@@ -1454,8 +1454,12 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
                 const bool descending = (((int)sc[16]) >> f) & 1;                  // the face's first vertex has the higher point id
                 const double wnx = rw[0] * (pb_.y - pa_.y), wny = -rw[0] * (pb_.x - pa_.x);      // (w_q |F|/2) n: the edge length cancels
                 const double t = descending ? -r0[0] : r0[0];                      // bases.hpp:260-261
-                const double x = 0.5 * (1 - t) * pa_.x + 0.5 * (1 + t) * pb_.x;    // quadratures.hpp:420-428
-                const double y = 0.5 * (1 - t) * pa_.y + 0.5 * (1 + t) * pb_.y;
+                // the point of quadratures.hpp:420-428, 0.5 (1 - t) a + 0.5 (1 + t) b, taken from the endpoint a: b - a is exact for a
+                // cell far from the origin and the point cannot leave an axis-parallel face by an ulp of the offset (one ulp of
+                // 1000 is 2e-10 of a cell of side 1e-3 and showed as 8e-11 in the stabilization)
+                const double cb = 0.5 * (1 + t);
+                const double x = __builtin_fma(cb, pb_.x - pa_.x, pa_.x);
+                const double y = __builtin_fma(cb, pb_.y - pa_.y, pa_.y);
                 const double bx_ = (x - barx) * ih, by_ = (y - bary) * ih;
                 double pwx[RD + 1], pwy[RD + 1];
                 pwx[0] = 1.0; pwy[0] = 1.0;
@@ -1546,8 +1550,10 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
                     // the face runs from its LOWER-id endpoint (basic_geom.hpp:202-203, bases.hpp:260-261):
                     // its q-th point sits at -t_q in cell order when the ids are descending
                     const double t = descending ? -r0[r] : r0[r];
-                    x = 0.5 * (1 - t) * ax + 0.5 * (1 + t) * bx;   // quadratures.hpp:420-428
-                    y = 0.5 * (1 - t) * ay + 0.5 * (1 + t) * by;
+                    // quadratures.hpp:420-428 taken from the endpoint a (see the split S1 above)
+                    const double cb = 0.5 * (1 + t);
+                    x = __builtin_fma(cb, bx - ax, ax);
+                    y = __builtin_fma(cb, by - ay, ay);
                     w = 0.0;
                 }
                 const double bx_ = (x - barx) * ih, by_ = (y - bary) * ih;

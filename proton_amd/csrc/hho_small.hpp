@@ -205,8 +205,10 @@ __global__ __launch_bounds__(64, C::GENERAL_FANCY ? PA_SMALL_WAVES_GF : 2) void 
         const bool descending = ids[f] > ids[f + 1];
         const double t0 = tab->gauss_x[NFQ][q];
         const double t = descending ? -t0 : t0;
-        const double x = 0.5 * (1 - t) * px[f] + 0.5 * (1 + t) * px[f + 1];      // quadratures.hpp:420-428
-        const double y = 0.5 * (1 - t) * py[f] + 0.5 * (1 + t) * py[f + 1];
+        // quadratures.hpp:420-428 taken from the endpoint a: a + 0.5 (1 + t) (b - a), as in S1 of hho_device.hpp
+        const double cb = 0.5 * (1 + t);
+        const double x = __builtin_fma(cb, px[f + 1] - px[f], px[f]);
+        const double y = __builtin_fma(cb, py[f + 1] - py[f], py[f]);
         bx_ = (x - barx) * ih; by_ = (y - bary) * ih;
         double pwx[RD + 1], pwy[RD + 1];
         pwx[0] = 1.0; pwy[0] = 1.0;
