@@ -53,4 +53,23 @@ hipError_t conjugated_gradient_ops(hipStream_t stream, size_t n, const CgMatrixO
                                    double convergence_threshold, double divergence_threshold, size_t max_iter, int precond,
                                    int *exit_reason, size_t *iterations, double *relative_residual);
 
+// conjugated_gradient on a plain CSR matrix (solver_cg.hpp:63-144)
+hipError_t conjugated_gradient(hipStream_t stream, size_t n, const int64_t *rowptr, const int32_t *colind, const double *values,
+                               const double *b, double *x, double convergence_threshold, double divergence_threshold,
+                               size_t max_iter, int precond, int *exit_reason, size_t *iterations, double *relative_residual);
+
+// The transport of the row-partitioned solve (solver.hip): sums over the ranks, the two ends of the search direction's window
+// from the neighbouring ranks, and what each neighbour needs of this rank's rows.
+struct CgTransport {
+    void *user;
+    int (*allreduce_sum)(void *user, double *vals, int n);
+    int (*halo)(void *user, const double *send_lo, size_t n_send_lo, const double *send_hi, size_t n_send_hi, double *recv_lo,
+                size_t n_recv_lo, double *recv_hi, size_t n_recv_hi, void *stream);
+    int (*neighbour_counts)(void *user, int64_t need_lo, int64_t need_hi, int64_t *give_lo, int64_t *give_hi);
+};
+hipError_t conjugated_gradient_rows(hipStream_t stream, const CgTransport *tp, int64_t row_begin, int64_t row_end, const int64_t *rowptr,
+                                    const int32_t *colind, const double *values, const double *b, double *x,
+                                    double convergence_threshold, double divergence_threshold, size_t max_iter, int precond,
+                                    int *exit_reason, size_t *iterations, double *relative_residual, int *transport_status);
+
 }  // namespace pa

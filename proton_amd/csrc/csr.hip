@@ -13,6 +13,7 @@
 
 #include <cstdint>
 
+#include "csr.hpp"
 #include "device_tmp.hpp"
 #include "scan.hpp"
 

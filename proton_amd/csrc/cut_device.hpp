@@ -843,7 +843,7 @@ __global__ __launch_bounds__(64, DD ? 2 : 4) void cut_local_ops_kernel(CutArgs a
 // Two launches: one block per CUT cell (the list of cut cells, ~0.5 % of the mesh) copies its matrix and right-hand side;
 // one thread per right-hand-side entry of the whole mesh zeroes those of the cells outside the domain (coalesced stores).
 // (One block per cell of the WHOLE mesh, most of them with nothing or 80 bytes to write, took 51 us of config 3's 620.)
-__global__ __launch_bounds__(64) void cut_merge_cells_kernel(uint32_t ncut, const uint32_t *cut_cells, int msize2, int cbs,
+static __global__ __launch_bounds__(64) void cut_merge_cells_kernel(uint32_t ncut, const uint32_t *cut_cells, int msize2, int cbs,
                                                             const double *cut_lc, const double *cut_rhs, double *lc, double *rhs)
 {
     const size_t cc = blockIdx.x;
@@ -860,7 +860,7 @@ __global__ __launch_bounds__(64) void cut_merge_cells_kernel(uint32_t ncut, cons
 }
 
 // condensed mode: the cut cells' packed records [upper triangle of S | g] into the cell-major record array
-__global__ __launch_bounds__(64) void cut_merge_condensed_kernel(uint32_t ncut, const uint32_t *cut_cells, int ntri, int nf, const double *cut_Sp,
+static __global__ __launch_bounds__(64) void cut_merge_condensed_kernel(uint32_t ncut, const uint32_t *cut_cells, int ntri, int nf, const double *cut_Sp,
                                                                 const double *cut_g, double *cond)
 {
     const size_t cc = blockIdx.x;
@@ -870,7 +870,7 @@ __global__ __launch_bounds__(64) void cut_merge_condensed_kernel(uint32_t ncut, 
     for (int e = threadIdx.x; e < nf; e += 64) dst[ntri + e] = cut_g[cc * (size_t)nf + e];
 }
 
-__global__ __launch_bounds__(256) void cut_zero_rhs_kernel(size_t total, uint32_t cbs, const int8_t *cell_loc, int where, double *rhs)
+static __global__ __launch_bounds__(256) void cut_zero_rhs_kernel(size_t total, uint32_t cbs, const int8_t *cell_loc, int where, double *rhs)
 {
     const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= total) return;

@@ -20,7 +20,7 @@
 #include <thread>
 #include <vector>
 
-#include "hho_assembly.hpp"      // StructuredMesh closed forms
+#include "structured_mesh.hpp"   // StructuredMesh closed forms
 #include "hho_device.hpp"        // QuadTables
 
 namespace pa {

@@ -604,7 +604,7 @@ __global__ __launch_bounds__(64, 2) void cut_interface_kernel(CutInterfaceArgs a
 
 // lc of a cut cell (cuthho_square.cpp:1692-1705): data of make_hho_laplacian_interface plus
 // kappa_1 * stab_n scattered over the (cell-, faces-) unknowns and kappa_2 * stab_p over (cell+, faces+)
-__global__ __launch_bounds__(256) void cut_interface_lc_kernel(uint32_t ncut, int cbs, int nfd, double k1, double k2,
+static __global__ __launch_bounds__(256) void cut_interface_lc_kernel(uint32_t ncut, int cbs, int nfd, double k1, double k2,
                                                                const double *data, const double *stab_n, const double *stab_p,
                                                                double *lc)
 {
@@ -622,7 +622,7 @@ __global__ __launch_bounds__(256) void cut_interface_lc_kernel(uint32_t ncut, in
 }
 
 // lc = kappa(side of the cell) * data + stab for the uncut cells (cuthho_square.cpp:1670-1679)
-__global__ __launch_bounds__(256) void cut_interface_uncut_lc_kernel(size_t ncells, int mm, const int8_t *cell_loc, double k1, double k2,
+static __global__ __launch_bounds__(256) void cut_interface_uncut_lc_kernel(size_t ncells, int mm, const int8_t *cell_loc, double k1, double k2,
                                                                      const double *data, const double *stab, double *lc)
 {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -17,7 +17,7 @@
 namespace pa {
 
 // face tables of the slab: local face index = global id - face_base; point ids local to the slab
-__global__ void structured_faces_kernel(StructuredMesh m, uint32_t nfaces_local, uint32_t *face_pts, uint8_t *face_dir,
+static __global__ void structured_faces_kernel(StructuredMesh m, uint32_t nfaces_local, uint32_t *face_pts, uint8_t *face_dir,
                                         int32_t *face_compress, uint32_t ncells_local, uint32_t *cell_faces)
 {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void dirichlet_data_kernel(const QuadTables *t
 }
 
 // face quadrature points (x, y, w) in the reference's order, for caller-sampled boundary data
-__global__ void face_qpoints_kernel(const QuadTables *tab, const double *points, const uint32_t *face_pts,
+static __global__ void face_qpoints_kernel(const QuadTables *tab, const double *points, const uint32_t *face_pts,
                                     uint32_t nfaces, int nfq, double *xyw)
 {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -123,7 +123,7 @@ struct TripletArgs {
 };
 
 // assembler::assemble (hho.hpp:344-406): one block per cell, one thread per (i, j) slot.
-__global__ __launch_bounds__(256) void triplets_kernel(TripletArgs a)
+static __global__ __launch_bounds__(256) void triplets_kernel(TripletArgs a)
 {
     extern __shared__ double sh[];                    // dirichlet data (msize), then int32 idx (msize)
     const int msize = a.cbs + 4 * a.fbs;
@@ -175,7 +175,7 @@ struct TakeArgs {
     double *out;
 };
 
-__global__ __launch_bounds__(256) void take_local_data_kernel(TakeArgs a)
+static __global__ __launch_bounds__(256) void take_local_data_kernel(TakeArgs a)
 {
     const int msize = a.cbs + 4 * a.fbs;
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -274,7 +274,7 @@ __global__ __launch_bounds__(256) void face_project_kernel(const QuadTables *tab
 
 // diff.dot(lc * diff) per cell (the energy error of convergence_test.cpp / obstacle.cpp:202-213):
 // one wavefront per cell, lc read once with coalesced loads.
-__global__ __launch_bounds__(64) void energy_form_kernel(size_t n, int msize, const double *lc, const double *u,
+static __global__ __launch_bounds__(64) void energy_form_kernel(size_t n, int msize, const double *lc, const double *u,
                                                          const double *v, double *out)
 {
     __shared__ double d[64];
@@ -304,7 +304,7 @@ struct ObstacleArgs {
 };
 
 // obstacle_assembler::assemble (hho.hpp:609-695): one block per cell, one thread per (i, j) slot.
-__global__ __launch_bounds__(256) void obstacle_triplets_kernel(ObstacleArgs o)
+static __global__ __launch_bounds__(256) void obstacle_triplets_kernel(ObstacleArgs o)
 {
     extern __shared__ double sh[];                    // dirichlet data (msize), then int32 row (msize), col (msize)
     const TripletArgs &a = o.t;
@@ -365,7 +365,7 @@ struct ExpandArgs {
     double *alpha, *beta;
 };
 
-__global__ __launch_bounds__(256) void obstacle_expand_kernel(ExpandArgs a)
+static __global__ __launch_bounds__(256) void obstacle_expand_kernel(ExpandArgs a)
 {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint64_t ncd = a.ncells * a.cbs;

@@ -24,7 +24,7 @@ enum { FN_SAMPLED = 0, FN_SIN_SIN_RHS = 1, FN_SIN_SIN_SOL = 2, FN_OBSTACLE_RHS =
 // cells {p, p+1, p+Nx+2, p+Nx+1}, cell id j*Nx+i (basic_mesh.hpp:239-264; the sort at :289 is the
 // identity).  The context holds rows [row0, row1): point ids are local to the slab, which keeps
 // their relative order (all the face-basis orientation depends on).
-__global__ void mesh_generate_kernel(double *points, uint32_t *ptids, size_t Nx, size_t row0, size_t row1,
+static __global__ void mesh_generate_kernel(double *points, uint32_t *ptids, size_t Nx, size_t row0, size_t row1,
                                      double min_x, double hx, double min_y, double hy)
 {
     const size_t npr = Nx + 1;

@@ -1,5 +1,5 @@
 // obstacle_rhs.hpp -- the per-(cell, local row) right-hand-side sum of obstacle_assembler::assemble (hho.hpp:676-679, :686), in a
-// header of its own: hho_assembly.hpp (the triplet route, capi.hip) and obstacle_csr.hip (the direct CSR route) include it.
+// header of its own: hho_assembly.hpp (the triplet route, capi_obstacle.hip) and obstacle_csr.hip (the direct CSR route) include it.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -224,14 +224,7 @@ hipError_t conjugated_gradient(hipStream_t stream, size_t n, const int64_t *rowp
 // -- the columns this rank's rows read; the matrix is symmetric and banded by the mesh's row structure, so they belong to the
 // two neighbouring ranks -- whose two ends are refreshed from the neighbours once per iteration; the dot products are local
 // partial sums added over the ranks.  The transport is three callbacks (RCCL: pa_comm_cg_transport; host-staged gloo in the
-// tests); without one the call is the one-rank solver above with its recurrences in the same order.
-struct CgTransport {
-    void *user;
-    int (*allreduce_sum)(void *user, double *vals, int n);
-    int (*halo)(void *user, const double *send_lo, size_t n_send_lo, const double *send_hi, size_t n_send_hi, double *recv_lo,
-                size_t n_recv_lo, double *recv_hi, size_t n_recv_hi, void *stream);
-    int (*neighbour_counts)(void *user, int64_t need_lo, int64_t need_hi, int64_t *give_lo, int64_t *give_hi);
-};
+// tests: CgTransport, cg.hpp); without one the call is the one-rank solver above with its recurrences in the same order.
 
 // smallest and largest column index of the local rows (one block per 256 entries, atomics on two words)
 __global__ __launch_bounds__(RB) void cg_col_range_kernel(size_t nnz, const int32_t *colind, int *minmax)
