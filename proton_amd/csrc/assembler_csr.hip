@@ -42,62 +42,29 @@ __global__ __launch_bounds__(256) void asm_counts_kernel(uint32_t ncells, uint32
     if (t == nown) nfcell[nown] = 0;
 }
 
-hipError_t asm_build_tables(hipStream_t stream, const CondMesh &m, uint32_t ncells, uint32_t nown, const CondFaceLean *lean,
-                            uint32_t *nfc, uint32_t *cprefix, uint32_t *nfcell, uint32_t *fprefix)
+hipError_t asm_build_tables(hipStream_t stream, const FaceSystemView &v, const AsmTables &t)
 {
-    const uint32_t top = ncells > nown ? ncells : nown;
-    hipLaunchKernelGGL(asm_counts_kernel, dim3(blocks_for((size_t)top + 1)), dim3(256), 0, stream, ncells, nown, m.cell_faces,
-                       m.face_compress, lean, nfc, nfcell);
+    const uint32_t top = v.ncells > v.nown ? v.ncells : v.nown;
+    hipLaunchKernelGGL(asm_counts_kernel, dim3(blocks_for((size_t)top + 1)), dim3(256), 0, stream, v.ncells, v.nown, v.cell_faces,
+                       v.face_compress, v.lean, t.nfc.get(), t.nfcell.get());
     DeviceTmp tmp(stream);
     if (!tmp.ok(hipGetLastError()) ||
-        exclusive_scan_with_total<uint32_t>(stream, nfc, cprefix, (size_t)ncells + 1, tmp, nullptr) != hipSuccess ||
-        exclusive_scan_with_total<uint32_t>(stream, nfcell, fprefix, (size_t)nown + 1, tmp, nullptr) != hipSuccess)
+        exclusive_scan_with_total<uint32_t>(stream, t.nfc.get(), t.cprefix.get(), (size_t)v.ncells + 1, tmp, nullptr) != hipSuccess ||
+        exclusive_scan_with_total<uint32_t>(stream, t.nfcell.get(), t.fprefix.get(), (size_t)v.nown + 1, tmp, nullptr) != hipSuccess)
         return tmp.error();
     tmp.ok(hipStreamSynchronize(stream));
     return tmp.error();
 }
 
-// the non-Dirichlet faces of a cell in ascending compressed order: comp[s], local index lf[s], s < n
-struct CellFaces {
-    int32_t comp[4];
-    int lf[4];
-    int n;
-};
-__device__ __forceinline__ CellFaces cell_faces_sorted(const uint32_t *cell_faces, const int32_t *face_compress, uint32_t c)
-{
-    const uint4 f = *reinterpret_cast<const uint4 *>(cell_faces + 4 * (size_t)c);
-    const int32_t cc[4] = {face_compress[f.x], face_compress[f.y], face_compress[f.z], face_compress[f.w]};
-    CellFaces r;
-    r.n = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { r.comp[q] = 0x7fffffff; r.lf[q] = 0; }
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-        if (cc[q] >= 0) {
-            // insertion into the sorted prefix (at most 4 entries)
-            int p = r.n;
-#pragma unroll
-            for (int s = 2; s >= 0; --s)
-                if (s < r.n && r.comp[s] > cc[q]) { r.comp[s + 1] = r.comp[s]; r.lf[s + 1] = r.lf[s]; p = s; }
-            r.comp[p] = cc[q]; r.lf[p] = q;
-            ++r.n;
-        }
-    return r;
-}
-
+// the sizes every kernel of one degree pair takes; the closed forms of the row starts are face_system.hpp's
 struct AsmDims {
     int cbs, fbs, ms;
     uint32_t ncells, nown;
-    uint64_t cell_nnz;        // entries of all cell rows = cbs (ncells cbs + cprefix[ncells] fbs)
+    uint64_t cell_nnz;        // entries of all cell rows
 };
-
-__device__ __forceinline__ uint64_t cell_block_start(const AsmDims &d, uint32_t c, uint32_t cpre)
+static AsmDims asm_dims(const FaceSystemView &v, int cbs, int fbs)
 {
-    return (uint64_t)d.cbs * ((uint64_t)c * d.cbs + (uint64_t)cpre * d.fbs);
-}
-__device__ __forceinline__ uint64_t face_block_start(const AsmDims &d, uint32_t fcpre, uint32_t colpre)
-{
-    return d.cell_nnz + (uint64_t)d.fbs * ((uint64_t)fcpre * d.cbs + (uint64_t)colpre * d.fbs);
+    return {cbs, fbs, cbs + 4 * fbs, v.ncells, v.nown, asm_sizes(v, cbs, fbs).cell_nnz};
 }
 
 // ---- pattern: row pointers and column indices ------------------------------------------------------------------------
@@ -110,7 +77,7 @@ __global__ __launch_bounds__(256) void asm_pattern_cells_kernel(AsmDims d, const
     if (c >= d.ncells) return;
     const CellFaces cf = cell_faces_sorted(cell_faces, face_compress, c);
     const int R = d.cbs + cf.n * d.fbs;
-    const uint64_t start = cell_block_start(d, c, cprefix[c]) + (uint64_t)i * R;
+    const uint64_t start = cell_block_start(d.cbs, d.fbs, c, cprefix[c]) + (uint64_t)i * R;
     rowptr[(size_t)c * d.cbs + i] = (int64_t)start;
     if (colind == nullptr) return;
     for (int j = 0; j < d.cbs; ++j) colind[start + j] = (int32_t)((uint64_t)c * d.cbs + j);
@@ -127,11 +94,11 @@ __global__ __launch_bounds__(256) void asm_pattern_faces_kernel(AsmDims d, const
     const int k = (int)(t % (uint32_t)d.fbs);
     int64_t *rp = rowptr + (size_t)d.cbs * d.ncells;
     if (q > d.nown || (q == d.nown && k > 0)) return;
-    if (q == d.nown) { rp[(size_t)d.nown * d.fbs] = (int64_t)face_block_start(d, fprefix[d.nown], colprefix[d.nown]); return; }
+    if (q == d.nown) { rp[(size_t)d.nown * d.fbs] = (int64_t)face_block_start(d.cell_nnz, d.cbs, d.fbs, fprefix[d.nown], colprefix[d.nown]); return; }
     const CondFace &r = faces[q];
     const int ncell = (r.cA >= 0) + (r.cB >= 0);
     const int R = ncell * d.cbs + r.ncol * d.fbs;
-    const uint64_t start = face_block_start(d, fprefix[q], colprefix[q]) + (uint64_t)k * R;
+    const uint64_t start = face_block_start(d.cell_nnz, d.cbs, d.fbs, fprefix[q], colprefix[q]) + (uint64_t)k * R;
     rp[(size_t)q * d.fbs + k] = (int64_t)start;
     if (colind == nullptr) return;
     int o = 0;
@@ -142,15 +109,13 @@ __global__ __launch_bounds__(256) void asm_pattern_faces_kernel(AsmDims d, const
             colind[start + o + s * d.fbs + kp] = (int32_t)((uint64_t)d.cbs * d.ncells + (uint64_t)r.colcomp[s] * d.fbs + kp);
 }
 
-hipError_t asm_pattern(hipStream_t stream, const CondMesh &m, int cbs, int fbs, uint32_t ncells, uint32_t nown, uint64_t cell_nnz,
-                       const CondFace *faces, const uint32_t *colprefix, const uint32_t *cprefix, const uint32_t *fprefix,
-                       int64_t *rowptr, int32_t *colind)
+hipError_t asm_pattern(hipStream_t stream, const FaceSystemView &v, int cbs, int fbs, int64_t *rowptr, int32_t *colind)
 {
-    const AsmDims d = {cbs, fbs, cbs + 4 * fbs, ncells, nown, cell_nnz};
-    hipLaunchKernelGGL(asm_pattern_cells_kernel, dim3(blocks_for((size_t)ncells * cbs)), dim3(256), 0, stream, d, m.cell_faces,
-                       m.face_compress, cprefix, rowptr, colind);
-    hipLaunchKernelGGL(asm_pattern_faces_kernel, dim3(blocks_for(((size_t)nown + 1) * fbs)), dim3(256), 0, stream, d, faces, colprefix,
-                       fprefix, rowptr, colind);
+    const AsmDims d = asm_dims(v, cbs, fbs);
+    hipLaunchKernelGGL(asm_pattern_cells_kernel, dim3(blocks_for((size_t)v.ncells * cbs)), dim3(256), 0, stream, d, v.cell_faces,
+                       v.face_compress, v.cprefix, rowptr, colind);
+    hipLaunchKernelGGL(asm_pattern_faces_kernel, dim3(blocks_for(((size_t)v.nown + 1) * fbs)), dim3(256), 0, stream, d, v.faces, v.colprefix,
+                       v.fprefix, rowptr, colind);
     return hipGetLastError();
 }
 
@@ -186,7 +151,7 @@ __global__ __launch_bounds__(256) void asm_fill_cells_kernel(AsmDims d, uint32_t
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const uint32_t R = (uint32_t)(CBS + cf[u].n * FBS);
-        const uint64_t start = cell_block_start(d, cell[u], cpre[u]);
+        const uint64_t start = cell_block_start(d.cbs, d.fbs, cell[u], cpre[u]);
         const double *A = lc + (size_t)cell[u] * (MS * MS);
 #pragma unroll
         for (int p = 0; p < PASSES; ++p) {
@@ -220,44 +185,12 @@ __global__ __launch_bounds__(256) void asm_fill_cells_kernel(AsmDims d, uint32_t
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (on[u] && lane < (uint32_t)CBS) {
-                const double *A = lc + (size_t)cell[u] * (MS * MS);
                 double s = rhs != nullptr ? rhs[(size_t)cell[u] * CBS + lane] : 0.0;
-                if (cf[u].n < 4) {
-                    const uint4 f = *reinterpret_cast<const uint4 *>(cell_faces + 4 * (size_t)cell[u]);
-                    const uint32_t fl[4] = {f.x, f.y, f.z, f.w};
-#pragma unroll
-                    for (int lf = 0; lf < 4; ++lf)
-                        if (face_compress[fl[lf]] < 0)
-                            for (int kp = 0; kp < FBS; ++kp) {
-                                const double dd = g != nullptr ? g[(size_t)fl[lf] * FBS + kp] : 0.0;
-                                s -= A[(size_t)(CBS + lf * FBS + kp) * MS + lane] * dd;
-                            }
-                }
+                if (cf[u].n < 4) s = dirichlet_rhs_contrib<CBS, FBS>(cell_faces, face_compress, lc, g, cell[u], lane, s);
                 RHS[(size_t)cell[u] * CBS + lane] = s;
             }
         }
     }
-}
-
-// contribution of local cell c to the right-hand side of its local row `row` (a face row): minus the Dirichlet columns
-// times the boundary data, accumulated from zero in local column order (hho.hpp:401)
-template <int CBS, int FBS>
-__device__ __forceinline__ double asm_face_rhs_contrib(const uint32_t *cell_faces, const int32_t *face_compress, const double *lc,
-                                                       const double *g, int32_t c, int row)
-{
-    constexpr int MS = CBS + 4 * FBS;
-    const double *A = lc + (size_t)c * (MS * MS);
-    const uint4 f = *reinterpret_cast<const uint4 *>(cell_faces + 4 * (size_t)c);
-    const uint32_t fl[4] = {f.x, f.y, f.z, f.w};
-    double s = 0.0;
-#pragma unroll
-    for (int lf = 0; lf < 4; ++lf)
-        if (face_compress[fl[lf]] < 0)
-            for (int kp = 0; kp < FBS; ++kp) {
-                const double dd = g != nullptr ? g[(size_t)fl[lf] * FBS + kp] : 0.0;
-                s -= A[(size_t)(CBS + lf * FBS + kp) * MS + row] * dd;
-            }
-    return s;
 }
 
 // Face rows: one wavefront per U faces at a time, lane e of a pass = entry e of the face's block of fbs rows.
@@ -289,11 +222,11 @@ __global__ __launch_bounds__(256) void asm_fill_faces_kernel(AsmDims d, uint32_t
     bool ok[U][PASSES], two[U][PASSES];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-        const uint32_t ncol = (uint32_t)(r[u].packed >> 46) & 7u, rows = (uint32_t)(r[u].packed >> 42) & 15u;
+        const uint32_t ncol = lean_ncol(r[u].packed), rows = lean_rows(r[u].packed);
         const bool hasA_ = r[u].cA >= 0, hasB_ = r[u].cB >= 0;
         const uint32_t ncell = (uint32_t)hasA_ + (uint32_t)hasB_;
         const uint32_t R = ncell * CBS + ncol * FBS;
-        const uint64_t start = face_block_start(d, fpre[u], cpre[u]);
+        const uint64_t start = face_block_start(d.cell_nnz, d.cbs, d.fbs, fpre[u], cpre[u]);
         const double *LA = lc + (size_t)(hasA_ ? r[u].cA : 0) * (MS * MS), *LB = lc + (size_t)(hasB_ ? r[u].cB : 0) * (MS * MS);
 #pragma unroll
         for (int p = 0; p < PASSES; ++p) {
@@ -301,7 +234,7 @@ __global__ __launch_bounds__(256) void asm_fill_faces_kernel(AsmDims d, uint32_t
             ok[u][p] = on[u] && e < (uint32_t)FBS * R;
             const uint32_t ee = ok[u][p] ? e : 0u;
             const uint32_t k = ee / R, jj = ee - k * R;
-            const uint32_t rowA = CBS + (rows & 3u) * FBS + k, rowB = CBS + ((rows >> 2) & 3u) * FBS + k;
+            const uint32_t rowA = CBS + frows_A(rows) * FBS + k, rowB = CBS + frows_B(rows) * FBS + k;
             const double *pA = LA, *pB = LB;
             bool useA = false, useB = false;
             if (jj < ncell * CBS) {
@@ -313,10 +246,10 @@ __global__ __launch_bounds__(256) void asm_fill_faces_kernel(AsmDims d, uint32_t
                 pB = LB + (size_t)j * MS + rowB;
             } else {
                 const uint32_t s = (jj - ncell * CBS) / (uint32_t)FBS, kp = (jj - ncell * CBS) % (uint32_t)FBS;
-                const uint32_t code = (uint32_t)(r[u].packed >> (6 * s)) & 63u;
-                useA = (code & 4u) != 0; useB = (code & 32u) != 0;
-                pA = LA + (size_t)(CBS + (code & 3u) * FBS + kp) * MS + rowA;
-                pB = LB + (size_t)(CBS + ((code >> 3) & 3u) * FBS + kp) * MS + rowB;
+                const uint32_t code = lean_code(r[u].packed, s);
+                useA = (code & FCODE_HAS_A) != 0; useB = (code & FCODE_HAS_B) != 0;
+                pA = LA + (size_t)(CBS + fcode_lf_A(code) * FBS + kp) * MS + rowA;
+                pB = LB + (size_t)(CBS + fcode_lf_B(code) * FBS + kp) * MS + rowB;
             }
             useA = useA && ok[u][p]; useB = useB && ok[u][p];
             pa_[u][p] = useA ? pA : (useB ? pB : lc);
@@ -339,14 +272,14 @@ __global__ __launch_bounds__(256) void asm_fill_faces_kernel(AsmDims d, uint32_t
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (on[u] && lane < (uint32_t)FBS) {
-                const uint32_t rows = (uint32_t)(r[u].packed >> 42) & 15u;
-                const bool dcols = (r[u].packed >> 49) & 1u;
-                const int rowA = CBS + (int)(rows & 3u) * FBS + (int)lane, rowB = CBS + (int)((rows >> 2) & 3u) * FBS + (int)lane;
+                const uint32_t rows = lean_rows(r[u].packed);
+                const bool dcols = lean_dirichlet(r[u].packed);
+                const int rowA = CBS + (int)frows_A(rows) * FBS + (int)lane, rowB = CBS + (int)frows_B(rows) * FBS + (int)lane;
                 double b = 0.0;
                 bool have = false;
-                if (r[u].cA >= 0) { b = dcols ? asm_face_rhs_contrib<CBS, FBS>(cell_faces, face_compress, lc, g, r[u].cA, rowA) : 0.0; have = true; }
+                if (r[u].cA >= 0) { b = dcols ? dirichlet_rhs_contrib<CBS, FBS>(cell_faces, face_compress, lc, g, (uint32_t)r[u].cA, rowA, 0.0) : 0.0; have = true; }
                 if (r[u].cB >= 0) {
-                    const double w = dcols ? asm_face_rhs_contrib<CBS, FBS>(cell_faces, face_compress, lc, g, r[u].cB, rowB) : 0.0;
+                    const double w = dcols ? dirichlet_rhs_contrib<CBS, FBS>(cell_faces, face_compress, lc, g, (uint32_t)r[u].cB, rowB, 0.0) : 0.0;
                     b = have ? b + w : w;
                 }
                 RHS[(size_t)d.cbs * d.ncells + (size_t)(q_begin + wave * U + u) * FBS + lane] = b;
@@ -359,44 +292,25 @@ __global__ __launch_bounds__(256) void asm_fill_faces_kernel(AsmDims d, uint32_t
 #ifndef PA_ASM_UNROLL
 #define PA_ASM_UNROLL 2
 #endif
-// lc of the cells of one piece of the numeric phase (see asm_fill_t).  One piece: the pieces were meant to keep a piece's lc in
-// the Infinity Cache between its cell rows and its face rows (lc fetched from HBM once instead of 1.7 times) -- measured SLOWER at
-// 1024 x 1024: k = 2 3.35 ms in one piece, 3.68 in pieces of 96 MB, 4.87 in pieces of 32 MB (k = 3: 6.3 / 7.4 / 10.3): the tails of
-// the extra launches cost more than the second fetch
-#ifndef PA_ASM_PIECE_BYTES
-#define PA_ASM_PIECE_BYTES ((size_t)1 << 40)
-#endif
 template <int CBS, int FBS>
-static hipError_t asm_fill_t(hipStream_t stream, const CondMesh &m, const AsmDims &d, const CondFaceLean *lean, const uint32_t *colprefix,
-                             const uint32_t *cprefix, const uint32_t *fprefix, const double *lc, const double *rhs, const double *g,
-                             double *values, double *RHS)
+static hipError_t asm_fill_t(hipStream_t stream, const FaceSystemView &v, const AsmDims &d, const double *lc, const double *rhs,
+                             const double *g, double *values, double *RHS)
 {
     constexpr int U = PA_ASM_UNROLL;
-    // (in pieces of about PA_ASM_PIECE_BYTES of lc -- the cell rows of a piece, then the face rows of the same fraction of the
-    // compressed faces; one piece by default, see above)
-    constexpr size_t lc_bytes = (size_t)(CBS + 4 * FBS) * (CBS + 4 * FBS) * 8;
-    const size_t piece_cells = PA_ASM_PIECE_BYTES / lc_bytes ? PA_ASM_PIECE_BYTES / lc_bytes : 1;
-    const uint32_t npieces = (uint32_t)((d.ncells + piece_cells - 1) / piece_cells);
-    for (uint32_t p = 0; p < npieces; ++p) {
-        const uint32_t c0 = (uint32_t)((uint64_t)d.ncells * p / npieces), c1 = (uint32_t)((uint64_t)d.ncells * (p + 1) / npieces);
-        const uint32_t q0 = (uint32_t)((uint64_t)d.nown * p / npieces), q1 = (uint32_t)((uint64_t)d.nown * (p + 1) / npieces);
-        if (c1 > c0)
-            hipLaunchKernelGGL((asm_fill_cells_kernel<CBS, FBS, U>), dim3(((size_t)(c1 - c0) + 4 * U - 1) / (4 * U)), dim3(256), 0, stream, d, c0, c1,
-                               m.cell_faces, m.face_compress, cprefix, lc, rhs, g, values, RHS);
-        if (q1 > q0)
-            hipLaunchKernelGGL((asm_fill_faces_kernel<CBS, FBS, U>), dim3(((size_t)(q1 - q0) + 4 * U - 1) / (4 * U)), dim3(256), 0, stream, d, q0, q1,
-                               m.cell_faces, m.face_compress, lean, colprefix, fprefix, lc, g, values, RHS);
-    }
+    hipLaunchKernelGGL((asm_fill_cells_kernel<CBS, FBS, U>), dim3(((size_t)d.ncells + 4 * U - 1) / (4 * U)), dim3(256), 0, stream, d, 0u, d.ncells,
+                       v.cell_faces, v.face_compress, v.cprefix, lc, rhs, g, values, RHS);
+    if (d.nown > 0)
+        hipLaunchKernelGGL((asm_fill_faces_kernel<CBS, FBS, U>), dim3(((size_t)d.nown + 4 * U - 1) / (4 * U)), dim3(256), 0, stream, d, 0u, d.nown,
+                           v.cell_faces, v.face_compress, v.lean, v.colprefix, v.fprefix, lc, g, values, RHS);
     return hipGetLastError();
 }
 
-hipError_t asm_fill(hipStream_t stream, const CondMesh &m, int cbs, int fbs, uint32_t ncells, uint32_t nown, uint64_t cell_nnz,
-                    const CondFaceLean *lean, const uint32_t *colprefix, const uint32_t *cprefix, const uint32_t *fprefix,
-                    const double *lc, const double *rhs, const double *g, double *values, double *RHS)
+hipError_t asm_fill(hipStream_t stream, const FaceSystemView &v, int cbs, int fbs, const double *lc, const double *rhs, const double *g,
+                    double *values, double *RHS)
 {
-    if (ncells == 0) return hipSuccess;
-    const AsmDims d = {cbs, fbs, cbs + 4 * fbs, ncells, nown, cell_nnz};
-#define PA_ASM_CASE(C, F) if (cbs == C && fbs == F) return asm_fill_t<C, F>(stream, m, d, lean, colprefix, cprefix, fprefix, lc, rhs, g, values, RHS)
+    if (v.ncells == 0) return hipSuccess;
+    const AsmDims d = asm_dims(v, cbs, fbs);
+#define PA_ASM_CASE(C, F) if (cbs == C && fbs == F) return asm_fill_t<C, F>(stream, v, d, lc, rhs, g, values, RHS)
     PA_ASM_CASE(1, 1); PA_ASM_CASE(3, 1); PA_ASM_CASE(1, 2); PA_ASM_CASE(3, 2); PA_ASM_CASE(6, 2); PA_ASM_CASE(3, 3); PA_ASM_CASE(6, 3);
     PA_ASM_CASE(10, 3); PA_ASM_CASE(6, 4); PA_ASM_CASE(10, 4); PA_ASM_CASE(15, 4);
 #undef PA_ASM_CASE
@@ -443,12 +357,11 @@ __global__ __launch_bounds__(256) void asm_scatter_table_kernel(uint32_t ncells,
     out[c] = rec;
 }
 
-hipError_t asm_build_scatter_table(hipStream_t stream, const CondMesh &m, uint32_t ncells, const CondFace *faces, const uint32_t *colprefix,
-                                   const uint32_t *cprefix, const uint32_t *fprefix, AsmCellRec *out)
+hipError_t asm_build_scatter_table(hipStream_t stream, const FaceSystemView &v, AsmCellRec *out)
 {
-    if (ncells == 0) return hipSuccess;
-    hipLaunchKernelGGL(asm_scatter_table_kernel, dim3(blocks_for(ncells)), dim3(256), 0, stream, ncells, m.cell_faces, m.face_compress,
-                       cprefix, faces, colprefix, fprefix, out);
+    if (v.ncells == 0) return hipSuccess;
+    hipLaunchKernelGGL(asm_scatter_table_kernel, dim3(blocks_for(v.ncells)), dim3(256), 0, stream, v.ncells, v.cell_faces, v.face_compress,
+                       v.cprefix, v.faces, v.colprefix, v.fprefix, out);
     const hipError_t e = hipGetLastError();
     return e != hipSuccess ? e : hipStreamSynchronize(stream);
 }
@@ -473,16 +386,14 @@ __global__ __launch_bounds__(256) void asm_zero_accumulated_kernel(AsmDims d, co
     const uint32_t R = ncell * d.cbs + (uint32_t)r.ncol * d.fbs;
     for (int s = 0; s < (int)r.ncol; ++s)
         if (r.colcomp[s] == (int32_t)q)
-            values[face_block_start(d, fprefix[q], colprefix[q]) + (uint64_t)k * R + ncell * d.cbs + (uint32_t)s * d.fbs + kp] = 0.0;
+            values[face_block_start(d.cell_nnz, d.cbs, d.fbs, fprefix[q], colprefix[q]) + (uint64_t)k * R + ncell * d.cbs + (uint32_t)s * d.fbs + kp] = 0.0;
 }
 
-hipError_t asm_zero_accumulated(hipStream_t stream, int cbs, int fbs, uint32_t ncells, uint32_t nown, uint64_t cell_nnz,
-                                const CondFace *faces, const uint32_t *colprefix, const uint32_t *fprefix, double *values, double *RHS)
+hipError_t asm_zero_accumulated(hipStream_t stream, const FaceSystemView &v, int cbs, int fbs, double *values, double *RHS)
 {
-    if (nown == 0) return hipSuccess;
-    const AsmDims d = {cbs, fbs, cbs + 4 * fbs, ncells, nown, cell_nnz};
-    hipLaunchKernelGGL(asm_zero_accumulated_kernel, dim3(blocks_for((size_t)nown * fbs * (fbs + 1))), dim3(256), 0, stream, d, faces,
-                       colprefix, fprefix, values, RHS);
+    if (v.nown == 0) return hipSuccess;
+    hipLaunchKernelGGL(asm_zero_accumulated_kernel, dim3(blocks_for((size_t)v.nown * fbs * (fbs + 1))), dim3(256), 0, stream,
+                       asm_dims(v, cbs, fbs), v.faces, v.colprefix, v.fprefix, values, RHS);
     return hipGetLastError();
 }
 

@@ -163,6 +163,14 @@ int pa_context_destroy(pa_context *ctx)
     return PA_OK;
 }
 
+hipError_t join_side_stream(pa_context *ctx)
+{
+    if (!ctx->side_pending) return hipSuccess;
+    const hipError_t e = hipStreamWaitEvent(ctx->stream, ctx->ev_side, 0);
+    if (e == hipSuccess) ctx->side_pending = false;
+    return e;
+}
+
 int pa_context_synchronize(pa_context *ctx)
 {
     if (!ctx) return PA_ERR_INVALID_ARG;
@@ -197,10 +205,7 @@ int pa_context_set_cut_overlap(pa_context *ctx, int on)
         PA_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_main, hipEventDisableTiming));
         PA_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_side, hipEventDisableTiming));
     }
-    if (!on && ctx->side_pending) {                      // join what is still out on the side stream
-        PA_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_side, 0));
-        ctx->side_pending = false;
-    }
+    if (!on) PA_HIP(ctx, join_side_stream(ctx));      // join what is still out on the side stream
     ctx->cut_overlap = on != 0;
     return PA_OK;
 }

@@ -15,7 +15,7 @@ int pa_triplets_batch(pa_context *ctx, pa_degree_info di, size_t first, size_t n
 {
     if (!ctx || !d_lc || !d_rows || !d_cols || !d_vals || !d_rhs_rows || !d_rhs_vals) return PA_ERR_INVALID_ARG;
     (void)hipSetDevice(ctx->device);
-    if (di.cell_deg < 0 || di.face_deg < 0 || di.face_deg > 3 || di.cell_deg > 4) return PA_ERR_INVALID_DEGREE;
+    if (!degree_ok(di)) return PA_ERR_INVALID_DEGREE;
     if (!ctx->faces.cell_faces.get()) return PA_ERR_NO_MESH;
     if (first > ctx->mesh.ncells || n > ctx->mesh.ncells - first) return PA_ERR_INVALID_ARG;
     pa_assembler_info info;
@@ -42,7 +42,7 @@ static int take_local(pa_context *ctx, pa_degree_info di, size_t first, size_t n
 {
     if (!ctx || !d_solution || !d_out) return PA_ERR_INVALID_ARG;
     (void)hipSetDevice(ctx->device);
-    if (di.cell_deg < 0 || di.face_deg < 0 || di.face_deg > 3 || di.cell_deg > 4) return PA_ERR_INVALID_DEGREE;
+    if (!degree_ok(di)) return PA_ERR_INVALID_DEGREE;
     if (!ctx->faces.cell_faces.get()) return PA_ERR_NO_MESH;
     if (first > ctx->mesh.ncells || n > ctx->mesh.ncells - first) return PA_ERR_INVALID_ARG;
     if (n == 0) return PA_OK;
@@ -74,7 +74,7 @@ int pa_energy_form_batch(pa_context *ctx, pa_degree_info di, size_t n, const dou
 {
     if (!ctx || !d_lc || !d_u || !d_out) return PA_ERR_INVALID_ARG;
     (void)hipSetDevice(ctx->device);
-    if (di.cell_deg < 0 || di.cell_deg > 4 || di.face_deg < 0 || di.face_deg > 3) return PA_ERR_INVALID_DEGREE;
+    if (!degree_ok(di)) return PA_ERR_INVALID_DEGREE;
     if (n == 0) return PA_OK;
     const int msize = pa::P2(di.cell_deg) + 4 * (di.face_deg + 1);
     const size_t resident = (size_t)ctx->num_cus * 32;
@@ -85,15 +85,27 @@ int pa_energy_form_batch(pa_context *ctx, pa_degree_info di, size_t n, const dou
 }
 
 // ---- condensed (face-only) system -----------------------------------------------------------------
-static bool cond_degree_ok(pa_degree_info di) { return di.cell_deg >= 0 && di.cell_deg <= 4 && di.face_deg >= 0 && di.face_deg <= 3; }
-
-pa::CondMesh cond_mesh(const pa_context *ctx)
+static pa::CondMesh cond_mesh(const pa_context *ctx)
 {
     pa::CondMesh m;
     m.cell_faces = ctx->faces.cell_faces.get(); m.face_compress = ctx->faces.face_compress.get(); m.adj = ctx->cond.adj.get();
     m.sm = ctx->faces.sm; m.structured = ctx->faces.structured;
     return m;
 }
+
+// the context's tables as the assemblers take them; `asmb`: the group under construction inside asm_prepare
+static pa::FaceSystemView face_system_view(const pa_context *ctx, const pa::CondTables &cond, const pa::AsmTables &asmb)
+{
+    pa::FaceSystemView v;
+    v.cell_faces = ctx->faces.cell_faces.get(); v.face_compress = ctx->faces.face_compress.get();
+    v.faces = cond.cfaces.get(); v.lean = cond.cfaces_lean.get(); v.colprefix = cond.prefix.get();
+    v.cprefix = asmb.cprefix.get(); v.fprefix = asmb.fprefix.get();
+    v.ncells = (uint32_t)ctx->mesh.ncells; v.nown = cond.nown;
+    v.total_cols = cond.total_cols; v.cell_faces_total = asmb.cell_faces_total; v.face_cells_total = asmb.face_cells_total;
+    return v;
+}
+
+pa::FaceSystemView face_system_view(const pa_context *ctx) { return face_system_view(ctx, ctx->cond, ctx->asmb); }
 
 // first compressed id at or after global face `gid` of the generator mesh (the compress table is monotone)
 static int32_t sm_first_compress_from(const pa::StructuredMesh &sm, uint32_t gid)
@@ -129,10 +141,8 @@ int cond_prepare(pa_context *ctx)
     PA_HIP(ctx, c.cfaces_lean.alloc((size_t)nown + 1));
     PA_HIP(ctx, c.ncols.alloc((size_t)nown + 1));
     PA_HIP(ctx, c.prefix.alloc((size_t)nown + 1));
-    pa::CondMesh m = cond_mesh(ctx);
-    m.adj = c.adj.get();
-    PA_HIP(ctx, pa::cond_build_tables(ctx->stream, m, (uint32_t)ctx->faces.nfaces_local, (uint32_t)ctx->mesh.ncells, owned_range, p0, nown,
-                                      c.adj.get(), c.cfaces.get(), c.cfaces_lean.get(), c.ncols.get(), c.prefix.get()));
+    PA_HIP(ctx, pa::cond_build_tables(ctx->stream, cond_mesh(ctx), (uint32_t)ctx->faces.nfaces_local, (uint32_t)ctx->mesh.ncells, owned_range, p0,
+                                      nown, c));
     uint32_t total = 0;
     PA_HIP(ctx, hipMemcpy(&total, c.prefix.get() + nown, sizeof(uint32_t), hipMemcpyDeviceToHost));
     c.nown = nown; c.owned_range = owned_range; c.p0 = p0; c.total_cols = total;
@@ -159,7 +169,7 @@ static void cond_partition_fill(const pa::StructuredMesh &sm, uint64_t fbs, pa_c
 
 int pa_condensed_partition_info(size_t Nx, size_t Ny, size_t row_begin, size_t row_end, pa_degree_info di, pa_condensed_info *out)
 {
-    if (!out || !cond_degree_ok(di) || Nx == 0 || Ny == 0 || row_begin >= row_end || row_end > Ny) return PA_ERR_INVALID_ARG;
+    if (!out || !degree_ok(di) || Nx == 0 || Ny == 0 || row_begin >= row_end || row_end > Ny) return PA_ERR_INVALID_ARG;
     if ((Nx + 1) * (Ny + 1) >= ((size_t)1 << 32)) return PA_ERR_INVALID_ARG;
     const pa::StructuredMesh sm = {(uint32_t)Nx, (uint32_t)Ny, (uint32_t)row_begin, (uint32_t)row_end};
     cond_partition_fill(sm, (uint64_t)di.face_deg + 1, out);
@@ -168,7 +178,7 @@ int pa_condensed_partition_info(size_t Nx, size_t Ny, size_t row_begin, size_t r
 
 int pa_condensed_query(pa_context *ctx, pa_degree_info di, pa_condensed_info *out)
 {
-    if (!ctx || !out || !cond_degree_ok(di)) return PA_ERR_INVALID_ARG;
+    if (!ctx || !out || !degree_ok(di)) return PA_ERR_INVALID_ARG;
     (void)hipSetDevice(ctx->device);
     const int st = cond_prepare(ctx);
     if (st != PA_OK) return st;
@@ -191,7 +201,7 @@ int pa_condensed_triplets_batch(pa_context *ctx, pa_degree_info di, size_t first
 {
     if (!ctx || !d_cond || !d_rows || !d_cols || !d_vals || !d_rhs_rows || !d_rhs_vals) return PA_ERR_INVALID_ARG;
     (void)hipSetDevice(ctx->device);
-    if (!cond_degree_ok(di)) return PA_ERR_INVALID_DEGREE;
+    if (!degree_ok(di)) return PA_ERR_INVALID_DEGREE;
     if (!ctx->faces.cell_faces.get()) return PA_ERR_NO_MESH;
     if (first > ctx->mesh.ncells || n > ctx->mesh.ncells - first) return PA_ERR_INVALID_ARG;
     if ((uint64_t)(di.face_deg + 1) * ctx->faces.num_other_faces >= ((uint64_t)1 << 31)) return PA_ERR_INVALID_ARG;      // int triplet indices
@@ -203,19 +213,19 @@ int pa_condensed_triplets_batch(pa_context *ctx, pa_degree_info di, size_t first
 
 int pa_condensed_csr_pattern(pa_context *ctx, pa_degree_info di, int64_t *d_rowptr, int32_t *d_colind)
 {
-    if (!ctx || !d_rowptr || !cond_degree_ok(di)) return PA_ERR_INVALID_ARG;
+    if (!ctx || !d_rowptr || !degree_ok(di)) return PA_ERR_INVALID_ARG;
     (void)hipSetDevice(ctx->device);
     const int st = cond_prepare(ctx);
     if (st != PA_OK) return st;
     if ((uint64_t)(di.face_deg + 1) * ctx->faces.num_other_faces >= ((uint64_t)1 << 31)) return PA_ERR_INVALID_ARG;      // int32 column ids
-    PA_HIP(ctx, pa::cond_pattern(ctx->stream, ctx->cond.nown, di.face_deg + 1, ctx->cond.cfaces.get(), ctx->cond.prefix.get(), d_rowptr, d_colind));
+    PA_HIP(ctx, pa::cond_pattern(ctx->stream, face_system_view(ctx), di.face_deg + 1, d_rowptr, d_colind));
     return PA_OK;
 }
 
 int pa_condensed_csr_fill(pa_context *ctx, pa_degree_info di, const double *d_cond, const double *d_g, const double *d_halo_below,
                           double *d_values, double *d_rhs)
 {
-    if (!ctx || !d_cond || !d_values || !cond_degree_ok(di)) return PA_ERR_INVALID_ARG;
+    if (!ctx || !d_cond || !d_values || !degree_ok(di)) return PA_ERR_INVALID_ARG;
     (void)hipSetDevice(ctx->device);
     const int st = cond_prepare(ctx);
     if (st != PA_OK) return st;
@@ -224,8 +234,7 @@ int pa_condensed_csr_fill(pa_context *ctx, pa_degree_info di, const double *d_co
         return PA_ERR_INVALID_ARG;
     }
     PA_HIP(ctx, hipSetDevice(ctx->device));
-    PA_HIP(ctx, pa::cond_fill(ctx->stream, cond_mesh(ctx), ctx->cond.nown, di.face_deg + 1, ctx->cond.cfaces_lean.get(), ctx->cond.prefix.get(), d_cond, d_g,
-                              d_halo_below, d_values, d_rhs));
+    PA_HIP(ctx, pa::cond_fill(ctx->stream, face_system_view(ctx), di.face_deg + 1, d_cond, d_g, d_halo_below, d_values, d_rhs));
     return PA_OK;
 }
 
@@ -245,66 +254,51 @@ int asm_prepare(pa_context *ctx)
     PA_HIP(ctx, t.cprefix.alloc((size_t)nc + 1));
     PA_HIP(ctx, t.nfcell.alloc((size_t)nown + 1));
     PA_HIP(ctx, t.fprefix.alloc((size_t)nown + 1));
-    PA_HIP(ctx, pa::asm_build_tables(ctx->stream, cond_mesh(ctx), nc, nown, ctx->cond.cfaces_lean.get(), t.nfc.get(), t.cprefix.get(),
-                                     t.nfcell.get(), t.fprefix.get()));
+    const pa::FaceSystemView v = face_system_view(ctx, ctx->cond, t);
+    PA_HIP(ctx, pa::asm_build_tables(ctx->stream, v, t));
     uint32_t a = 0, b = 0;
     PA_HIP(ctx, hipMemcpy(&a, t.cprefix.get() + nc, sizeof(uint32_t), hipMemcpyDeviceToHost));
     PA_HIP(ctx, hipMemcpy(&b, t.fprefix.get() + nown, sizeof(uint32_t), hipMemcpyDeviceToHost));
     // the per-cell scatter table of the fused path
     PA_HIP(ctx, t.scatter.alloc(nc));
-    PA_HIP(ctx, pa::asm_build_scatter_table(ctx->stream, cond_mesh(ctx), nc, ctx->cond.cfaces.get(), ctx->cond.prefix.get(), t.cprefix.get(),
-                                            t.fprefix.get(), t.scatter.get()));
+    PA_HIP(ctx, pa::asm_build_scatter_table(ctx->stream, v, t.scatter.get()));
     t.cell_faces_total = a; t.face_cells_total = b;
     ctx->asmb = std::move(t);
     return PA_OK;
 }
 
-void asm_sizes(const pa_context *ctx, pa_degree_info di, uint64_t *cell_nnz, uint64_t *nnz, uint64_t *nrows)
-{
-    const uint64_t cbs = (uint64_t)(di.cell_deg + 2) * (di.cell_deg + 1) / 2, fbs = (uint64_t)di.face_deg + 1;
-    *cell_nnz = cbs * (ctx->mesh.ncells * cbs + ctx->asmb.cell_faces_total * fbs);
-    *nnz = *cell_nnz + fbs * (ctx->asmb.face_cells_total * cbs + ctx->cond.total_cols * fbs);
-    *nrows = cbs * ctx->mesh.ncells + fbs * ctx->faces.num_other_faces;
-}
-
 int pa_assembler_csr_query(pa_context *ctx, pa_degree_info di, pa_assembler_csr_info *out)
 {
-    if (!ctx || !out || !cond_degree_ok(di)) return PA_ERR_INVALID_ARG;
+    if (!ctx || !out || !degree_ok(di)) return PA_ERR_INVALID_ARG;
     (void)hipSetDevice(ctx->device);
     const int st = asm_prepare(ctx);
     if (st != PA_OK) return st;
-    uint64_t cell_nnz;
-    asm_sizes(ctx, di, &cell_nnz, &out->nnz, &out->nrows);
+    const pa::AsmSizes z = pa::asm_sizes(face_system_view(ctx), pa::P2(di.cell_deg), di.face_deg + 1);
+    out->nnz = z.nnz; out->nrows = z.nrows;
     return PA_OK;
 }
 
 int pa_assembler_csr_pattern(pa_context *ctx, pa_degree_info di, int64_t *d_rowptr, int32_t *d_colind)
 {
-    if (!ctx || !d_rowptr || !cond_degree_ok(di)) return PA_ERR_INVALID_ARG;
+    if (!ctx || !d_rowptr || !degree_ok(di)) return PA_ERR_INVALID_ARG;
     (void)hipSetDevice(ctx->device);
     const int st = asm_prepare(ctx);
     if (st != PA_OK) return st;
-    uint64_t cell_nnz, nnz, nrows;
-    asm_sizes(ctx, di, &cell_nnz, &nnz, &nrows);
-    if (nrows >= ((uint64_t)1 << 31)) return PA_ERR_INVALID_ARG;                    // int32 column ids
-    PA_HIP(ctx, pa::asm_pattern(ctx->stream, cond_mesh(ctx), (di.cell_deg + 2) * (di.cell_deg + 1) / 2, di.face_deg + 1, (uint32_t)ctx->mesh.ncells,
-                                ctx->cond.nown, cell_nnz, ctx->cond.cfaces.get(), ctx->cond.prefix.get(), ctx->asmb.cprefix.get(), ctx->asmb.fprefix.get(), d_rowptr,
-                                d_colind));
+    const pa::FaceSystemView v = face_system_view(ctx);
+    const int cbs = pa::P2(di.cell_deg), fbs = di.face_deg + 1;
+    if (pa::asm_sizes(v, cbs, fbs).nrows >= ((uint64_t)1 << 31)) return PA_ERR_INVALID_ARG;      // int32 column ids
+    PA_HIP(ctx, pa::asm_pattern(ctx->stream, v, cbs, fbs, d_rowptr, d_colind));
     return PA_OK;
 }
 
 int pa_assembler_csr_fill(pa_context *ctx, pa_degree_info di, const double *d_lc, const double *d_rhs, const double *d_g,
                           double *d_values, double *d_RHS)
 {
-    if (!ctx || !d_lc || !d_values || !cond_degree_ok(di)) return PA_ERR_INVALID_ARG;
+    if (!ctx || !d_lc || !d_values || !degree_ok(di)) return PA_ERR_INVALID_ARG;
     (void)hipSetDevice(ctx->device);
     const int st = asm_prepare(ctx);
     if (st != PA_OK) return st;
-    uint64_t cell_nnz, nnz, nrows;
-    asm_sizes(ctx, di, &cell_nnz, &nnz, &nrows);
-    PA_HIP(ctx, pa::asm_fill(ctx->stream, cond_mesh(ctx), (di.cell_deg + 2) * (di.cell_deg + 1) / 2, di.face_deg + 1, (uint32_t)ctx->mesh.ncells,
-                             ctx->cond.nown, cell_nnz, ctx->cond.cfaces_lean.get(), ctx->cond.prefix.get(), ctx->asmb.cprefix.get(), ctx->asmb.fprefix.get(), d_lc, d_rhs,
-                             d_g, d_values, d_RHS));
+    PA_HIP(ctx, pa::asm_fill(ctx->stream, face_system_view(ctx), pa::P2(di.cell_deg), di.face_deg + 1, d_lc, d_rhs, d_g, d_values, d_RHS));
     return PA_OK;
 }
 
@@ -323,25 +317,20 @@ int pa_assembler_csr_assemble(pa_context *ctx, pa_degree_info di, int quad_kind,
     if (!e->launch_asm) return PA_ERR_INVALID_DEGREE;
     st = asm_prepare(ctx);
     if (st != PA_OK) return st;
-    if (ctx->side_pending) {                              // cut-cell work still out on the side stream
-        PA_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_side, 0));
-        ctx->side_pending = false;
-    }
-    uint64_t cell_nnz, nnz, nrows;
-    asm_sizes(ctx, di, &cell_nnz, &nnz, &nrows);
-    const int cbs = (di.cell_deg + 2) * (di.cell_deg + 1) / 2, fbs = di.face_deg + 1;
-    PA_HIP(ctx, pa::asm_zero_accumulated(ctx->stream, cbs, fbs, (uint32_t)ctx->mesh.ncells, ctx->cond.nown, cell_nnz, ctx->cond.cfaces.get(), ctx->cond.prefix.get(),
-                                         ctx->asmb.fprefix.get(), d_values, d_RHS));
+    PA_HIP(ctx, join_side_stream(ctx));      // cut-cell work still out on the side stream
+    const pa::FaceSystemView v = face_system_view(ctx);
+    const int cbs = pa::P2(di.cell_deg), fbs = di.face_deg + 1;
+    PA_HIP(ctx, pa::asm_zero_accumulated(ctx->stream, v, cbs, fbs, d_values, d_RHS));
     LocalOpsOut o;
     o.cond = true; o.assemble = true; o.rhs = d_rhs; o.lc = d_lc; o.info = d_info;
     o.scatter.tab = ctx->asmb.scatter.get(); o.scatter.g = d_g; o.scatter.values = d_values; o.scatter.RHS = d_RHS;
-    o.scatter.cell_nnz = cell_nnz; o.scatter.ncells = ctx->mesh.ncells;
+    o.scatter.cell_nnz = pa::asm_sizes(v, cbs, fbs).cell_nnz; o.scatter.ncells = ctx->mesh.ncells;
     return run_local_ops(ctx, di, quad_kind, stab_kind, 0, ctx->mesh.ncells, o);
 }
 
 int pa_condensed_halo_pack(pa_context *ctx, pa_degree_info di, const double *d_cond, const double *d_g, double *d_halo)
 {
-    if (!ctx || !d_cond || !d_halo || !cond_degree_ok(di)) return PA_ERR_INVALID_ARG;
+    if (!ctx || !d_cond || !d_halo || !degree_ok(di)) return PA_ERR_INVALID_ARG;
     (void)hipSetDevice(ctx->device);
     if (!ctx->faces.cell_faces.get()) return PA_ERR_NO_MESH;
     if (!ctx->faces.structured || ctx->faces.sm.row1 >= ctx->faces.sm.Ny) return PA_OK;          // nothing above this slab
@@ -356,7 +345,7 @@ int pa_condensed_take_faces(pa_context *ctx, pa_degree_info di, size_t first, si
 {
     if (!ctx || !d_solution || !d_uF) return PA_ERR_INVALID_ARG;
     (void)hipSetDevice(ctx->device);
-    if (!cond_degree_ok(di)) return PA_ERR_INVALID_DEGREE;
+    if (!degree_ok(di)) return PA_ERR_INVALID_DEGREE;
     if (!ctx->faces.cell_faces.get()) return PA_ERR_NO_MESH;
     if (first > ctx->mesh.ncells || n > ctx->mesh.ncells - first) return PA_ERR_INVALID_ARG;
     PA_HIP(ctx, hipSetDevice(ctx->device));
@@ -368,7 +357,7 @@ int pa_condensed_expand_solution(pa_context *ctx, pa_degree_info di, const doubl
 {
     if (!ctx || !d_uT || !d_full) return PA_ERR_INVALID_ARG;
     (void)hipSetDevice(ctx->device);
-    if (!cond_degree_ok(di)) return PA_ERR_INVALID_DEGREE;
+    if (!degree_ok(di)) return PA_ERR_INVALID_DEGREE;
     if (!ctx->faces.cell_faces.get()) return PA_ERR_NO_MESH;
     PA_HIP(ctx, hipSetDevice(ctx->device));
     PA_HIP(ctx, pa::cond_expand(ctx->stream, ctx->mesh.ncells, ctx->mesh.cell_base, ctx->mesh.ncells_global, pa::P2(di.cell_deg),

@@ -345,10 +345,7 @@ int pa_cut_merge(pa_context *ctx, int face_deg, int where, const double *d_cut_l
     const int cbs = pa::P2(face_deg + 1), ms = cbs + 4 * (face_deg + 1);
     const uint32_t nc = (uint32_t)ctx->mesh.ncells;
     const uint32_t ncut = (uint32_t)ctx->cut.host->cut_cells.size();
-    if (ctx->side_pending) {                              // the cut cells' kernel ran on the side stream
-        PA_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_side, 0));
-        ctx->side_pending = false;
-    }
+    PA_HIP(ctx, join_side_stream(ctx));      // the cut cells' kernel ran on the side stream
     if (d_rhs != nullptr && nc) {
         const size_t total = (size_t)nc * (size_t)cbs;
         hipLaunchKernelGGL(pa::cut_zero_rhs_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, total, (uint32_t)cbs,
@@ -369,10 +366,7 @@ int pa_cut_merge_condensed(pa_context *ctx, int face_deg, const double *d_cut_Sp
     const uint32_t ncut = (uint32_t)ctx->cut.host->cut_cells.size();
     if (ncut == 0) return PA_OK;
     if (!d_cut_Sp || !d_cut_g) return PA_ERR_INVALID_ARG;
-    if (ctx->side_pending) {                              // the cut cells' kernel ran on the side stream
-        PA_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_side, 0));
-        ctx->side_pending = false;
-    }
+    PA_HIP(ctx, join_side_stream(ctx));      // the cut cells' kernel ran on the side stream
     const int nf = 4 * (face_deg + 1), ntri = nf * (nf + 1) / 2;
     hipLaunchKernelGGL(pa::cut_merge_condensed_kernel, dim3(ncut), dim3(64), 0, ctx->stream, ncut, ctx->cut.cut_cells.get(), ntri, nf, d_cut_Sp, d_cut_g,
                        d_cond);
@@ -405,19 +399,14 @@ int pa_fictdom_csr_assemble(pa_context *ctx, int face_deg, int where, const doub
     if (!e->launch_asm) return PA_ERR_INVALID_DEGREE;
     st = asm_prepare(ctx);
     if (st != PA_OK) return st;
-    if (ctx->side_pending) {                              // d_cut_lc may come from the cut kernel on the side stream
-        PA_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_side, 0));
-        ctx->side_pending = false;
-    }
-    uint64_t cell_nnz, nnz, nrows;
-    asm_sizes(ctx, di, &cell_nnz, &nnz, &nrows);
-    const int cbs = pa::P2(face_deg + 1), fbs = face_deg + 1;
-    PA_HIP(ctx, pa::asm_zero_accumulated(ctx->stream, cbs, fbs, (uint32_t)ctx->mesh.ncells, ctx->cond.nown, cell_nnz, ctx->cond.cfaces.get(), ctx->cond.prefix.get(),
-                                         ctx->asmb.fprefix.get(), d_values, d_RHS));
+    PA_HIP(ctx, join_side_stream(ctx));      // d_cut_lc may come from the cut kernel on the side stream
+    const pa::FaceSystemView v = face_system_view(ctx);
+    const int cbs = pa::P2(di.cell_deg), fbs = di.face_deg + 1;
+    PA_HIP(ctx, pa::asm_zero_accumulated(ctx->stream, v, cbs, fbs, d_values, d_RHS));
     LocalOpsOut o;
     o.cond = true; o.assemble = true; o.rhs = d_rhs; o.lc = d_lc; o.info = d_info;
     o.scatter.tab = ctx->asmb.scatter.get(); o.scatter.g = d_g; o.scatter.values = d_values; o.scatter.RHS = d_RHS;
-    o.scatter.cell_nnz = cell_nnz; o.scatter.ncells = ctx->mesh.ncells;
+    o.scatter.cell_nnz = pa::asm_sizes(v, cbs, fbs).cell_nnz; o.scatter.ncells = ctx->mesh.ncells;
     o.scatter.cell_loc = ctx->cut.cell_loc.get(); o.scatter.where = where;
     st = run_local_ops(ctx, di, PA_QUAD_FAN, PA_STAB_NAIVE, 0, ctx->mesh.ncells, o);
     if (st != PA_OK) return st;

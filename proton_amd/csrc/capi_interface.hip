@@ -206,10 +206,7 @@ static int ifcsr_prepare(pa_context *ctx, int face_deg, bool cut_arrays)
 {
     const int st = if_refusals(ctx, face_deg, cut_arrays);
     if (st != PA_OK) return st;
-    if (ctx->side_pending) {                              // cut-cell work still out on the side stream
-        PA_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_side, 0));
-        ctx->side_pending = false;
-    }
+    PA_HIP(ctx, join_side_stream(ctx));      // cut-cell work still out on the side stream
     if (ctx->cut.ifcsr.t.groups == nullptr || ctx->cut.ifcsr.t.face_deg != face_deg)
         PA_HIP(ctx, pa::ifcsr_build(ctx->stream, ifcsr_mesh(ctx), face_deg, &ctx->cut.ifcsr.t));
     return PA_OK;
@@ -437,10 +434,7 @@ static int ifrows_prepare(pa_context *ctx, int face_deg, bool cut_arrays, bool h
         ctx->last_error = "pa_interface_rows: this slab has a slab below: d_halo_below (pa_interface_rows_halo_pack of that slab) is required";
         return PA_ERR_INVALID_ARG;
     }
-    if (ctx->side_pending) {                              // cut-cell work still out on the side stream
-        PA_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_side, 0));
-        ctx->side_pending = false;
-    }
+    PA_HIP(ctx, join_side_stream(ctx));      // cut-cell work still out on the side stream
     if (!r.ready()) {
         pa::IfRowsArrays d;                               // held by the context only once it is complete
         hipError_t e = hipSuccess;

@@ -350,7 +350,7 @@ int pa_project_function_batch(pa_context *ctx, pa_degree_info di, int quad_kind,
 {
     if (!ctx || !d_out || dinc < 0) return PA_ERR_INVALID_ARG;
     (void)hipSetDevice(ctx->device);
-    if (di.cell_deg < 0 || di.cell_deg > 4 || di.face_deg < 0 || di.face_deg > 3) return PA_ERR_INVALID_DEGREE;
+    if (!degree_ok(di)) return PA_ERR_INVALID_DEGREE;
     if (!ctx->mesh.points) return PA_ERR_NO_MESH;
     if (!ctx->faces.cell_faces.get()) return PA_ERR_NO_MESH;
     if (first > ctx->mesh.ncells || n > ctx->mesh.ncells - first) return PA_ERR_INVALID_ARG;

@@ -44,7 +44,7 @@ int pa_obstacle_triplets_batch(pa_context *ctx, pa_degree_info di, size_t first,
     if (!ctx || !d_lc || !d_gamma || !d_in_A || !d_A_ct || !d_B_ct || !d_rows || !d_cols || !d_vals || !d_rhs_rows ||
         !d_rhs_vals)
         return PA_ERR_INVALID_ARG;
-    if (di.cell_deg < 0 || di.face_deg < 0 || di.face_deg > 3 || di.cell_deg > 4) return PA_ERR_INVALID_DEGREE;
+    if (!degree_ok(di)) return PA_ERR_INVALID_DEGREE;
     if (!ctx->faces.cell_faces.get()) return PA_ERR_NO_MESH;
     if (!whole_mesh(ctx)) { ctx->last_error = "obstacle assembler needs the whole mesh on the context"; return PA_ERR_INVALID_ARG; }
     if (first > ctx->mesh.ncells || n > ctx->mesh.ncells - first || num_I > ctx->mesh.ncells) return PA_ERR_INVALID_ARG;
@@ -75,7 +75,7 @@ int pa_obstacle_expand_solution(pa_context *ctx, pa_degree_info di, const double
 {
     if (!ctx || !d_solution || !d_gamma || !d_in_A || !d_A_ct || !d_B_ct || !d_alpha || !d_beta) return PA_ERR_INVALID_ARG;
     (void)hipSetDevice(ctx->device);
-    if (di.cell_deg < 0 || di.face_deg < 0 || di.face_deg > 3 || di.cell_deg > 4) return PA_ERR_INVALID_DEGREE;
+    if (!degree_ok(di)) return PA_ERR_INVALID_DEGREE;
     if (!ctx->faces.cell_faces.get()) return PA_ERR_NO_MESH;
     if (!whole_mesh(ctx)) { ctx->last_error = "obstacle assembler needs the whole mesh on the context"; return PA_ERR_INVALID_ARG; }
     pa::ExpandArgs a;
@@ -101,7 +101,7 @@ int pa_obstacle_csr_assemble(pa_context *ctx, pa_degree_info di, const double *d
         return PA_ERR_INVALID_ARG;
     }
     (void)hipSetDevice(ctx->device);
-    if (di.cell_deg < 0 || di.face_deg < 0 || di.face_deg > 3 || di.cell_deg > 4) return PA_ERR_INVALID_DEGREE;
+    if (!degree_ok(di)) return PA_ERR_INVALID_DEGREE;
     if (di.cell_deg != 0) {
         ctx->last_error = "pa_obstacle_csr_assemble: the direct path covers cell degree 0 (cbs = 1, obstacle.cpp:51); the overlapping "
                           "cell rows of hho.hpp:631 for cbs > 1 stay with pa_obstacle_triplets_batch + pa_csr_from_triplets";
@@ -116,18 +116,16 @@ int pa_obstacle_csr_assemble(pa_context *ctx, pa_degree_info di, const double *d
     }
     const int st = asm_prepare(ctx);
     if (st != PA_OK) return st;
-    uint64_t cell_nnz, nnz_plain, nrows;
-    asm_sizes(ctx, di, &cell_nnz, &nnz_plain, &nrows);
     pa::ObstacleCsrArgs a;
-    a.cell_faces = ctx->faces.cell_faces.get(); a.face_compress = ctx->faces.face_compress.get(); a.faces = ctx->cond.cfaces.get(); a.lean = ctx->cond.cfaces_lean.get();
-    a.colprefix = ctx->cond.prefix.get(); a.cprefix = ctx->asmb.cprefix.get(); a.fprefix = ctx->asmb.fprefix.get();
-    a.ncells = (uint32_t)ctx->mesh.ncells; a.nown = ctx->cond.nown; a.cell_nnz = cell_nnz;
+    a.v = face_system_view(ctx);
+    const pa::AsmSizes plain = pa::asm_sizes(a.v, 1, fbs);
+    a.cell_nnz = plain.cell_nnz;
     a.in_A = d_in_A; a.A_ct = d_A_ct; a.B_ct = d_B_ct; a.num_I = num_I; a.num_other = ctx->faces.num_other_faces;
     a.lc = d_lc; a.rhs = d_rhs; a.g = d_g; a.gamma = d_gamma;
     a.rowptr = d_rowptr; a.colind = d_colind; a.values = d_values; a.RHS = d_RHS;
     uint32_t removed = 0;
     PA_HIP(ctx, pa::obstacle_csr_assemble(ctx->stream, fbs, a, &removed));
-    *nnz = (size_t)(nnz_plain - (uint64_t)fbs * removed);
+    *nnz = (size_t)(plain.nnz - (uint64_t)fbs * removed);
     return PA_OK;
 }
 
@@ -135,7 +133,7 @@ int pa_obstacle_csr_assemble(pa_context *ctx, pa_degree_info di, const double *d
 // the refusals the three entry points share with pa_obstacle_csr_assemble; PA_OK = go on
 static int obstacle_solve_refusals(pa_context *ctx, pa_degree_info di, const char *who)
 {
-    if (di.cell_deg < 0 || di.face_deg < 0 || di.face_deg > 3 || di.cell_deg > 4) return PA_ERR_INVALID_DEGREE;
+    if (!degree_ok(di)) return PA_ERR_INVALID_DEGREE;
     if (di.cell_deg != 0) {
         ctx->last_error = std::string(who) + ": cell degree 0 only (cbs = 1, obstacle.cpp:51), as pa_obstacle_csr_assemble";
         return PA_ERR_INVALID_DEGREE;

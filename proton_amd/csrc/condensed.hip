@@ -47,8 +47,7 @@ __global__ __launch_bounds__(256) void cond_adj_cells_kernel(uint32_t ncells, co
 }
 
 // The symbolic record of an owned, non-Dirichlet face: its column faces in ascending compressed order and where each
-// of them sits in the face's cells.
-//   code[s] bits 0-1: local face index of column face s in cell A, bit 2: present in A; bits 3-4 / 5: the same for B
+// of them sits in the face's cells (code[s]: face_system.hpp).
 __device__ inline void cond_describe_face(const CondMesh &m, uint32_t f, int32_t &cA, int32_t &cB, int &rowA, int &rowB,
                                           int32_t (&colcomp)[7], uint8_t (&code)[7], int &ncol, bool &dirichlet_cols)
 {
@@ -88,7 +87,7 @@ __device__ inline void cond_describe_face(const CondMesh &m, uint32_t f, int32_t
             int pos = -1;
             for (int q = 0; q < nc; ++q) if (cand_comp[q] == comp) pos = q;
             if (pos < 0) { pos = nc++; cand_comp[pos] = comp; cand_code[pos] = 0; }
-            cand_code[pos] |= side == 0 ? (uint8_t)(lf | 4) : (uint8_t)((lf << 3) | 32);
+            cand_code[pos] |= (uint8_t)(side == 0 ? fcode_in_A(lf) : fcode_in_B(lf));
         }
     }
     // ascending compressed id (insertion sort of at most 7)
@@ -116,15 +115,14 @@ __global__ __launch_bounds__(256) void cond_symbolic_kernel(CondMesh m, uint32_t
     int rowA, rowB, ncol;
     bool dcols;
     cond_describe_face(m, f, r.cA, r.cB, rowA, rowB, r.colcomp, r.code, ncol, dcols);
-    r.rows = (uint8_t)(rowA | (rowB << 2));
+    r.rows = (uint8_t)frows_make(rowA, rowB);
     r.ncol = (uint8_t)ncol;
     r.face = f;
     faces[q] = r;
     ncols[q] = (uint32_t)ncol;
     CondFaceLean ln;
     ln.cA = r.cA; ln.cB = r.cB;
-    ln.packed = ((uint64_t)r.rows << 42) | ((uint64_t)ncol << 46) | ((uint64_t)(dcols ? 1 : 0) << 49);
-    for (int s = 0; s < 7; ++s) ln.packed |= (uint64_t)(r.code[s] & 63) << (6 * s);
+    ln.packed = lean_pack(r.code, r.rows, (uint32_t)ncol, dcols);
     lean[q] = ln;
 }
 
@@ -147,13 +145,14 @@ __global__ __launch_bounds__(256) void cond_pattern_kernel(uint32_t nown, int fb
 
 // contribution of cell `c` (local; rec = its packed record) to right-hand-side row `row` (a face unknown index in
 // 0..nf-1): g_row minus the Dirichlet columns times the boundary data, accumulated in local column order (hho.hpp:401)
-__device__ __forceinline__ double cond_rhs_contrib(const CondMesh &m, const double *rec, int32_t c, int row, int fbs, const double *g)
+__device__ __forceinline__ double cond_rhs_contrib(const uint32_t *cell_faces, const int32_t *face_compress, const double *rec, int32_t c,
+                                                   int row, int fbs, const double *g)
 {
     const int nf = 4 * fbs;
     double s = rec[nf * (nf + 1) / 2 + row];
     for (int lf = 0; lf < 4; ++lf) {
-        const uint32_t fl = m.cell_faces[4 * (uint32_t)c + lf];
-        if (m.face_compress[fl] >= 0) continue;
+        const uint32_t fl = cell_faces[4 * (uint32_t)c + lf];
+        if (face_compress[fl] >= 0) continue;
         for (int kp = 0; kp < fbs; ++kp) {
             const double d = g != nullptr ? g[(size_t)fl * fbs + kp] : 0.0;
             s -= cond_S(rec, row, lf * fbs + kp) * d;
@@ -196,7 +195,7 @@ __global__ __launch_bounds__(256) void cond_fill_kernel(uint32_t nown, const Con
     bool ok[U][PASSES], two[U][PASSES];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-        const uint32_t ncol = (uint32_t)(d[u].packed >> 46) & 7u, rows = (uint32_t)(d[u].packed >> 42) & 15u;
+        const uint32_t ncol = lean_ncol(d[u].packed), rows = lean_rows(d[u].packed);
         const uint32_t rowlen = ncol * FBS;
 #pragma unroll
         for (uint32_t p = 0; p < PASSES; ++p) {
@@ -205,10 +204,10 @@ __global__ __launch_bounds__(256) void cond_fill_kernel(uint32_t nown, const Con
             const uint32_t k = (e >= rowlen) + (e >= 2 * rowlen) + (e >= 3 * rowlen);
             const uint32_t er = ok[u][p] ? e - k * rowlen : 0u;
             const uint32_t s = er / (uint32_t)FBS, kp = er % (uint32_t)FBS;
-            const uint32_t code = (uint32_t)(d[u].packed >> (6 * s)) & 63u;
-            const int rowA = (int)((rows & 3u) * FBS + k), rowB = (int)(((rows >> 2) & 3u) * FBS + k);
-            const int colA = (int)((code & 3u) * FBS + kp), colB = (int)(((code >> 3) & 3u) * FBS + kp);
-            const bool hasA = code & 4u, hasB = code & 32u;
+            const uint32_t code = lean_code(d[u].packed, s);
+            const int rowA = (int)(frows_A(rows) * FBS + k), rowB = (int)(frows_B(rows) * FBS + k);
+            const int colA = (int)(fcode_lf_A(code) * FBS + kp), colB = (int)(fcode_lf_B(code) * FBS + kp);
+            const bool hasA = code & FCODE_HAS_A, hasB = code & FCODE_HAS_B;
             const int aA = rowA < colA ? rowA : colA, bA = rowA < colA ? colA : rowA;
             const int aB = rowB < colB ? rowB : colB, bB = rowB < colB ? colB : rowB;
             const double *pA = d[u].cA >= 0 ? cond + (size_t)d[u].cA * ncond + (bA * (bA + 1) / 2 + aA)
@@ -235,30 +234,31 @@ __global__ __launch_bounds__(256) void cond_fill_kernel(uint32_t nown, const Con
 }
 
 // right-hand side of the owned rows: one thread per (owned face, row k)
-__global__ __launch_bounds__(256) void cond_rhs_rows_kernel(CondMesh m, uint32_t nown, int fbs, const CondFaceLean *lean,
-                                                            const double *cond, const double *g, const double *halo, double *rhs)
+__global__ __launch_bounds__(256) void cond_rhs_rows_kernel(const uint32_t *cell_faces, const int32_t *face_compress, uint32_t nown, int fbs,
+                                                            const CondFaceLean *lean, const double *cond, const double *g,
+                                                            const double *halo, double *rhs)
 {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t q = t / (uint32_t)fbs;
     if (q >= nown) return;
     const int k = (int)(t % (uint32_t)fbs);
     const CondFaceLean r = lean[q];
-    const uint32_t rows = (uint32_t)(r.packed >> 42) & 15u;
+    const uint32_t rows = lean_rows(r.packed);
     const int nf = 4 * fbs, ncond = nf * (nf + 1) / 2 + nf, hd = fbs * (nf + 1);
-    const int rowA = (int)(rows & 3u) * fbs + k, rowB = (int)((rows >> 2) & 3u) * fbs + k;
-    // (bit 49: some face of its local cells is Dirichlet; otherwise a cell's contribution is its g entry alone)
-    const bool dcols = (r.packed >> 49) & 1u;
+    const int rowA = (int)frows_A(rows) * fbs + k, rowB = (int)frows_B(rows) * fbs + k;
+    // (some face of its local cells is Dirichlet; otherwise a cell's contribution is its g entry alone)
+    const bool dcols = lean_dirichlet(r.packed);
     const int og = nf * (nf + 1) / 2;
     double b = 0.0;
     bool have = false;
     if (r.cA >= 0) {
         const double *rec = cond + (size_t)r.cA * ncond;
-        b = dcols ? cond_rhs_contrib(m, rec, r.cA, rowA, fbs, g) : rec[og + rowA];
+        b = dcols ? cond_rhs_contrib(cell_faces, face_compress, rec, r.cA, rowA, fbs, g) : rec[og + rowA];
         have = true;
     } else if (r.cA <= -2) { b = halo[(size_t)(-2 - r.cA) * hd + fbs * nf + k]; have = true; }
     if (r.cB >= 0) {
         const double *rec = cond + (size_t)r.cB * ncond;
-        const double w = dcols ? cond_rhs_contrib(m, rec, r.cB, rowB, fbs, g) : rec[og + rowB];
+        const double w = dcols ? cond_rhs_contrib(cell_faces, face_compress, rec, r.cB, rowB, fbs, g) : rec[og + rowB];
         b = have ? b + w : w;
     }
     rhs[t] = b;
@@ -277,7 +277,7 @@ __global__ __launch_bounds__(256) void cond_halo_pack_kernel(CondMesh m, uint32_
     const double *rec = cond + (size_t)c * ncond;
     double v;
     if (e < fbs * nf) v = cond_S(rec, 2 * fbs + e / nf, e % nf);
-    else v = cond_rhs_contrib(m, rec, (int32_t)c, 2 * fbs + (e - fbs * nf), fbs, g);
+    else v = cond_rhs_contrib(m.cell_faces, m.face_compress, rec, (int32_t)c, 2 * fbs + (e - fbs * nf), fbs, g);
     halo[t] = v;
 }
 
@@ -346,36 +346,38 @@ __global__ __launch_bounds__(256) void condensed_expand_kernel(size_t ncells_loc
 
 // ---- host side ---------------------------------------------------------------------------------------------------
 hipError_t cond_build_tables(hipStream_t stream, CondMesh m, uint32_t nfaces_local, uint32_t ncells, uint32_t owned_range,
-                             int32_t p0, uint32_t nown, int32_t *adj, CondFace *faces, CondFaceLean *lean, uint32_t *ncols,
-                             uint32_t *prefix)
+                             int32_t p0, uint32_t nown, const CondTables &t)
 {
-    hipLaunchKernelGGL(cond_adj_init_kernel, dim3(blocks_for(nfaces_local)), dim3(256), 0, stream, nfaces_local, adj);
-    hipLaunchKernelGGL(cond_adj_cells_kernel, dim3(blocks_for((size_t)4 * ncells)), dim3(256), 0, stream, ncells, m.cell_faces, adj);
+    m.adj = t.adj.get();
+    uint32_t *ncols = t.ncols.get();
+    hipLaunchKernelGGL(cond_adj_init_kernel, dim3(blocks_for(nfaces_local)), dim3(256), 0, stream, nfaces_local, t.adj.get());
+    hipLaunchKernelGGL(cond_adj_cells_kernel, dim3(blocks_for((size_t)4 * ncells)), dim3(256), 0, stream, ncells, m.cell_faces, t.adj.get());
     hipError_t e = hipMemsetAsync(ncols, 0, ((size_t)nown + 1) * sizeof(uint32_t), stream);
     if (e != hipSuccess) return e;
-    m.adj = adj;
-    hipLaunchKernelGGL(cond_symbolic_kernel, dim3(blocks_for(owned_range)), dim3(256), 0, stream, m, owned_range, p0, nown, faces, lean, ncols);
+    hipLaunchKernelGGL(cond_symbolic_kernel, dim3(blocks_for(owned_range)), dim3(256), 0, stream, m, owned_range, p0, nown, t.cfaces.get(),
+                       t.cfaces_lean.get(), ncols);
     DeviceTmp tmp(stream);
-    if (!tmp.ok(hipGetLastError()) || exclusive_scan_with_total<uint32_t>(stream, ncols, prefix, (size_t)nown + 1, tmp, nullptr) != hipSuccess)
+    if (!tmp.ok(hipGetLastError()) ||
+        exclusive_scan_with_total<uint32_t>(stream, ncols, t.prefix.get(), (size_t)nown + 1, tmp, nullptr) != hipSuccess)
         return tmp.error();
     tmp.ok(hipStreamSynchronize(stream));
     return tmp.error();
 }
 
-hipError_t cond_pattern(hipStream_t stream, uint32_t nown, int fbs, const CondFace *faces, const uint32_t *prefix, int64_t *rowptr,
-                        int32_t *colind)
+hipError_t cond_pattern(hipStream_t stream, const FaceSystemView &v, int fbs, int64_t *rowptr, int32_t *colind)
 {
-    hipLaunchKernelGGL(cond_pattern_kernel, dim3(blocks_for(((size_t)nown + 1) * fbs)), dim3(256), 0, stream, nown, fbs, faces, prefix,
-                       rowptr, colind);
+    hipLaunchKernelGGL(cond_pattern_kernel, dim3(blocks_for(((size_t)v.nown + 1) * fbs)), dim3(256), 0, stream, v.nown, fbs, v.faces,
+                       v.colprefix, rowptr, colind);
     return hipGetLastError();
 }
 
 #ifndef PA_FILL_UNROLL
 #define PA_FILL_UNROLL 4
 #endif
-hipError_t cond_fill(hipStream_t stream, const CondMesh &m, uint32_t nown, int fbs, const CondFaceLean *lean, const uint32_t *prefix,
-                     const double *cond, const double *g, const double *halo, double *values, double *rhs)
+hipError_t cond_fill(hipStream_t stream, const FaceSystemView &v, int fbs, const double *cond, const double *g, const double *halo,
+                     double *values, double *rhs)
 {
+    const uint32_t nown = v.nown;
     if (nown == 0) return hipSuccess;
     constexpr int U = PA_FILL_UNROLL;
     const uint32_t per_face = 7u * fbs * fbs, fpw = per_face <= 32 ? 64u / per_face : 1u;
@@ -383,15 +385,15 @@ hipError_t cond_fill(hipStream_t stream, const CondMesh &m, uint32_t nown, int f
     const dim3 grid((nown + faces_per_block - 1) / faces_per_block), block(256);
     const double *h = halo ? halo : cond;
     switch (fbs) {
-    case 1: hipLaunchKernelGGL((cond_fill_kernel<1, U>), grid, block, 0, stream, nown, lean, prefix, cond, h, values); break;
-    case 2: hipLaunchKernelGGL((cond_fill_kernel<2, U>), grid, block, 0, stream, nown, lean, prefix, cond, h, values); break;
-    case 3: hipLaunchKernelGGL((cond_fill_kernel<3, U>), grid, block, 0, stream, nown, lean, prefix, cond, h, values); break;
-    case 4: hipLaunchKernelGGL((cond_fill_kernel<4, U>), grid, block, 0, stream, nown, lean, prefix, cond, h, values); break;
+    case 1: hipLaunchKernelGGL((cond_fill_kernel<1, U>), grid, block, 0, stream, nown, v.lean, v.colprefix, cond, h, values); break;
+    case 2: hipLaunchKernelGGL((cond_fill_kernel<2, U>), grid, block, 0, stream, nown, v.lean, v.colprefix, cond, h, values); break;
+    case 3: hipLaunchKernelGGL((cond_fill_kernel<3, U>), grid, block, 0, stream, nown, v.lean, v.colprefix, cond, h, values); break;
+    case 4: hipLaunchKernelGGL((cond_fill_kernel<4, U>), grid, block, 0, stream, nown, v.lean, v.colprefix, cond, h, values); break;
     default: return hipErrorInvalidValue;
     }
     if (rhs != nullptr)
-        hipLaunchKernelGGL(cond_rhs_rows_kernel, dim3(blocks_for((size_t)nown * fbs)), dim3(256), 0, stream, m, nown, fbs, lean, cond, g,
-                           h, rhs);
+        hipLaunchKernelGGL(cond_rhs_rows_kernel, dim3(blocks_for((size_t)nown * fbs)), dim3(256), 0, stream, v.cell_faces, v.face_compress,
+                           nown, fbs, v.lean, cond, g, h, rhs);
     return hipGetLastError();
 }
 

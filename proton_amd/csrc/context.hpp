@@ -52,27 +52,6 @@ struct FaceState {
     bool structured = false;
 };
 
-// condensed (face-only) assembly: face adjacency and the symbolic records of the owned faces, built on first use (cond_prepare)
-struct CondTables {
-    DeviceBuf<int32_t> adj;
-    DeviceBuf<CondFace> cfaces;
-    DeviceBuf<CondFaceLean> cfaces_lean;
-    DeviceBuf<uint32_t> ncols, prefix;
-    uint32_t nown = 0, owned_range = 0;
-    int32_t p0 = 0;
-    uint64_t total_cols = 0;                  // sum of the column-face counts of the owned faces
-    bool ready() const { return prefix.get() != nullptr; }
-};
-
-// direct CSR of the assembler's own system (assembler_csr.hip): non-Dirichlet faces per cell / cells per face and their prefixes,
-// and per cell where the fused assembly's scatter writes (hho_asm_scatter.hpp); built on first use (asm_prepare)
-struct AsmTables {
-    DeviceBuf<uint32_t> nfc, cprefix, nfcell, fprefix;
-    DeviceBuf<AsmCellRec> scatter;
-    uint64_t cell_faces_total = 0, face_cells_total = 0;
-    bool ready() const { return scatter.get() != nullptr; }
-};
-
 // IfCsrTables (interface_csr.hpp) held by a group: released with it.  ifcsr_build frees what *t holds first and leaves it empty
 // on failure.
 struct IfCsrOwner {
@@ -164,7 +143,13 @@ struct pa_context {
 #include "pa_configs.def"
 #undef PA_CONFIG
 
+// the degree pairs every entry point with a pa_degree_info accepts (each answers a pair outside with its own status code)
+static inline bool degree_ok(pa_degree_info di) { return di.cell_deg >= 0 && di.cell_deg <= 4 && di.face_deg >= 0 && di.face_deg <= 3; }
+
 // capi.hip
+// work still out on the side stream (the cut cells' kernel under pa_context_set_cut_overlap) is ordered before what the
+// context's stream gets next
+PA_INTERNAL hipError_t join_side_stream(pa_context *ctx);
 PA_INTERNAL const pa::KernelEntry *find_kernel(int cd, int fd, int quad, int stab, int lanes);
 PA_INTERNAL int min_lanes(int cd, int fd, int quad);
 PA_INTERNAL bool whole_mesh(const pa_context *ctx);
@@ -193,10 +178,10 @@ PA_INTERNAL int condense(pa_context *ctx, pa_degree_info di, size_t n, const dou
                          double *d_rec, int32_t *d_info, int packed);
 
 // capi_assembly.hip
-PA_INTERNAL pa::CondMesh cond_mesh(const pa_context *ctx);
 PA_INTERNAL int cond_prepare(pa_context *ctx);
 PA_INTERNAL int asm_prepare(pa_context *ctx);
-PA_INTERNAL void asm_sizes(const pa_context *ctx, pa_degree_info di, uint64_t *cell_nnz, uint64_t *nnz, uint64_t *nrows);
+// the tables of face_system.hpp as the context holds them: the condensed part after cond_prepare, all of it after asm_prepare
+PA_INTERNAL pa::FaceSystemView face_system_view(const pa_context *ctx);
 
 // capi_cut.hip
 PA_INTERNAL int ensure_cut_lists(pa_context *ctx, int face_deg, int where);

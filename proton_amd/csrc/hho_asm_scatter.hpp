@@ -13,7 +13,7 @@
 namespace pa {
 
 // Where the entries of one cell go.  The record holds counts, not offsets, so that one table serves every degree pair of a
-// mesh: the offsets are the closed forms of assembler_csr.hip (cell_block_start, face_block_start) in the block sizes the
+// mesh: the offsets are the closed forms of face_system.hpp (cell_block_start, face_block_start) in the block sizes the
 // kernel instance knows at compile time.
 struct alignas(16) AsmCellRec {
     uint32_t cpre;           // non-Dirichlet faces of the cells before this one (cprefix)
@@ -104,7 +104,7 @@ __device__ __forceinline__ void asm_scatter_cell(const AsmScatterArgs &s, const 
                            : n == 2 ? (65536u + CBS + 2 * FBS - 1) / (CBS + 2 * FBS)
                            : n == 3 ? (65536u + CBS + 3 * FBS - 1) / (CBS + 3 * FBS) : (65536u + MS - 1) / MS;
         static_assert(CBS * MS < 1024 && MS < 64, "the reciprocal division of the cell rows");
-        double *dst = s.values + (uint64_t)CBS * ((uint64_t)cell * CBS + (uint64_t)rp->cpre * FBS);
+        double *dst = s.values + (uint64_t)CBS * ((uint64_t)cell * CBS + (uint64_t)rp->cpre * FBS);         // cell_block_start
         constexpr int NIT = (CBS * MS + G - 1) / G;
         const int E = CBS * R;
 #pragma unroll
@@ -139,7 +139,7 @@ __device__ __forceinline__ void asm_scatter_cell(const AsmScatterArgs &s, const 
         const uint32_t ncell = (pk >> 12) & 3u, ncol = (pk >> 16) & 7u;
         const uint32_t R = ncell * CBS + ncol * FBS;
         const uint32_t coff = (pk & (1u << 14)) ? (uint32_t)CBS : 0u;
-        double *dst = s.values + s.cell_nnz + (uint64_t)FBS * ((uint64_t)rp->fpre[lf] * CBS + (uint64_t)rp->colpre[lf] * FBS);
+        double *dst = s.values + s.cell_nnz + (uint64_t)FBS * ((uint64_t)rp->fpre[lf] * CBS + (uint64_t)rp->colpre[lf] * FBS);      // face_block_start
         constexpr int NIT = (FBS * MS + G - 1) / G;
         static_assert(NIT <= CH, "one chunk per face");
         double v[NIT];
@@ -167,7 +167,7 @@ __device__ __forceinline__ void asm_scatter_cell(const AsmScatterArgs &s, const 
             else dst[off[it]] = v[it];
         }
     }
-    // ---- right-hand side: the terms and the order of asm_fill_cells_kernel / asm_face_rhs_contrib (the triplet path's
+    // ---- right-hand side: the terms and the order of dirichlet_rhs_contrib (face_system.hpp; the triplet path's
     // rhs - sum lc g over the Dirichlet columns in local column order, hho.hpp:401, 405)
     if (s.RHS != nullptr && l < MS) {
         const bool crow = l < CBS;

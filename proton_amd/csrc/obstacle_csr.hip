@@ -48,13 +48,13 @@ template <int FBS>
 __device__ __forceinline__ void obstacle_known(const ObstacleCsrArgs &a, uint32_t c, int32_t (&col)[1 + 4 * FBS],
                                                double (&dd)[1 + 4 * FBS])
 {
-    const uint4 f = *reinterpret_cast<const uint4 *>(a.cell_faces + 4 * (size_t)c);
+    const uint4 f = *reinterpret_cast<const uint4 *>(a.v.cell_faces + 4 * (size_t)c);
     const uint32_t fl[4] = {f.x, f.y, f.z, f.w};
     col[0] = a.in_A[c] != 0 ? -1 : 0;
     dd[0] = 0.0;
 #pragma unroll
     for (int lf = 0; lf < 4; ++lf) {
-        const bool dirichlet = a.face_compress[fl[lf]] < 0;
+        const bool dirichlet = a.v.face_compress[fl[lf]] < 0;
 #pragma unroll
         for (int k = 0; k < FBS; ++k) {
             col[1 + lf * FBS + k] = dirichlet ? -1 : 0;
@@ -70,29 +70,13 @@ __global__ __launch_bounds__(256) void obstacle_csr_cells_kernel(ObstacleCsrArgs
 {
     constexpr int MS = 1 + 4 * FBS, G = MS < 16 ? 16 : 32;
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t / G >= a.ncells) return;
+    if (t / G >= a.v.ncells) return;
     const uint32_t c = (uint32_t)(t / G);
     const int e = (int)(t % G);
-    // the non-Dirichlet faces of the cell in ascending compressed order (insertion into a sorted prefix of at most 4)
-    const uint4 f4 = *reinterpret_cast<const uint4 *>(a.cell_faces + 4 * (size_t)c);
-    const int32_t cc[4] = {a.face_compress[f4.x], a.face_compress[f4.y], a.face_compress[f4.z], a.face_compress[f4.w]};
-    int32_t comp[4] = {0x7fffffff, 0x7fffffff, 0x7fffffff, 0x7fffffff};
-    int lfs[4] = {0, 0, 0, 0}, nf = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-        if (cc[q] >= 0) {
-            int p = nf;
-#pragma unroll
-            for (int s = 2; s >= 0; --s)
-                if (s < nf && comp[s] > cc[q]) { comp[s + 1] = comp[s]; lfs[s + 1] = lfs[s]; p = s; }
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-                if (s == p) { comp[s] = cc[q]; lfs[s] = q; }
-            ++nf;
-        }
+    const CellFaces cf = cell_faces_sorted<true>(a.v.cell_faces, a.v.face_compress, c);
     const bool active = a.in_A[c] != 0;
-    const int len = 1 + nf * FBS;
-    const uint64_t start = (uint64_t)c + (uint64_t)a.cprefix[c] * FBS;
+    const int len = 1 + cf.n * FBS;
+    const uint64_t start = cell_block_start(1, FBS, c, a.v.cprefix[c]);
     const double *A = a.lc + (size_t)c * (MS * MS);
     if (e == 0) a.rowptr[c] = (int64_t)start;
     if (e < len) {
@@ -107,8 +91,8 @@ __global__ __launch_bounds__(256) void obstacle_csr_cells_kernel(ObstacleCsrArgs
         } else {
             const int fe = active ? e : e - 1;
             const int s = fe / FBS, kp = fe % FBS;
-            const int32_t cs = s == 0 ? comp[0] : s == 1 ? comp[1] : s == 2 ? comp[2] : comp[3];
-            const int lf = s == 0 ? lfs[0] : s == 1 ? lfs[1] : s == 2 ? lfs[2] : lfs[3];
+            const int32_t cs = s == 0 ? cf.comp[0] : s == 1 ? cf.comp[1] : s == 2 ? cf.comp[2] : cf.comp[3];
+            const int lf = s == 0 ? cf.lf[0] : s == 1 ? cf.lf[1] : s == 2 ? cf.lf[2] : cf.lf[3];
             col = (int32_t)(a.num_I + (uint64_t)cs * FBS + kp);    // :645
             v = A[(size_t)(1 + lf * FBS + kp) * MS];
         }
@@ -131,22 +115,22 @@ __global__ __launch_bounds__(256) void obstacle_csr_faces_kernel(ObstacleCsrArgs
 {
     constexpr int MS = 1 + 4 * FBS, G = FBS == 1 ? 16 : FBS == 2 ? 32 : 64;
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t / G > a.nown) return;
+    if (t / G > a.v.nown) return;
     const uint32_t q = (uint32_t)(t / G);
     const int l = (int)(t % G);
-    int64_t *rp = a.rowptr + a.ncells;
-    const uint64_t start = a.cell_nnz + (uint64_t)FBS * ((uint64_t)(a.fprefix[q] - rprefix[q]) + (uint64_t)a.colprefix[q] * FBS);
-    if (q == a.nown) {
-        if (l == 0) rp[(size_t)a.nown * FBS] = (int64_t)start;
+    int64_t *rp = a.rowptr + a.v.ncells;
+    const uint64_t start = face_block_start(a.cell_nnz, 1, FBS, a.v.fprefix[q], a.v.colprefix[q]) - (uint64_t)FBS * rprefix[q];
+    if (q == a.v.nown) {
+        if (l == 0) rp[(size_t)a.v.nown * FBS] = (int64_t)start;
         return;
     }
-    const CondFace &r = a.faces[q];
+    const CondFace &r = a.v.faces[q];
     const int32_t cA = r.cA, cB = r.cB;
     const bool hasA = cA >= 0, hasB = cB >= 0;
     const bool keepA = hasA && a.in_A[cA] == 0, keepB = hasB && a.in_A[cB] == 0;
     const int nkeep = (int)keepA + (int)keepB, ncol = r.ncol;
     const int R = nkeep + ncol * FBS;
-    const int rowA = 1 + (r.rows & 3) * FBS, rowB = 1 + ((r.rows >> 2) & 3) * FBS;
+    const int rowA = 1 + (int)frows_A(r.rows) * FBS, rowB = 1 + (int)frows_B(r.rows) * FBS;
     const double *LA = a.lc + (size_t)(hasA ? cA : 0) * (MS * MS), *LB = a.lc + (size_t)(hasB ? cB : 0) * (MS * MS);
     for (int e = l; e < FBS * R; e += G) {
         const int k = e / R, jj = e - k * R;
@@ -159,10 +143,10 @@ __global__ __launch_bounds__(256) void obstacle_csr_faces_kernel(ObstacleCsrArgs
         } else {
             const int s = (jj - nkeep) / FBS, kp = (jj - nkeep) % FBS;
             const uint32_t code = r.code[s];
-            const bool useA = (code & 4u) != 0, useB = (code & 32u) != 0;
+            const bool useA = (code & FCODE_HAS_A) != 0, useB = (code & FCODE_HAS_B) != 0;
             col = (int32_t)(a.num_I + (uint64_t)r.colcomp[s] * FBS + kp);
-            const double va = useA ? LA[(size_t)(1 + (code & 3u) * FBS + kp) * MS + rowA + k] : 0.0;
-            const double vb = useB ? LB[(size_t)(1 + ((code >> 3) & 3u) * FBS + kp) * MS + rowB + k] : 0.0;
+            const double va = useA ? LA[(size_t)(1 + fcode_lf_A(code) * FBS + kp) * MS + rowA + k] : 0.0;
+            const double vb = useB ? LB[(size_t)(1 + fcode_lf_B(code) * FBS + kp) * MS + rowB + k] : 0.0;
             v = useA && useB ? va + vb : (useA ? va : vb);         // two addends: the face's own block
         }
         a.colind[start + e] = col;
@@ -182,7 +166,7 @@ __global__ __launch_bounds__(256) void obstacle_csr_faces_kernel(ObstacleCsrArgs
                 obstacle_known<FBS>(a, (uint32_t)cB, kcol, dd);
                 b += obstacle_rhs_row(LB, MS, 1, rowB + l, true, kcol, dd, a.gamma[cB], nullptr);
             }
-            a.RHS[(size_t)a.ncells + (size_t)q * FBS + l] = b;
+            a.RHS[(size_t)a.v.ncells + (size_t)q * FBS + l] = b;
         }
     }
 }
@@ -191,9 +175,9 @@ template <int FBS>
 static hipError_t obstacle_csr_fill_t(hipStream_t stream, const ObstacleCsrArgs &a, const uint32_t *rprefix)
 {
     constexpr size_t GC = 1 + 4 * FBS < 16 ? 16 : 32, GF = FBS == 1 ? 16 : FBS == 2 ? 32 : 64;
-    if (a.ncells > 0)
-        hipLaunchKernelGGL((obstacle_csr_cells_kernel<FBS>), dim3(blocks_for((size_t)a.ncells * GC)), dim3(256), 0, stream, a);
-    hipLaunchKernelGGL((obstacle_csr_faces_kernel<FBS>), dim3(blocks_for(((size_t)a.nown + 1) * GF)), dim3(256), 0, stream, a, rprefix);
+    if (a.v.ncells > 0)
+        hipLaunchKernelGGL((obstacle_csr_cells_kernel<FBS>), dim3(blocks_for((size_t)a.v.ncells * GC)), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL((obstacle_csr_faces_kernel<FBS>), dim3(blocks_for(((size_t)a.v.nown + 1) * GF)), dim3(256), 0, stream, a, rprefix);
     return hipGetLastError();
 }
 
@@ -202,13 +186,13 @@ hipError_t obstacle_csr_assemble(hipStream_t stream, int fbs, const ObstacleCsrA
     if (fbs < 1 || fbs > 4) return hipErrorInvalidValue;
     DeviceTmp tmp(stream);
     uint32_t *removed = nullptr, *rprefix = nullptr;
-    if (!tmp.alloc(&removed, (size_t)args.nown + 1) || !tmp.alloc(&rprefix, (size_t)args.nown + 1)) return tmp.error();
-    hipLaunchKernelGGL(obstacle_removed_kernel, dim3(blocks_for((size_t)args.nown + 1)), dim3(256), 0, stream, args.nown, args.lean,
+    if (!tmp.alloc(&removed, (size_t)args.v.nown + 1) || !tmp.alloc(&rprefix, (size_t)args.v.nown + 1)) return tmp.error();
+    hipLaunchKernelGGL(obstacle_removed_kernel, dim3(blocks_for((size_t)args.v.nown + 1)), dim3(256), 0, stream, args.v.nown, args.v.lean,
                        args.in_A, removed);
     if (!tmp.ok(hipGetLastError())) return tmp.error();
-    if (exclusive_scan_with_total<uint32_t>(stream, removed, rprefix, (size_t)args.nown + 1, tmp, nullptr) != hipSuccess) return tmp.error();
+    if (exclusive_scan_with_total<uint32_t>(stream, removed, rprefix, (size_t)args.v.nown + 1, tmp, nullptr) != hipSuccess) return tmp.error();
     uint32_t total = 0;
-    if (!tmp.ok(hipMemcpyAsync(&total, rprefix + args.nown, sizeof(uint32_t), hipMemcpyDeviceToHost, stream))) return tmp.error();
+    if (!tmp.ok(hipMemcpyAsync(&total, rprefix + args.v.nown, sizeof(uint32_t), hipMemcpyDeviceToHost, stream))) return tmp.error();
     const hipError_t e = fbs == 1 ? obstacle_csr_fill_t<1>(stream, args, rprefix) : fbs == 2 ? obstacle_csr_fill_t<2>(stream, args, rprefix)
                        : fbs == 3 ? obstacle_csr_fill_t<3>(stream, args, rprefix) : obstacle_csr_fill_t<4>(stream, args, rprefix);
     if (!tmp.ok(e)) return tmp.error();

@@ -1,25 +1,18 @@
 // obstacle_csr.hpp -- host entry point of obstacle_csr.hip: obstacle_assembler's system (hho.hpp:609-695, :746-750) for cell
-// degree 0, built directly in CSR from the face adjacency tables of condensed.hpp and the prefix counts of assembler_csr.hpp.
+// degree 0, built directly in CSR from the tables of face_system.hpp (a FaceSystemView).
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "condensed.hpp"
+#include "face_system.hpp"
 
 namespace pa {
 
 struct ObstacleCsrArgs {
-    // the mesh and the symbolic tables of the plain assembler's system (whole-mesh context)
-    const uint32_t *cell_faces;
-    const int32_t *face_compress;
-    const CondFace *faces;             // nown records
-    const CondFaceLean *lean;
-    const uint32_t *colprefix;         // nown + 1: column faces of the faces before q
-    const uint32_t *cprefix;           // ncells + 1: non-Dirichlet faces of the cells before c
-    const uint32_t *fprefix;           // nown + 1: cells of the faces before q
-    uint32_t ncells, nown;
-    uint64_t cell_nnz;                 // entries of all cell rows: ncells + fbs cprefix[ncells]
+    // the mesh and the symbolic tables of the plain assembler's system (whole-mesh context, after asm_prepare)
+    FaceSystemView v;
+    uint64_t cell_nnz;                 // entries of all cell rows: asm_sizes(v, 1, fbs).cell_nnz
     // the active set
     const uint8_t *in_A;
     const int32_t *A_ct, *B_ct;

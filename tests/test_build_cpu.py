@@ -119,3 +119,24 @@ def test_cell_loop_of_the_headline_kernels_stays_within_its_instruction_budget()
         assert tot["mfma"] == mfma, (cfg, dict(tot))
         assert tot["valu64"] + tot["valu"] <= vmax, (cfg, dict(tot))
         assert tot["lds"] <= ldsmax, (cfg, dict(tot))
+
+
+def test_face_descriptor_packs_and_unpacks_every_field_on_the_host():
+    """The bit layout of CondFaceLean::packed and of a column-face code lives in proton_amd/csrc/face_system.hpp alone; three
+    assemblers read it through that header's accessors.  tests/cpp/face_descriptor_check.cpp, compiled for the host only, packs
+    every value of every field (seven 6-bit codes, rows, ncol, the Dirichlet flag) with all other fields zero and with all other
+    fields all-ones, and requires every field back unchanged, bits 50-63 clear and a 16-byte record."""
+    import shutil
+    import subprocess
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    out_dir = os.path.join(ROOT, "tests", "cpp", "build")
+    os.makedirs(out_dir, exist_ok=True)
+    exe = os.path.join(out_dir, "face_descriptor_check")
+    cmd = [hipcc, "-x", "hip", "--cuda-host-only", "-O1", "-std=c++17", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "proton_amd", "csrc"),
+           os.path.join(ROOT, "tests", "cpp", "face_descriptor_check.cpp"), "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    packs = 2 * (7 * 64 + 16 + 8 + 2)
+    assert r.stdout.strip() == "packs %d ok" % packs, r.stdout
