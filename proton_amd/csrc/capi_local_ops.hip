@@ -91,32 +91,26 @@ int run_local_ops(pa_context *ctx, pa_degree_info di, int quad_kind, int stab_ki
         PA_HIP(ctx, e->launch_small(sa, ctx->stream));
         return PA_OK;
     }
-    // Kernels that take the per-cell head from the pre-pass run in pieces of at most `piece` cells: pre-pass of a
-    // piece into the context's record buffer, then the cooperative kernel over the same cells (same stream).
+    // The cooperative kernel takes the per-cell head from the pre-pass and runs in pieces of at most `piece` cells: pre-pass
+    // of a piece into the context's record buffer, then the cooperative kernel over the same cells (same stream).
     size_t piece = n;
-    if (e->launch_pre && e->self_pre) {
-        // the cooperative kernel forms the records itself: one ring of 64 records per block of the (persistent) grid, one launch
-        const size_t need = (size_t)grid * 64 * (size_t)e->pre_doubles;
-        PA_HIP(ctx, ctx->records.pre.grow(need, ctx->stream));
-    } else if (e->launch_pre) {
-        size_t cap_bytes = ctx->records.cap_bytes;                            // (pa_context_set_record_cap; default 4 GiB)
-        const size_t per_cell = (size_t)e->pre_doubles * sizeof(double);
-        size_t max_cells = (cap_bytes / per_cell) & ~(size_t)4095;
-        // Pieces of at most PA_PIECE_CELLS cells by default: the records of a piece (134 MB at k = 2, 255 MB at k = 3) are then
-        // still in the Infinity Cache when the cooperative kernel reads them, and the next piece's overwrite them there --
-        // measured on 1024 x 1024 cells against one piece: 0.53 -> 0.46 ms at k = 1, 1.35 -> 1.27 ms at k = 2, 2.70 -> 2.44 ms at
-        // k = 3, 11.1 -> 9.8 ms on 2048 x 2048 at k = 3 (tools/slab_timing.py; 96 Ki ... 256 Ki cells per piece within 2 %)
-        // (not in the condensed mode, which writes 720 B per cell instead of 3.9 KB and is not short of HBM bandwidth: there the
-        // extra launches and tails cost 2-8 %)
-        if (!o.cond && max_cells > PA_PIECE_CELLS) max_cells = PA_PIECE_CELLS;
-        if (max_cells < 4096) max_cells = 4096;
-        if (piece > max_cells) {                                          // equal pieces, whole multiples of 4096 cells
-            const size_t npieces = (n + max_cells - 1) / max_cells;
-            piece = (((n + npieces - 1) / npieces) + 4095) & ~(size_t)4095;
-        }
-        const size_t need = ((piece + 7) / 8) * 8 * (size_t)e->pre_doubles;      // whole tiles of 8 records
-        PA_HIP(ctx, ctx->records.pre.grow(need, ctx->stream));
+    size_t cap_bytes = ctx->records.cap_bytes;                            // (pa_context_set_record_cap; default 4 GiB)
+    const size_t per_cell = (size_t)e->pre_doubles * sizeof(double);
+    size_t max_cells = (cap_bytes / per_cell) & ~(size_t)4095;
+    // Pieces of at most PA_PIECE_CELLS cells by default: the records of a piece (134 MB at k = 2, 255 MB at k = 3) are then
+    // still in the Infinity Cache when the cooperative kernel reads them, and the next piece's overwrite them there --
+    // measured on 1024 x 1024 cells against one piece: 0.53 -> 0.46 ms at k = 1, 1.35 -> 1.27 ms at k = 2, 2.70 -> 2.44 ms at
+    // k = 3, 11.1 -> 9.8 ms on 2048 x 2048 at k = 3 (tools/slab_timing.py; 96 Ki ... 256 Ki cells per piece within 2 %)
+    // (not in the condensed mode, which writes 720 B per cell instead of 3.9 KB and is not short of HBM bandwidth: there the
+    // extra launches and tails cost 2-8 %)
+    if (!o.cond && max_cells > PA_PIECE_CELLS) max_cells = PA_PIECE_CELLS;
+    if (max_cells < 4096) max_cells = 4096;
+    if (piece > max_cells) {                                          // equal pieces, whole multiples of 4096 cells
+        const size_t npieces = (n + max_cells - 1) / max_cells;
+        piece = (((n + npieces - 1) / npieces) + 4095) & ~(size_t)4095;
     }
+    const size_t need = ((piece + 7) / 8) * 8 * (size_t)e->pre_doubles;      // whole tiles of 8 records
+    PA_HIP(ctx, ctx->records.pre.grow(need, ctx->stream));
     pa_sizes sz;
     (void)pa_sizes_for(di, quad_kind, &sz);
     const size_t mm = (size_t)sz.msize * (size_t)sz.msize, opn = (size_t)sz.oper_rows * (size_t)sz.msize;
@@ -131,17 +125,12 @@ int run_local_ops(pa_context *ctx, pa_degree_info di, int quad_kind, int stab_ki
         pa::LocalOpsArgs a;
         a.tab = ctx->tab.get(); a.points = ctx->mesh.points; a.ptids = ctx->mesh.ptids;
         a.first = first + off; a.n = m;
-        a.pre = nullptr;
         a.pre_ring = nullptr;
-        if (e->launch_pre && e->self_pre) {
-            a.pre_ring = ctx->records.pre.get();
-        } else if (e->launch_pre) {
-            pa::PreArgs pa_;
-            pa_.tab = ctx->tab.get(); pa_.points = ctx->mesh.points; pa_.ptids = ctx->mesh.ptids;
-            pa_.first = first + off; pa_.n = m; pa_.pre = ctx->records.pre.get();
-            PA_HIP(ctx, e->launch_pre(pa_, ctx->stream));
-            a.pre = ctx->records.pre.get();
-        }
+        pa::PreArgs pa_;
+        pa_.tab = ctx->tab.get(); pa_.points = ctx->mesh.points; pa_.ptids = ctx->mesh.ptids;
+        pa_.first = first + off; pa_.n = m; pa_.pre = ctx->records.pre.get();
+        PA_HIP(ctx, e->launch_pre(pa_, ctx->stream));
+        a.pre = ctx->records.pre.get();
         a.oper = d_oper ? d_oper + off * opn : nullptr;
         a.data = d_data ? d_data + off * mm : nullptr;
         a.stab = d_stab ? d_stab + off * mm : nullptr;

@@ -12,16 +12,17 @@
 // HOW is not the reference's.  The path is two kernels: the per-cell head -- geometry, cell quadrature, moments,
 // stiffness, Cholesky of gr_lhs (and the mass rows / factor of the dense fancy form) -- runs one THREAD per cell
 // (hho_pre.hpp) and hands a small record per cell to the kernel of this file, in which G lanes of a 64-wide
-// wavefront cooperate on one cell (a -DPA_USE_PRE=0 build keeps the head in this kernel: stages S0-S4 below):
+// wavefront cooperate on one cell:
 //   * the cell basis is a set of scaled monomials, so every cell integral of phi_i phi_j or
 //     grad phi_i . grad phi_j is a *moment*  sum_q w_q bx_q^p by_q^r  of the same quadrature
-//     rule: P2(2 recdeg) moments are accumulated and the stiffness / mass
-//     matrices are gathered from them -- term by term the same sums the reference forms;
+//     rule: the pre-pass accumulates P2(2 recdeg) moments and gathers the stiffness / mass matrices from them -- term
+//     by term the same sums the reference forms; the moments the cell columns of gr_rhs need travel with the record;
 //   * the face basis evaluated at the face Gauss points is t_q^k exactly, so every face mass
 //     matrix is (|F|/2) M^ with one constant factorization shared by all faces of all cells;
 //   * lane c of a cell owns COLUMN c of every msize-wide matrix (gr_rhs, Y, oper, T, U): uniform
 //     loops, broadcast LDS reads, no per-entry index arithmetic;
-//   * data = gr_rhs^T (L L^T)^-1 gr_rhs = Y^T Y with Y = L^-1 gr_rhs (forward substitution only);
+//   * data = gr_rhs^T (L L^T)^-1 gr_rhs = Y^T Y with Y = L^-1 gr_rhs (forward substitution only), the packed factor
+//     in registers and broadcast through DPP operands (the dense fancy instances read an LDS image of it);
 //   * stab = (1/h) sum_F B_F^T M_F B_F = U^T U with U_F = sqrt(|F|/2h) L^^T B_F, where
 //     B_F = M_F^-1 T_F - E_F is the reference's proj2 + proj3 (hho.hpp:222-231); T_F = [trace_F | 0]
 //     for the naive stabilization and for the fancy one when celdeg == recdeg (then
@@ -30,172 +31,33 @@
 //     asked for (one LDS read per lane feeds 16 FMAs), accumulators to HBM directly or through an LDS image;
 //     each lane forming the entries (c, c+d mod msize), d = 0..msize/2, with vector FMAs when data and stab
 //     are wanted apart;
+//   * the condensed and the assembling mode keep the image on the chip: the cell unknowns are eliminated in it, or its
+//     entries go straight to the CSR arrays of the global system;
 //   * the block's one wavefront synchronises on its LDS data with wave_sync() (no wait for outstanding
 //     stores), and the next cell's record is in flight while the current cell is processed;
 //   * reciprocals and square roots are v_rcp/v_rsq seeds refined by Newton steps (<= 1 ulp).
+//
+// Design choices that were measured and settled are not switches here: DESIGN.md section 6 lists what was tried, the
+// figure, and the commit that last held the code.  A switch lives in this header only while its question is open.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "hho_asm_scatter.hpp"
 
+// Per-instance settings of the build (proton_amd/_build.py):
 // minimum waves per SIMD the register allocator must leave room for (2nd __launch_bounds__
 // argument); 0 = per configuration (Cfg::WAVES)
 #ifndef PA_WAVES_PER_EU
 #define PA_WAVES_PER_EU 0
 #endif
-// 1: the per-cell head (geometry, cell quadrature, moments, stiffness, Cholesky of gr_lhs) comes from the
-// one-thread-per-cell pre-pass of hho_pre.hpp; 0: the cooperative kernel computes it itself (A/B builds)
-// the same for the condensed-mode instance (0 = as the local-operator kernel)
-#ifndef PA_COND_WAVES_PER_EU
-#define PA_COND_WAVES_PER_EU 0
-#endif
-#ifndef PA_USE_PRE
-#define PA_USE_PRE 1
-#endif
-
-// A/B switches of measured design choices; the defaults are what ships:
 // msize from which the lc-only kernel stores its accumulators straight to HBM instead of through an LDS image
 #ifndef PA_DIRECT_MIN
 #define PA_DIRECT_MIN 14
 #endif
-// 1: lc = Z^T Z with vector FMAs also when only lc is wanted (the matrix pipe is 15 ... 50 % faster)
-#ifndef PA_LC_VALU
-#define PA_LC_VALU 0
-#endif
-// bottom-right tile of Z^T Z (msize 17..24) on the vector pipe
-#ifndef PA_CORNER_VALU
-#define PA_CORNER_VALU 1
-#endif
-// cell part of U formed by (face, column) units instead of by the column owners
-#ifndef PA_UNIT_U
-#define PA_UNIT_U 1
-#endif
-// dense fancy instances (celdeg != recdeg) take mass rows + chol(M1) from the pre-pass record
-#ifndef PA_PRE_DENSE
-#define PA_PRE_DENSE 1
-#endif
-// k = 3 class: cell columns of gr_rhs on the matrix pipe
-#ifndef PA_GRC_MFMA
-#define PA_GRC_MFMA 1
-#endif
-// ... from this many rows of gr_lhs on (14 at k = 3; the 9 of k = 2 measured slower: see DESIGN.md section 6)
-#ifndef PA_GRC_MFMA_MIN_NR
-#define PA_GRC_MFMA_MIN_NR 12
-#endif
-// cell columns of gr_rhs from the cell moments (divergence theorem) instead of the face-point tables
-#ifndef PA_LAPG
-#define PA_LAPG 1
-#endif
-// face-basis constants of a lane selected per pass from uniform tables instead of held in registers (fbs <= 3)
-#ifndef PA_FACE_SEL
-#define PA_FACE_SEL 0
-#endif
-// corner tile of Z^T Z: U term in closed form, only the Y rows read
-#ifndef PA_CORNER_SHORT
-#define PA_CORNER_SHORT 1
-#endif
-// face columns of gr_rhs: the whole table of the face read before the products (k <= 2)
-#ifndef PA_S3B_BATCH
-#define PA_S3B_BATCH 1
-#endif
-// forward substitution Y = L^-1 gr_rhs: doubles of L read per LDS round trip (0: row by row)
+// forward substitution Y = L^-1 gr_rhs from the LDS image of L: doubles of L read per LDS round trip (0: row by row)
 #ifndef PA_FWD_CAP
 #define PA_FWD_CAP 24
-#endif
-// rows of U ordered so that the second column tile of Z^T Z needs fewer k-steps (see Cfg::UPERM)
-#ifndef PA_UPERM
-#define PA_UPERM 1
-#endif
-// forward / backward substitution with L in registers, broadcast by DPP (see Cfg::DPPFWD)
-#ifndef PA_DPPFWD
-#define PA_DPPFWD 1
-#endif
-// lc through the LDS image: each cell's image stored as soon as it is complete, all 64 lanes on it (measured: +-1 %, off)
-#ifndef PA_EARLY_OUT
-#define PA_EARLY_OUT 0
-#endif
-// condensed mode: the elimination chain in registers with DPP broadcasts of the pivot row (see hho_local_ops_kernel, S9)
-#ifndef PA_COND_DPP
-#define PA_COND_DPP 1
-#endif
-// condensed mode: region P outside the image of S9 (more LDS, the record deposit where the other modes have it)
-#ifndef PA_COND_OWN_P
-#define PA_COND_OWN_P 1
-#endif
-// blocks of one XCD (blockIdx mod 8) take consecutive cells
-#ifndef PA_XCD_MAP
-#define PA_XCD_MAP 1
-#endif
-// condensed mode: pivots per LDS round trip of the partial factorization (1 = the unblocked chain)
-#ifndef PA_COND_NB
-#define PA_COND_NB 1
-#endif
-// condensed mode: face count from which the Schur complement A_FF - W^T W is formed on the matrix pipe
-#ifndef PA_COND_SCHUR_MFMA_MIN
-#define PA_COND_SCHUR_MFMA_MIN 12
-#endif
-// the per-cell opaque lane index is masked to its range, so that index arithmetic uses 24-bit multiplies
-#ifndef PA_LANE_RANGE
-#define PA_LANE_RANGE 1
-#endif
-// matrix-pipe product: no select on the operand of lanes beyond the last column of Z (they feed entries that are never stored)
-#ifndef PA_ZCOL_NOSEL
-#define PA_ZCOL_NOSEL 1
-#endif
-// lc through the LDS image: columns of Z permuted in the tiles so that a lane's accumulators are four consecutive rows (16-byte image writes)
-#ifndef PA_ACC_PERM
-#define PA_ACC_PERM 1
-#endif
-// two column tiles without the vector-pipe corner (msize 25..32): tile (1,1) of Z^T Z holds face columns only -- its U term in closed form,
-// its matrix instructions stop after the rows of Y
-#ifndef PA_T11_SHORT
-#define PA_T11_SHORT 1
-#endif
-// condensed mode: number of pivots from which the elimination chain runs in its right-looking form (see cond_dpp_chain_rl;
-// measured: -2.5 % at the 15 pivots of k = 3, +-0.5 % at the 10 of k = 2 and the 6 of k = 1)
-#ifndef PA_COND_RL_MIN
-#define PA_COND_RL_MIN 12
-#endif
-// 8-byte LDS reads of the product's operands and of the unit form of U kept single (volatile): no ds_read2_b64
-#ifndef PA_LDS_NOPAIR
-#define PA_LDS_NOPAIR 0
-#endif
-// S1 with the pre-pass: TWO lanes per face point -- one forms its row of scaled monomials, the other its row of weighted normal
-// derivatives -- and ONE common run of LDS stores (a store instruction costs its 6 ... 13 cycles of the store path whatever the
-// number of active lanes: 5 instead of 10 of them per pass at k = 2)
-#ifndef PA_S1_SPLIT
-#define PA_S1_SPLIT 1
-#endif
-// 1: no separate pre-pass kernel and no record array of the whole piece: every 64 / CPW passes a wavefront of the cooperative
-// kernel forms the heads of the 64 cells it visits next itself -- one cell per lane, the thread-per-cell code of hho_pre.hpp -- into a
-// ring of 64 records of its own in global memory (45 KB at k = 2: written and read back by the same compute unit within ~0.2 ms), and
-// reads them from there as before (per instance: proton_amd/_build.py)
-// Wavefront priority by stage (s_setprio 0..3): a wavefront raises its issue priority as it moves through a pass -- head 0, cell
-// columns of gr_rhs (S3b) 1, substitutions and the face part (S4..S6) 2, product + output (S7/S8, and the elimination of the
-// condensed mode) 3 -- so that of the three wavefronts of a SIMD the one closest to its stores wins the issue slot: the stores of
-// a pass go out earlier and the wavefronts of a SIMD drift apart in phase instead of queueing for the same pipe in the same stage.
-// Measured (A/B of tagged builds, 5 rounds each in one call, kernels of 1024 x 1024 cells): k = 2 L 1.204 -> 1.143 ms, k = 1 L
-// 0.438 -> 0.424, k = 3 L 2.470 -> 2.380, k = 2 C (rhs + operators + fill) 2.21 -> 2.05; out 3 alone 1.175 / 0.429 / 2.399; out 3
-// + substitutions 1: 1.160 / 0.424 / 2.395; the reverse (head 3, out 0) 1.202 / 0.433 / 2.483 against 1.212 / 0.440 / 2.513.
-// PA_PRIO_OUT = -1: no s_setprio at all (the kernels of rounds 1-2).
-#ifndef PA_PRIO_OUT
-#define PA_PRIO_OUT 3
-#endif
-#ifndef PA_PRIO_HEAD
-#define PA_PRIO_HEAD 0
-#endif
-#ifndef PA_PRIO_S3B      /* from S3b (cell columns of gr_rhs) on; -1: as the head */
-#define PA_PRIO_S3B 1
-#endif
-#ifndef PA_PRIO_MID      /* from S4 (substitutions) on; -1: as the stage before */
-#define PA_PRIO_MID 2
-#endif
-#ifndef PA_PRIO_S6       /* from S6 (face part of U, Z complete) on; -1: as the stage before */
-#define PA_PRIO_S6 -1
-#endif
-#ifndef PA_SELF_PRE
-#define PA_SELF_PRE 0
 #endif
 #ifdef PA_MARKERS
 #define PA_MARK(x) asm volatile("; PAMARK " x)
@@ -214,6 +76,20 @@ namespace pa {
 
 enum { QUAD_TENSOR = 0, QUAD_FAN = 1 };
 enum { STAB_NONE = 0, STAB_NAIVE = 1, STAB_FANCY = 2 };
+
+// Wavefront priority by stage (s_setprio): a wavefront raises its issue priority as it moves through a pass, so that of the
+// wavefronts of a SIMD the one closest to its stores wins the issue slot -- the stores of a pass go out earlier, and the
+// wavefronts drift apart in phase instead of queueing for the same pipe in the same stage.
+constexpr int PRIO_HEAD = 0;      // S0 - S3: the record's scalars, the face-point tables
+constexpr int PRIO_S3B = 1;       // S3b: columns of gr_rhs
+constexpr int PRIO_MID = 2;       // S4 - S6: substitutions, U
+constexpr int PRIO_OUT = 3;       // S7 - S9: product, output, elimination / scatter of the condensed and assembling modes
+// condensed mode: number of pivots (cbs) from which the elimination chain runs right-looking (cond_dpp_chain_rl): shorter
+// dependent path per step, worth it only on the 15 pivots of k = 3
+constexpr int COND_RL_MIN = 12;
+// condensed mode: face unknowns (4 fbs) from which the Schur complement A_FF - W^T W is one tile of the matrix pipe; below
+// (k <= 1) the tile would be more than half empty
+constexpr int COND_SCHUR_MFMA_MIN = 12;
 
 // Quadrature tables, filled by the host (quad_tables.hpp) and passed by device pointer:
 //   gauss_*[n][i]: the n-node rule of gauss_legendre() in the reference's emission order;
@@ -264,41 +140,29 @@ struct Cfg {
     static constexpr bool GENERAL_FANCY = FANCY && CD != RD;  // T_F is dense; otherwise T_F = [trace_F | 0]
     // The per-cell head is taken from the pre-pass (hho_pre.hpp); for the dense fancy form its record also carries the
     // rows of the cell mass matrix and the Cholesky factor of its leading block (hho.hpp:173-190).
-    static constexpr bool USE_PRE = PA_USE_PRE && (PA_PRE_DENSE || !GENERAL_FANCY);
     // Cell columns of gr_rhs (hho.hpp:64-85): stiff[i, c] - sum_F int_F (grad phi_i . n) phi_c = -int_T phi_c lap(phi_i)
     // (divergence theorem; both quadratures of the reference are exact for these integrands), i.e. 0, 1 or 2 cell
     // moments of degree <= recdeg - 2 + celdeg with integer coefficients.  The moments travel with the record.
-    static constexpr bool LAPG = USE_PRE && PA_LAPG;
     static constexpr int DG = RD - 2 + CD;                    // highest moment degree that is needed
-    static constexpr int NMG = (LAPG && RD >= 2) ? P2(DG) : 0, NMGP = (NMG + 1) & ~1;
+    static constexpr int NMG = RD >= 2 ? P2(DG) : 0, NMGP = (NMG + 1) & ~1;
     // Every lane of a cell reads the SAME element of L in every step of the substitutions Y = L^-1 gr_rhs and L^-T Y: as LDS
     // reads that is a 16-byte broadcast per two FMAs, a quarter of the kernel's LDS cycles at k = 3 -- and the LDS pipeline is
     // its busiest unit.  Instead the packed factor (and the reciprocal diagonal) sits in registers, element e in lane e mod 16 of
     // each row of 16 lanes (ceil((NL + NR) / 16) doubles per lane, one 8-byte LDS read each), and the FMAs take it through the
     // DPP operand  v_fmac_f64_dpp ... row_newbcast:n  (gfx90a+: lane n of the row of 16, for 64-bit operands).  No image of L.
-    static constexpr bool DPPFWD = LAPG && !GENERAL_FANCY && PA_DPPFWD;
-    static constexpr int NQB = USE_PRE ? 0 : NQ;              // cell points evaluated by THIS kernel
-    static constexpr int NP = NQB + NFP;
-    static constexpr int NPW = 2 * RD + 1;                    // powers 0..2 recdeg
+    // The dense fancy instances keep an LDS image of L (batched reads, lds_forward_rd_batched).
+    static constexpr bool DPPFWD = !GENERAL_FANCY;
+    static constexpr int NPW = 2 * RD + 1;                    // powers 0..2 recdeg (the head: hho_pre.hpp, hho_small.hpp)
     static constexpr int NMOM = P2(2 * RD);
     static constexpr int CPW = 64 / G;                        // cells per wavefront
-    static constexpr int PPL = cdiv(NP, G);                   // evaluation points per lane
-    static constexpr int MPL = cdiv(NMOM, G);                 // moments per lane
-    static constexpr int NSYM = RBS * (RBS + 1) / 2;          // stiffness is symmetric: packed lower triangle
-    static constexpr int SPL = cdiv(NSYM, G);                 // stiffness entries per lane
+    static constexpr int PPL = cdiv(NFP, G);                  // face points per lane (S1)
     static constexpr int ND = MS / 2 + 1;                     // rotations of the symmetric update
     // register budget: the k = 3 kernels need > 168 VGPRs to run without spills (measured: 2 waves/SIMD
     // without spills beat 3 with), the others fit 3 waves/SIMD
     // (the dense fancy form carries the mass factor and the dense T_F as well: one step lower, or it spills by the hundred)
-    static constexpr bool DENSE_FANCY = STAB_ == STAB_FANCY && CD_ != FD_ + 1;
-#ifdef PA_WAVES_OVERRIDE      /* A/B builds: beats the per-instance setting of _build.py */
-    static constexpr int WAVES_LC = PA_WAVES_OVERRIDE;
-#else
-    static constexpr int WAVES_LC = PA_WAVES_PER_EU ? PA_WAVES_PER_EU
-                                 : DENSE_FANCY ? ((MS > 24 || RBS > 10) ? 1 : (MS > 16 || RBS > 6) ? 2 : (CBS <= 1 ? 4 : 3))      /* (cell degree 0 -- the obstacle pair (0,1): 120 registers --: 4 against 3 waves: -5 % lc, -17 % condensed; (1,1) spills at 4) */
-                                               : ((MS > 24 || RBS > 10) ? 2 : 3);
-#endif
-    static constexpr int WAVES = (COND_ != 0 && PA_COND_WAVES_PER_EU) ? PA_COND_WAVES_PER_EU : WAVES_LC;
+    static constexpr int WAVES = PA_WAVES_PER_EU ? PA_WAVES_PER_EU
+                              : GENERAL_FANCY ? ((MS > 24 || RBS > 10) ? 1 : (MS > 16 || RBS > 6) ? 2 : (CBS <= 1 ? 4 : 3))      /* (cell degree 0 -- the obstacle pair (0,1): 120 registers --: 4 against 3 waves: -5 % lc, -17 % condensed; (1,1) spills at 4) */
+                                            : ((MS > 24 || RBS > 10) ? 2 : 3);
     static constexpr bool HAS_STAB = STAB != STAB_NONE;
     // lc-only path: accumulators -> HBM directly (no LDS image) where the matrix is big enough for the
     // 128-byte runs to pay (measured: -5 % at msize 14, -2 % at 22, -1 % at 31, but +19 % at msize 9)
@@ -306,12 +170,12 @@ struct Cfg {
     // msize 17..24: the bottom-right tile of Z^T Z holds at most 8 x 8 useful entries and would cost the matrix pipe as
     // much as a full one -> vector FMAs, one lane per unordered pair of its columns
     static constexpr int NCORNER = CBS + 4 * FBS - 16;
-    static constexpr bool CORNER_VALU = PA_CORNER_VALU && NCORNER > 0 && NCORNER <= 8 && NCORNER * (NCORNER + 1) / 2 <= G;
+    static constexpr bool CORNER_VALU = NCORNER > 0 && NCORNER <= 8 && NCORNER * (NCORNER + 1) / 2 <= G;
 
     // lc with T_F = [trace_F | 0] and 17..32 columns: the second column tile holds face columns only, of the faces UF1..3,
     // and the U rows of the other faces are zero in it.  With the rows of those faces FIRST behind Y (a permutation of the
     // rows of Z does not change Z^T Z) the products of that tile stop after the Y rows and theirs: KS1 k-steps instead of KS.
-    static constexpr bool UPERM = PA_UPERM && HAS_STAB && !GENERAL_FANCY && PA_UNIT_U && CBS <= 16 && CBS + 4 * FBS > 16 && CBS + 4 * FBS <= 32;
+    static constexpr bool UPERM = HAS_STAB && !GENERAL_FANCY && CBS <= 16 && CBS + 4 * FBS > 16 && CBS + 4 * FBS <= 32;
     static constexpr int UF1 = UPERM ? (16 - CBS) / FBS : 0;
     static constexpr int KS1 = cdiv(((RBS - 1 + 1) & ~1) + (4 - UF1) * FBS, 4);
     // ---- record of a cell written by the pre-pass (doubles): packed lower triangle of L = chol(gr_lhs), row-major,
@@ -320,7 +184,7 @@ struct Cfg {
     struct Pre {
         static constexpr int NL = (RBS - 1) * RBS / 2;
         static constexpr int oSCAL = (NL + (RBS - 1) + 1) & ~1;
-        static constexpr int NSCAL = 18 + NMGP;               // ([17]: pivot status of the mass factor; [18..]: moments, LAPG)
+        static constexpr int NSCAL = 18 + NMGP;               // ([17]: pivot status of the mass factor; [18..]: the NMG moments)
         // dense fancy form only: rows i < CBS of the cell mass matrix, [j][i]; packed chol(M1), true diagonal; 1/diagonal
         static constexpr int oMR = oSCAL + NSCAL, NMR = GENERAL_FANCY ? CBS * RBS : 0;
         static constexpr int oMC = oMR + NMR, NMC = GENERAL_FANCY ? CBS * (CBS + 1) / 2 : 0;
@@ -329,9 +193,6 @@ struct Cfg {
         static constexpr int NP2 = NPRE / 2;                  // 16-byte pairs
     };
     static constexpr int PLC = cdiv(Pre::NP2, G);             // pairs of the record per lane
-    // the wavefront produces the records it consumes (see PA_SELF_PRE): SELF_IT passes per batch of 64 cells
-    static constexpr bool SELF_PRE = USE_PRE && PA_SELF_PRE;
-    static constexpr int SELF_IT = 64 / (64 / G);
 
     // ---- LDS map (doubles, per cell).  Every vector that is read as a contiguous run starts at
     // an even offset and has an even stride, so the reads are 16-byte ds_read_b128.
@@ -342,68 +203,42 @@ struct Cfg {
     static constexpr int LD = (((RBS + 1) & ~1) % 4 == 0 && RBS > 10) ? ((RBS + 1) & ~1) + 2 : ((RBS + 1) & ~1);
     static constexpr int ZR = NRP + (HAS_STAB ? NF : 0);      // rows of Z = [Y; pad; U]
     static constexpr int ZS = ((ZR + 1) & ~1) % 4 == 2 ? ((ZR + 1) & ~1) : ((ZR + 1) & ~1) + 2;   // even, ZS/2 odd
-    // region Q: quadrature-point tables and moments -- dead once the gr_rhs columns are in registers
-    // (after S3b); Z = [Y; U] and later the output image reuse it.
-    static constexpr int oWPX = 0;                            // NQ x NPW   w * bx^e
-    static constexpr int oPY = oWPX + NQB * NPW;              // NQ x NPW   by^e
-    static constexpr int oPHF = oPY + NQB * NPW;              // NFP x RBS  phi at face points
+    // region Q: the face-point tables -- dead once the gr_rhs columns are in registers and the trace columns are formed
+    // (after S4b); Z = [Y; U] and later the output image reuse it.
+    static constexpr int oPHF = 0;                            // NFP x RBS  phi at face points
     static constexpr int oDN = (oPHF + NFP * RBS + 1) & ~1;   // NFP x NRP  (w_q/2) (grad phi . edge normal)
-    static constexpr int oMOM = oDN + NFP * NRP;              // NMOM moments
-    static constexpr int endQ0 = oMOM + (USE_PRE ? 0 : NMOM);
-    // gr_rhs cell columns are assembled by SPC lanes each (RPP rows per lane) and meet in GRC, which
-    // lies on the w*bx^e / by^e tables (dead after the moments)
-    // (measured: -1.7 % at k = 2, nothing at k = 3, +1 % with 16 lanes per cell -> only for G = 32)
-    static constexpr int SPC = LAPG ? 1 : G >= 32 ? imin(G / CBS, NR) : 1, RPP = cdiv(NR, SPC < 1 ? 1 : SPC);
-    // (with the pre-pass there are no such tables: GRC follows the face tables)
-    static constexpr int oGRC = USE_PRE ? endQ0 : 0;          // CBS x NRP
-    static constexpr int endQ = endQ0 + (USE_PRE && SPC > 1 ? CBS * NRP : 0);
-    static_assert(USE_PRE || SPC <= 1 || CBS * NRP <= 2 * NQ * NPW, "GRC must fit the dead quadrature tables");
+    static constexpr int endQ = oDN + NFP * NRP;
     static constexpr int oZ = 0;                              // ZS x MS    (written from S5 on)
     static constexpr int oOUT = 0;                            // MS x MS    (written in S8, after the last read of Z)
     // condensed mode: image of the symmetric matrix [lc f_T; f_T^T 0], MS + 1 rows, row-major == column-major; stride
-    // LDI even (16-byte rows) with LDI / 2 odd (the row-per-lane reads touch every bank once).  It lies over regions Q
-    // AND P: nothing of P is needed after S6, and the condensed mode deposits the next cell's record only after S9.
-    // The packed result (upper triangle of S, then g) is staged on the rows of the cell block once they are dead, or
+    // LDI even (16-byte rows) with LDI / 2 odd (the row-per-lane reads touch every bank once).  It lies over region Q
+    // only, which is sized for it: region P keeps its place behind it and takes the next cell's record as soon as S6 is
+    // done, as in the other modes.  The packed result (upper triangle of S, then g) is staged on the rows of the cell block once they are dead, or
     // behind the image where that block is too small (cbs <= 3).
     static constexpr int LDI = ((MS + 1) & ~1) % 4 == 2 ? ((MS + 1) & ~1) : ((MS + 1) & ~1) + 2;
     static constexpr int NSP = NF * (NF + 1) / 2, NCOND = NSP + NF;
     static constexpr int oSTG = CBS * LDI >= NCOND ? 0 : (MS + 1) * LDI;
     static constexpr int condNeed = (MS + 1) * LDI + (CBS * LDI >= NCOND ? 0 : NCOND);
-    // (condensed mode with COND_OWN_P: the image of S9 lies over region Q only, region P keeps its place behind it and
-    // takes the next cell's record as soon as S6 is done, as in the other modes)
-    static constexpr bool COND_OWN_P = COND && PA_COND_OWN_P && USE_PRE;
-    static constexpr int sizeQ = imax(imax(imax(endQ, ZS * MS), MS * MS), COND_OWN_P ? ((condNeed + 1) & ~1) : 0);
-    // region P: lives until the forward substitutions are done.  Stiffness, stride LD; its [1:,1:]
-    // block becomes chol(gr_lhs) row by row: oST is odd so that the block (and every row of it)
-    // starts on a 16-byte boundary
-    static constexpr int oST = sizeQ | 1;
-    static constexpr int oMA = (oST + LD * RBS + 1) & ~1;     // RBS x RBS  mass (general fancy); chol(M1) in place
-    static constexpr int oFTo = oMA + (GENERAL_FANCY ? LD * RBS : 0);    // NF x RBS trace / (|F|/2) (general fancy)
-    static constexpr int oSUo = (oFTo + (GENERAL_FANCY ? NF * RBS : 0) + 1) & ~1;   // 4: sqrt(|F| / 2h)
-    // region P with the pre-pass: the image of L (NR x LD, row-major, true diagonal; the upper triangle and one
-    // more row are zeroed once per kernel and never written again) and the tail of the record as it comes
-    // (reciprocals, scalars), shifted so that the scalars start on a 16-byte boundary
-    // ... with DPPFWD: the record as it comes (packed L, reciprocals, scalars, moments), 16-byte pairs in place
+    static constexpr int sizeQ = imax(imax(imax(endQ, ZS * MS), MS * MS), COND ? ((condNeed + 1) & ~1) : 0);
+    // region P: the cell's record, live until S6 is done.  With DPPFWD the record as it comes (packed L, reciprocals,
+    // scalars, moments), 16-byte pairs in place.  Otherwise the image of L (NR x LD, row-major, true diagonal; the upper
+    // triangle is zeroed once per kernel and never written again) and the tail of the record as it comes (reciprocals,
+    // scalars), shifted so that the scalars start on a 16-byte boundary.
     static constexpr int oREC = (sizeQ + 1) & ~1;
     static constexpr int NLR = cdiv(Pre::NL + (RBS - 1), 16);   // registers of the packed factor + reciprocals
-    static constexpr int oLGp = (sizeQ + 1) & ~1;
-    // (the zero row NR behind the image is what the columns without a stiffness part add; not needed with LAPG)
-    static constexpr int LGR = LAPG ? NR : RBS;               // rows of the image of L
-    static constexpr int oLIN = ((oLGp + LGR * LD + 1) & ~1) + ((Pre::oSCAL - Pre::NL) & 1);
+    static constexpr int oLG = (sizeQ + 1) & ~1;
+    static constexpr int oLIN = ((oLG + NR * LD + 1) & ~1) + ((Pre::oSCAL - Pre::NL) & 1);
     static constexpr int oRCP = DPPFWD ? oREC + Pre::NL : oLIN;      // NR: 1 / L[i][i]
-    static constexpr int oSU = DPPFWD ? oREC + Pre::oSCAL : USE_PRE ? oLIN + (Pre::oSCAL - Pre::NL) : oSUo;
-    static constexpr int oLG = USE_PRE ? oLGp : oST + 1 + LD;  // chol(gr_lhs): stiff[1:,1:] in place without the pre-pass
-    static constexpr int oMG = oSU + 18;                      // NMG moments (LAPG)
-    static constexpr int oDUMMY = oSU + (USE_PRE ? Pre::NSCAL : 4);    // 4: sink of masked-out stores
-    // dense fancy form on the pre-pass: mass rows, image of chol(M1) (row-major, stride LDM), its reciprocals, trace table
+    static constexpr int oSU = DPPFWD ? oREC + Pre::oSCAL : oLIN + (Pre::oSCAL - Pre::NL);
+    static constexpr int oMG = oSU + 18;                      // NMG moments
+    static constexpr int oDUMMY = oSU + Pre::NSCAL;           // 4: sink of masked-out stores
+    // dense fancy form: mass rows, image of chol(M1) (row-major, stride LDM), its reciprocals, trace table
     static constexpr int LDM = (CBS + 1) & ~1;
     static constexpr int oMRl = (oDUMMY + 4 + 1) & ~1;
     static constexpr int oMCl = (oMRl + Pre::NMR + 1) & ~1;
     static constexpr int oMCRl = oMCl + CBS * LDM;
-    static constexpr int oFTp = (oMCRl + CBS + 1) & ~1;
-    static constexpr int oFT = USE_PRE ? oFTp : oFTo;
-    static constexpr int LDS_BASE = (USE_PRE && GENERAL_FANCY) ? ((oFTp + NF * RBS + 1) & ~1) : ((oDUMMY + 4 + 1) & ~1);
-    static constexpr int LDS_PER_CELL = COND ? imax(LDS_BASE, (condNeed + 1) & ~1) : LDS_BASE;
+    static constexpr int oFT = (oMCRl + CBS + 1) & ~1;        // NF x RBS trace / (|F|/2)
+    static constexpr int LDS_PER_CELL = GENERAL_FANCY ? ((oFT + NF * RBS + 1) & ~1) : ((oDUMMY + 4 + 1) & ~1);
     static constexpr int LDS_DOUBLES = CPW * LDS_PER_CELL;
 };
 
@@ -412,8 +247,9 @@ struct LocalOpsArgs {
     const double *points;      // np x 2
     const uint32_t *ptids;     // nc x 4
     size_t first, n;
-    const double *pre;         // records of Cfg::Pre::NPRE doubles (hho_pre.hpp) in tiles of 8 cells; Cfg::USE_PRE only
-    double *pre_ring;          // Cfg::SELF_PRE: gridDim.x rings of 64 records (8 tiles), one per wavefront, written by the kernel itself
+    const double *pre;         // records of Cfg::Pre::NPRE doubles (hho_pre.hpp) in tiles of 8 cells
+    double *pre_ring;          // always null, never read: the slot keeps the kernel-argument layout -- without it 248 of the 530
+                               // kernels compile to other code (profiles/operator_switches_isa.txt)
     double *oper, *data, *stab, *lc;
     int32_t *info;
     // condensed mode (MODE_COND): f_T per cell (n x cbs, may be null = 0) in; per cell the packed upper triangle of the
@@ -482,14 +318,6 @@ __device__ __forceinline__ double fast_sqrt(double x)
 // keeps the order, not s_barrier -- and not what __syncthreads() adds to it, a wait for every outstanding global
 // store (vmcnt(0)): with it each cell ended with the wavefront idle until HBM had acknowledged its local matrix.
 __device__ __forceinline__ void wave_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
-// 8-byte LDS read that the compiler may not pair with a neighbour into ds_read2_b64 (volatile, in the LDS address space: a volatile
-// access through a generic pointer would become a flat load)
-__device__ __forceinline__ double lds_single(const double *p)
-{
-    typedef const volatile __attribute__((address_space(3))) double *lds_cvp;
-    return *(lds_cvp)p;
-}
 
 // 16-byte LDS read of two consecutive doubles (p is 16-byte aligned by construction of the LDS map)
 __device__ __forceinline__ double2 lds_pair(const double *p) { return *reinterpret_cast<const double2 *>(p); }
@@ -579,183 +407,6 @@ __device__ __forceinline__ int lds_cholesky(double *A, int l)
         const double r = fast_rsqrt<RSQ_ITERS>(d);   // seed 2^-26 -> ~3e-16 after one Newton step
         row[j] = s * r;
         if (act && l >= j) A[i * LD + j] = (l == j) ? r : row[j];
-        wave_sync();
-    }
-    return bad;
-}
-
-// -------------------------------------------------------------------------------------
-// Blocked variant (block size 3), same input / output convention as lds_cholesky.  The unblocked
-// form is a chain of N steps, each with three dependent LDS round trips (row prefix, broadcast of
-// the pivot, write of the new column) that nothing overlaps; here every lane factors the 3 x 3
-// diagonal block redundantly in registers, so there is one round trip per block:
-//   D = A[J,J] - L[J,:j0] L[J,:j0]^T  (all lanes, from the LDS rows of J)      D = Ld Ld^T
-//   lane i: t = A[i,J] - L[i,:j0] L[J,:j0]^T (own row in registers),  L[i,J] = t Ld^-T
-// -------------------------------------------------------------------------------------
-template <int N, int LD, int G, int RSQ_ITERS = 1>
-__device__ __forceinline__ int lds_cholesky_blocked(double *A, int l)
-{
-    constexpr int NB = 3;
-    double row[N];
-    const bool act = l < N;
-    const int i = act ? l : 0;
-#pragma unroll
-    for (int k = 0; k + 1 < N; k += 2) {
-        const double2 v = lds_pair(A + i * LD + k);
-        row[k] = v.x; row[k + 1] = v.y;
-    }
-    if (N & 1) row[N - 1] = A[i * LD + N - 1];
-    int bad = 0;
-#pragma unroll
-    for (int j0 = 0; j0 < N; j0 += NB) {
-        const int nb = (N - j0 < NB) ? (N - j0) : NB;       // constant after unrolling
-        // Schur complement of the diagonal block (lower triangle) and of the own row, sharing the reads of rows J
-        double d[NB][NB], t[NB];
-#pragma unroll
-        for (int r = 0; r < NB; ++r) {
-            if (r < nb) {
-                t[r] = row[j0 + r];
-#pragma unroll
-                for (int c = 0; c <= r; ++c) d[r][c] = A[(j0 + r) * LD + j0 + c];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < j0; k += 2) {                    // rows of J, two columns per 16-byte read
-            const bool two = k + 1 < j0;
-            double lj[NB], lj1[NB];
-#pragma unroll
-            for (int r = 0; r < NB; ++r) {
-                if (r < nb) {
-                    if (two) { const double2 v = lds_pair(A + (j0 + r) * LD + k); lj[r] = v.x; lj1[r] = v.y; }
-                    else { lj[r] = A[(j0 + r) * LD + k]; lj1[r] = 0.0; }
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < NB; ++r) {
-                if (r < nb) {
-                    t[r] = __builtin_fma(-row[k], lj[r], t[r]);
-                    if (two) t[r] = __builtin_fma(-row[k + 1], lj1[r], t[r]);
-#pragma unroll
-                    for (int c = 0; c <= r; ++c) {
-                        d[r][c] = __builtin_fma(-lj[r], lj[c], d[r][c]);
-                        if (two) d[r][c] = __builtin_fma(-lj1[r], lj1[c], d[r][c]);
-                    }
-                }
-            }
-        }
-        // factor the block in registers (reciprocal diagonal), solve the own row against it
-        double rd[NB];
-#pragma unroll
-        for (int c = 0; c < NB; ++c) {
-            if (c < nb) {
-                double p = d[c][c];
-#pragma unroll
-                for (int k = 0; k < c; ++k) p = __builtin_fma(-d[c][k], d[c][k], p);
-                if (!(p > 0.0) && !bad) bad = j0 + c + 1;
-                rd[c] = fast_rsqrt<RSQ_ITERS>(p);
-#pragma unroll
-                for (int r = c + 1; r < NB; ++r) {
-                    if (r < nb) {
-                        double q = d[r][c];
-#pragma unroll
-                        for (int k = 0; k < c; ++k) q = __builtin_fma(-d[r][k], d[c][k], q);
-                        d[r][c] = q * rd[c];                    // Ld[r][c]
-                    }
-                }
-                double x = t[c];
-#pragma unroll
-                for (int k = 0; k < c; ++k) x = __builtin_fma(-row[j0 + k], d[c][k], x);
-                row[j0 + c] = x * rd[c];                        // L[i][j0 + c] (meaningful for i > j0 + c; == Ld for i in J)
-            }
-        }
-        // column block to LDS: L below the diagonal, 1/L[j][j] on it
-#pragma unroll
-        for (int c = 0; c < NB; ++c)
-            if (c < nb && act && l >= j0 + c) A[i * LD + j0 + c] = (l == j0 + c) ? rd[c] : row[j0 + c];
-        wave_sync();
-    }
-    return bad;
-}
-
-// -------------------------------------------------------------------------------------
-// The first NPV steps of the Cholesky factorization of a symmetric NROWS x NROWS matrix (NROWS >= NPV), one lane per
-// row, NB pivots per LDS round trip -- the condensed mode's elimination of the cell unknowns.  Lane i holds the first
-// NPV entries of row i in `row` and leaves L[i][0..NPV) there; the rows in LDS (row-major, stride LD) receive the same,
-// with 1 / L[j][j] on the diagonal.  Per block J = j0 .. j0+nb-1 every lane forms, from the LDS rows of J,
-//   D = M[J,J] - L[J,:j0] L[J,:j0]^T   (redundantly: it is the pivot block every lane needs)  and
-//   t = M[i,J] - L[i,:j0] L[J,:j0]^T   (its own row),
-// factors D in registers and solves its row against it: one round trip per block instead of one per pivot.
-// Returns 0 or 1 + index of the first non-positive pivot.
-// -------------------------------------------------------------------------------------
-template <int NPV, int NROWS, int NB, int LD>
-__device__ __forceinline__ int lds_partial_cholesky(double *A, int l, double (&row)[NPV])
-{
-    const bool act = l < NROWS;
-    const int i = act ? l : 0;
-    int bad = 0;
-#pragma unroll
-    for (int j0 = 0; j0 < NPV; j0 += NB) {
-        const int nb = (NPV - j0 < NB) ? (NPV - j0) : NB;       // constant after unrolling
-        double d[NB][NB], t[NB];
-#pragma unroll
-        for (int r = 0; r < NB; ++r) {
-            if (r < nb) {
-                t[r] = row[j0 + r];
-#pragma unroll
-                for (int c = 0; c <= r; ++c) d[r][c] = A[(j0 + r) * LD + j0 + c];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < j0; k += 2) {                    // rows of J, two columns per 16-byte read
-            const bool two = k + 1 < j0;
-            double lj[NB], lj1[NB];
-#pragma unroll
-            for (int r = 0; r < NB; ++r) {
-                if (r < nb) {
-                    if (two) { const double2 v = lds_pair(A + (j0 + r) * LD + k); lj[r] = v.x; lj1[r] = v.y; }
-                    else { lj[r] = A[(j0 + r) * LD + k]; lj1[r] = 0.0; }
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < NB; ++r) {
-                if (r < nb) {
-                    t[r] = __builtin_fma(-row[k], lj[r], t[r]);
-                    if (two) t[r] = __builtin_fma(-row[k + 1], lj1[r], t[r]);
-#pragma unroll
-                    for (int c = 0; c <= r; ++c) {
-                        d[r][c] = __builtin_fma(-lj[r], lj[c], d[r][c]);
-                        if (two) d[r][c] = __builtin_fma(-lj1[r], lj1[c], d[r][c]);
-                    }
-                }
-            }
-        }
-        double rd[NB];
-#pragma unroll
-        for (int c = 0; c < NB; ++c) {
-            if (c < nb) {
-                double p = d[c][c];
-#pragma unroll
-                for (int k = 0; k < c; ++k) p = __builtin_fma(-d[c][k], d[c][k], p);
-                if (!(p > 0.0) && !bad) bad = j0 + c + 1;
-                rd[c] = fast_rsqrt<1>(p);
-#pragma unroll
-                for (int r = c + 1; r < NB; ++r) {
-                    if (r < nb) {
-                        double q = d[r][c];
-#pragma unroll
-                        for (int k = 0; k < c; ++k) q = __builtin_fma(-d[r][k], d[c][k], q);
-                        d[r][c] = q * rd[c];                    // Ld[r][c]
-                    }
-                }
-                double x = t[c];
-#pragma unroll
-                for (int k = 0; k < c; ++k) x = __builtin_fma(-row[j0 + k], d[c][k], x);
-                row[j0 + c] = x * rd[c];                        // L[i][j0 + c] (for i in J, i > j0 + c: == Ld; i == j0 + c: L[j][j])
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < NB; ++c)
-            if (c < nb && act && l >= j0 + c) A[i * LD + j0 + c] = (l == j0 + c) ? rd[c] : row[j0 + c];
         wave_sync();
     }
     return bad;
@@ -978,25 +629,6 @@ __device__ __forceinline__ double to_sgpr(double v)
     return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
 }
 
-// lane-dependent choice among four register values (kept as scalars: an array indexed this way
-// is demoted to scratch memory)
-__device__ __forceinline__ double sel4(double v0, double v1, double v2, double v3, int i)
-{
-    double r = v0;
-    r = (i == 1) ? v1 : r;
-    r = (i == 2) ? v2 : r;
-    r = (i == 3) ? v3 : r;
-    return r;
-}
-__device__ __forceinline__ uint32_t sel4u(uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3, int i)
-{
-    uint32_t r = v0;
-    r = (i == 1) ? v1 : r;
-    r = (i == 2) ? v2 : r;
-    r = (i == 3) ? v3 : r;
-    return r;
-}
-
 // -------------------------------------------------------------------------------------
 // The kernel.  One wavefront per block; G lanes per cell; persistent over cells.
 // -------------------------------------------------------------------------------------
@@ -1010,16 +642,6 @@ __device__ __forceinline__ uint32_t sel4u(uint32_t v0, uint32_t v1, uint32_t v2,
 //             image's entries to their places in the CSR values and right-hand side of the assembler's own system
 //             (hho_asm_scatter.hpp), and lc itself only when asked for.
 enum { MODE_LC = 0, MODE_SPLIT = 1, MODE_COND = 2, MODE_ASM = 3 };
-// hho_pre.hpp: the head of one cell in the registers of the calling lane, its record to `out` (pairs 16 doubles apart)
-struct PreArgs {
-    const QuadTables *tab;
-    const double *points;
-    const uint32_t *ptids;
-    size_t first, n;           // cells first .. first+n-1; record of cell first+i: tile i / 8, slot i % 8 (see the kernel)
-    double *pre;
-};
-template <class C>
-__device__ __forceinline__ void cell_pre_record(const PreArgs &a, size_t cell, double *out);
 template <class C, int MODE>
 __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::WAVES) void hho_local_ops_kernel(LocalOpsArgs a)
 {
@@ -1027,51 +649,12 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
     static_assert(COND == C::COND, "the condensed mode runs on the Cfg instance that reserves its LDS image");
     static_assert(!COND || (C::CBS + C::NF + 1 <= C::G && C::HAS_STAB), "condensed mode: one lane per row of [lc f_T; f_T^T 0]");
     constexpr int G = C::G, RBS = C::RBS, CBS = C::CBS, FBS = C::FBS, MS = C::MS, NR = C::NR, NF = C::NF;
-    constexpr int NQ = C::NQ, NFQ = C::NFQ, NFP = C::NFP, NP = C::NP, RD = C::RD, NPW = C::NPW;
+    constexpr int NFQ = C::NFQ, NFP = C::NFP, RD = C::RD;
     constexpr int ZS = C::ZS, ND = C::ND, NRP = C::NRP, LD = C::LD;
     static_assert(MS <= G, "one lane per local-matrix column");
     static_assert(RBS <= G && NF <= G, "one lane per row in the factorizations");
     static_assert(C::NQ > 0, "empty quadrature rule (the rules[8] hole)");
 
-#if PA_SELF_PRE
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    const QuadTables *__restrict__ tab = a.tab;
-    typedef typename C::Pre PRE;
-    // Blocks b and b + 8 share an XCD (round-robin dispatch; a speed assumption only): give the blocks of an XCD
-    // consecutive cells, so that the 8 cells of a record tile, and the lines of lc they share, meet in one L2.
-    const size_t lblock = (PA_XCD_MAP && gridDim.x % 8 == 0) ? (size_t)(blockIdx.x % 8) * (gridDim.x / 8) + blockIdx.x / 8 : (size_t)blockIdx.x;
-    const size_t stride = (size_t)gridDim.x * C::CPW;
-    // Cfg::SELF_PRE: the wavefront's own ring of 64 records; pass ib of a batch reads the slots ib CPW + g
-    constexpr bool SELF = C::SELF_PRE;
-    constexpr int SELF_IT = C::SELF_IT;
-    double *ring = SELF ? a.pre_ring + (size_t)blockIdx.x * (size_t)(64 * PRE::NPRE) : nullptr;
-#ifdef PA_STAGE_CLOCK
-    long long tk_sum[PA_NSTAGE] = {0}, tk_last = clock64();
-#endif
-    // Cfg::SELF_PRE: an outer loop over batches of SELF_IT passes -- the heads of the batch's 64 cells first (the thread-per-cell code
-    // of hho_pre.hpp, which needs every register the kernel has), then the per-lane bookkeeping of the cooperative passes, re-derived
-    // per batch from an opaque lane index so that nothing of it is live across the production, then the passes.  Otherwise one batch.
-    size_t base = lblock * C::CPW;
-    // the FIRST batch of a wavefront is shorter by a pseudo-random number of passes: the wavefronts of a compute unit then stop for their
-    // production at different times, next to the others' passes (all at once they are the pre-pass again: the whole chip writing records)
-    int nb = SELF ? SELF_IT - (int)(((uint32_t)blockIdx.x * 2654435761u) >> 8) % SELF_IT : 1;
-    while (base < a.n) {
-    int lane = threadIdx.x;
-    if (SELF) {
-        // lane j's cell is the one group j % CPW of pass j / CPW of the batch will work on.  Every record of the previous batch has
-        // been consumed (the last one was deposited in region P a pass ago), so the ring is free.  Own stores, then own loads:
-        // s_waitcnt vmcnt(0) orders them (the vector L1 is write-through and the lines belong to this compute unit alone).
-        PA_MARK("SELFPRE");
-        const size_t idx = base + (size_t)(lane / C::CPW) * stride + (size_t)(lane % C::CPW);
-        if (idx < a.n && lane / C::CPW < nb)
-            cell_pre_record<C>(PreArgs{tab, a.points, a.ptids, 0, 0, nullptr}, a.first + idx,
-                               ring + ((uint32_t)lane >> 3) * (uint32_t)(PRE::NP2 * 16) + ((uint32_t)lane & 7u) * 2u);
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(lane) : : "memory");
-    }
-    const int g = lane / G, l0 = lane % G;
-    const int l = l0;
-    double *S = smem + g * C::LDS_PER_CELL;
-#else
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int lane = threadIdx.x;
     const int g = lane / G, l0 = lane % G;
@@ -1081,12 +664,10 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
     typedef typename C::Pre PRE;
     // Blocks b and b + 8 share an XCD (round-robin dispatch; a speed assumption only): give the blocks of an XCD
     // consecutive cells, so that the 8 cells of a record tile, and the lines of lc they share, meet in one L2.
-    const size_t lblock = (PA_XCD_MAP && gridDim.x % 8 == 0) ? (size_t)(blockIdx.x % 8) * (gridDim.x / 8) + blockIdx.x / 8 : (size_t)blockIdx.x;
+    const size_t lblock = gridDim.x % 8 == 0 ? (size_t)(blockIdx.x % 8) * (gridDim.x / 8) + blockIdx.x / 8 : (size_t)blockIdx.x;
     const size_t stride = (size_t)gridDim.x * C::CPW;
-    constexpr bool SELF = false;
 #ifdef PA_STAGE_CLOCK
     long long tk_sum[PA_NSTAGE] = {0}, tk_last = clock64();
-#endif
 #endif
     // constant face tables, kept in scalar registers
     FaceTables ft;
@@ -1099,99 +680,38 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
 #pragma unroll
         for (int k = 0; k <= i; ++k) ft.lf[i][k] = to_sgpr(tab->face[C::FD].lf[i][k]);
 
-    constexpr bool S1_SPLIT = PA_S1_SPLIT && C::USE_PRE && 2 * NFP <= G && C::PPL == 1;
+    // S1: TWO lanes per face point where the group has them -- one forms its row of scaled monomials, the other its row of
+    // weighted normal derivatives -- and ONE common run of LDS stores (a store instruction costs its 6 ... 13 cycles of the
+    // store path whatever the number of active lanes: 5 instead of 10 of them per pass at k = 2)
+    constexpr bool S1_SPLIT = 2 * NFP <= G && C::PPL == 1;
     // ---- per-lane, cell-invariant bookkeeping -------------------------------------------
-    // reference coordinates of the evaluation points this lane owns
-    double r0[C::PPL], r1[C::PPL], r2[C::PPL], rw[C::PPL];
+    // reference coordinate and half weight of the face points this lane evaluates
+    double r0[C::PPL], rw[C::PPL];
 #pragma unroll
     for (int r = 0; r < C::PPL; ++r) {
         const int p = l + r * G;
-        r0[r] = r1[r] = r2[r] = rw[r] = 0.0;
-        if (C::NQB > 0 && p < C::NQB) {
-            if (C::QUAD == QUAD_TENSOR) {
-                const int i = p % C::NG, j = p / C::NG;            // outer eta, inner xi  quadratures.hpp:355-357
-                r0[r] = tab->gauss_x[C::NG][i];
-                r1[r] = tab->gauss_x[C::NG][j];
-                rw[r] = tab->gauss_w[C::NG][i] * tab->gauss_w[C::NG][j];
-            } else {
-                const int row = p % C::NT;
-                constexpr int R = C::QDEG == 0 ? 1 : C::QDEG;      // rules[deg]  quadratures.hpp:257
-                r0[r] = tab->dun[R][row][0];
-                r1[r] = tab->dun[R][row][1];
-                r2[r] = tab->dun[R][row][2];
-                rw[r] = tab->dun[R][row][3];
-            }
-        } else if (p < NP || (S1_SPLIT && p < 2 * NFP)) {
-            const int q = (S1_SPLIT && p >= NFP ? p - NFP : p - C::NQB) % NFQ;
+        r0[r] = rw[r] = 0.0;
+        if (p < NFP || (S1_SPLIT && p < 2 * NFP)) {
+            const int q = (S1_SPLIT && p >= NFP ? p - NFP : p) % NFQ;
             r0[r] = tab->gauss_x[NFQ][q];
             rw[r] = 0.5 * tab->gauss_w[NFQ][q];
         }
-    }
-    // moments owned by this lane: LDS offsets of w bx^p and by^r
-    int mom_ox[C::MPL], mom_oy[C::MPL];
-#pragma unroll
-    for (int t = 0; t < C::MPL; ++t) {
-        const int mu = l + t * G;
-        int p = 0, r = 0;
-        if (mu < C::NMOM) mono_exps(mu, p, r);
-        mom_ox[t] = C::oWPX + p;
-        mom_oy[t] = C::oPY + r;
-    }
-    // stiffness entries owned by this lane: stiff(i,j) = ih^2 (a a' MOM(a+a'-2, b+b') + b b' MOM(a+a', b+b'-2))
-    // packed as idx1 | idx2<<8 | c1<<16 | c2<<24   (bases.hpp:170-176 with hho.hpp:57-61)
-    // (i, j <= i of the packed lower triangle; the mirror entry is written with it) in bits 0-7 / 8-15 of st_ij
-    uint32_t st_code[C::SPL], st_ij[C::SPL];
-#pragma unroll
-    for (int t = 0; t < C::SPL; ++t) {
-        const int e = l + t * G;
-        uint32_t code = 0, ij = 0;
-        if (e < C::NSYM) {
-            int i = 0;
-            while ((i + 1) * (i + 2) / 2 <= e) ++i;
-            const int j = e - i * (i + 1) / 2;
-            int ai, bi, aj, bj;
-            mono_exps(i, ai, bi);
-            mono_exps(j, aj, bj);
-            const int c1 = ai * aj, c2 = bi * bj;
-            const int i1 = c1 ? mono_index(ai + aj - 2, bi + bj) : 0;
-            const int i2 = c2 ? mono_index(ai + aj, bi + bj - 2) : 0;
-            code = (uint32_t)i1 | ((uint32_t)i2 << 8) | ((uint32_t)c1 << 16) | ((uint32_t)c2 << 24);
-            ij = (uint32_t)i | ((uint32_t)j << 8);
-        }
-        st_code[t] = code; st_ij[t] = ij;
     }
     // column role of this lane: cell column (c < CBS) or column kf of face fc
     const bool is_col = l < MS, is_cellcol = l < CBS;
     const int c0 = is_col ? l : 0;
     const int fc = is_cellcol ? 0 : (c0 - CBS) / FBS, kf = is_cellcol ? 0 : (c0 - CBS) % FBS;
-    // t_q^kf ; column kf of L^^T.  Per lane and cell-invariant: 2 (NFQ + FBS) registers for the whole kernel -- or, where
-    // the tables are small (FACE_SEL), the uniform tables in scalar registers and a select per use from the lane index
-    // of the pass.
-    // (measured: -4 % for the k = 2 tensor lc kernel while it ran four waves and spilled six registers at its 128; +4 % in
-    // its condensed form and at k = 1, where nothing spills -- and +3 % at the three waves it runs now: off)
-    constexpr bool FACE_SEL = PA_FACE_SEL && FBS == 3 && C::CD == 3 && C::QUAD == QUAD_TENSOR && G == 32 && MODE == MODE_LC;
-    double fbq0[NFQ], ufc0[FBS];
-    double fbt[FACE_SEL ? NFQ : 1][FACE_SEL ? FBS : 1], lftt[FACE_SEL ? FBS : 1][FACE_SEL ? FBS : 1];
+    // t_q^kf ; column kf of L^^T.  Per lane and cell-invariant: 2 (NFQ + FBS) registers for the whole kernel
+    double fbq[NFQ], ufc[FBS];
 #pragma unroll
-    for (int q = 0; q < NFQ; ++q) fbq0[q] = FACE_SEL ? 0.0 : tab->face[C::FD].fb[q][kf];
+    for (int q = 0; q < NFQ; ++q) fbq[q] = tab->face[C::FD].fb[q][kf];
 #pragma unroll
-    for (int j = 0; j < FBS; ++j) ufc0[j] = FACE_SEL ? 0.0 : tab->face[C::FD].lft[j][kf];
-    if (FACE_SEL) {
-#pragma unroll
-        for (int q = 0; q < NFQ; ++q)
-#pragma unroll
-            for (int k = 0; k < FBS; ++k) fbt[q][k] = tab->face[C::FD].fb[q][k];
-#pragma unroll
-        for (int j = 0; j < FBS; ++j)
-#pragma unroll
-            for (int k = 0; k < FBS; ++k) lftt[j][k] = tab->face[C::FD].lft[j][k];
-    }
+    for (int j = 0; j < FBS; ++j) ufc[j] = tab->face[C::FD].lft[j][kf];
 
     // Corner tile of Z^T Z on the vector pipe (msize 17..24): with T_F = [trace_F | 0] its columns are face columns, whose
     // U parts are -sqrt(|F|/2h) L^^T e_k on the rows of their own face: the U term of an entry is su_F^2 (L^^ L^^T)[ki][kj]
     // for two columns of one face and nothing otherwise -- a constant per lane; only the Y rows are read from LDS.
-    constexpr bool CORNER_SHORT = C::CORNER_VALU && PA_CORNER_SHORT && C::HAS_STAB && !C::GENERAL_FANCY && PA_UNIT_U && MODE != MODE_SPLIT &&
-                                  CBS <= 16 && !PA_LC_VALU;
+    constexpr bool CORNER_SHORT = C::CORNER_VALU && C::HAS_STAB && !C::GENERAL_FANCY && !SPLIT && CBS <= 16;
     double cornerT = 0.0;
     if (CORNER_SHORT && l < C::NCORNER * (C::NCORNER + 1) / 2) {
         int cj_ = 0;
@@ -1210,8 +730,8 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
     //   unit word:   bits 0-11 offset of the unit's first phi value in the face-point table (doubles from oPHF),
     //                bits 12-23 offset of its first U entry in Z (doubles from S; the sink for lanes without a unit), bits 24-25 face
     //   corner word: bits 0-7 ci, 8-15 cj (ci <= cj: the pair of corner columns of this lane), 16-17 face of column ci
-    constexpr bool UNIT_U = C::HAS_STAB && !C::GENERAL_FANCY && !SPLIT && PA_UNIT_U;
-    constexpr bool UPERM_ON = C::UPERM && UNIT_U && !PA_LC_VALU;
+    constexpr bool UNIT_U = C::HAS_STAB && !C::GENERAL_FANCY && !SPLIT;
+    constexpr bool UPERM_ON = C::UPERM && UNIT_U;
     constexpr int NU = 4 * CBS, UR = UNIT_U ? cdiv(NU, G) : 1;
     uint32_t unit_pk[UR];
 #pragma unroll
@@ -1241,8 +761,8 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
     // scale, added after the products -- which then stop after the rows of Y (k = 3: 4 of 8 k-steps, 20 instead of 24 matrix
     // instructions per cell).
     constexpr int NTL_ = (MS + 15) / 16;
-    constexpr bool T11_SHORT = PA_T11_SHORT && UNIT_U && NTL_ == 2 && !C::CORNER_VALU && CBS <= 16 && !PA_LC_VALU && !SPLIT;
-    constexpr bool ACC_PERM_ = PA_ACC_PERM && !(C::DIRECT_STORE && !COND) && !COND && MS % 2 == 0;
+    constexpr bool T11_SHORT = UNIT_U && NTL_ == 2 && !C::CORNER_VALU && CBS <= 16;
+    constexpr bool ACC_PERM_ = !C::DIRECT_STORE && !COND && MS % 2 == 0;
     double t11c[4] = {0.0, 0.0, 0.0, 0.0};
     int t11f = 0;
     if (T11_SHORT) {
@@ -1296,19 +816,6 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
     // registers while S1-S6 run, and go to region P when S6 is done with it -- before the stores of S8 are
     // issued, so that no load ever queues behind them (vector memory operations complete in order).
     double2 rec[C::PLC];
-#if PA_SELF_PRE
-    auto rec_issue_slot = [&](int ib) {
-        const uint32_t s = (uint32_t)(ib * C::CPW + g);
-        const double *pc = ring + (s >> 3) * (uint32_t)(PRE::NP2 * 16) + (s & 7u) * 2u;
-#pragma unroll
-        for (int t = 0; t < C::PLC; ++t) {
-            const int e2 = l0 + t * G;
-            rec[t] = *reinterpret_cast<const double2 *>(pc + 16 * (e2 < PRE::NP2 ? e2 : 0));
-        }
-    };
-#else
-    auto rec_issue_slot = [&](int) {};
-#endif
     auto rec_issue = [&](size_t b) {
         // records lie in tiles of 8 cells, [tile][pair][cell % 8] (hho_pre.hpp): the pairs of one record are 128 bytes apart
         // (b is a multiple of the CPW cells of a wavefront, CPW divides 8: the wavefront's cells share a tile, whose address is
@@ -1335,109 +842,35 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
             }
         }
     };
-    if (C::USE_PRE) {
-        if (!C::DPPFWD) {
-            for (int e = l; e < C::LGR * LD; e += G) S[C::oLG + e] = 0.0;
-            wave_sync();
-        }
-        if (!SELF) rec_issue(lblock * C::CPW);
-        else rec_issue_slot(0);
-        rec_deposit();
+    if (!C::DPPFWD) {
+        for (int e = l; e < NR * LD; e += G) S[C::oLG + e] = 0.0;
         wave_sync();
     }
+    rec_issue(lblock * C::CPW);
+    rec_deposit();
+    wave_sync();
 
-#if PA_SELF_PRE
-    const int nbc = nb;
-    nb = SELF_IT;
-    for (int ib = 0; (!SELF || ib < nbc) && base < a.n; base += stride, ++ib) {
-#else
-    constexpr int ib = 0, nbc = 1;
     for (size_t base = lblock * C::CPW; base < a.n; base += stride) {
-#endif
         // Re-derive the lane index opaquely per cell: otherwise LICM hoists the index computations
         // of every stage out of the cell loop and the kernel spills.
         int l = l0;
         asm volatile("" : "+v"(l));
-        if (PA_PRIO_OUT >= 0) __builtin_amdgcn_s_setprio(PA_PRIO_HEAD);
-#if PA_LANE_RANGE
+        __builtin_amdgcn_s_setprio(PRIO_HEAD);
         l &= G - 1;      // tell the compiler the range again: its index products fit 24 bits (v_mul_u32_u24 / v_mad_u32_u24 are full rate)
-#endif
         const bool valid = base + g < a.n;
         const size_t cell = a.first + (valid ? base + g : a.n - 1);
         // offset of the lane's cell in an output / input array of X doubles per cell: the block's part is wave-uniform (scalar
         // arithmetic), the lane adds its group's (lanes past the end: the first cell of the pass, which exists)
         const uint32_t gl = valid ? (uint32_t)g : 0u;
         auto rel = [&](uint32_t X) -> size_t { return base * (size_t)X + (size_t)(gl * X); };
-        double fbq[NFQ], ufc[FBS];
-        if (FACE_SEL) {
-            const int kfl = (l >= CBS && l < MS) ? (l - CBS) % FBS : 0;
-#pragma unroll
-            for (int q = 0; q < NFQ; ++q) fbq[q] = kfl == 0 ? fbt[q][0] : (kfl == 1 || FBS < 3) ? fbt[q][FBS > 1 ? 1 : 0] : fbt[q][FBS > 2 ? 2 : 0];
-#pragma unroll
-            for (int j = 0; j < FBS; ++j) ufc[j] = kfl == 0 ? lftt[j][0] : (kfl == 1 || FBS < 3) ? lftt[j][FBS > 1 ? 1 : 0] : lftt[j][FBS > 2 ? 2 : 0];
-        } else {
-#pragma unroll
-            for (int q = 0; q < NFQ; ++q) fbq[q] = fbq0[q];
-#pragma unroll
-            for (int j = 0; j < FBS; ++j) ufc[j] = ufc0[j];
-        }
 
-        // ================= S0: geometry (every lane of the group, registers) ==========
+        // ================= S0: the cell's scalars ======================================
+        // The per-cell head comes from the pre-pass; its record is in region P already (fetched a pass ahead).
         PA_MARK("S0");
-        uint4 idv = {0u, 0u, 0u, 0u};
-        double px0 = 0.0, py0 = 0.0, px1 = 0.0, py1 = 0.0, px2 = 0.0, py2 = 0.0, px3 = 0.0, py3 = 0.0;
-        double barx, bary, ih;
-        double e0x = 0.0, e0y = 0.0, e1x = 0.0, e1y = 0.0, e2x = 0.0, e2y = 0.0, e3x = 0.0, e3y = 0.0;
-        int bad_pre = 0;
-        if (C::USE_PRE) {
-            // the per-cell head comes from the pre-pass; its record is in region P already (prefetched)
-            if (!SELF) rec_issue(base + stride);
-            else if (ib + 1 < nbc) rec_issue_slot(ib + 1);
-            const double2 bb = lds_pair(S + C::oSU + 4), ib = lds_pair(S + C::oSU + 6);
-            barx = bb.x; bary = bb.y; ih = ib.x; bad_pre = (int)ib.y;
-        } else {
-        idv = *reinterpret_cast<const uint4 *>(a.ptids + 4 * cell);
-        {
-            const double2 q0 = *reinterpret_cast<const double2 *>(a.points + 2 * (size_t)idv.x);
-            const double2 q1 = *reinterpret_cast<const double2 *>(a.points + 2 * (size_t)idv.y);
-            const double2 q2 = *reinterpret_cast<const double2 *>(a.points + 2 * (size_t)idv.z);
-            const double2 q3 = *reinterpret_cast<const double2 *>(a.points + 2 * (size_t)idv.w);
-            px0 = q0.x; py0 = q0.y; px1 = q1.x; py1 = q1.y; px2 = q2.x; py2 = q2.y; px3 = q3.x; py3 = q3.y;
-        }
-        {                                           // barycenter  basic_geom.hpp:247-270
-            const double ax = px1 - px0, ay = py1 - py0, bx = px2 - px0, by = py2 - py0;
-            const double cx = px3 - px0, cy = py3 - py0;
-            const double d1 = (ax * by - ay * bx) * 0.5, d2 = (bx * cy - by * cx) * 0.5;
-            const double rx = (ax + bx) * d1 + (bx + cx) * d2, ry = (ay + by) * d1 + (by + cy) * d2;
-            const double iden = fast_rcp((d1 + d2) * 3);
-            barx = px0 + rx * iden; bary = py0 + ry * iden;
-        }
-        // edge vectors in cell (CCW) order, squared lengths of edges and diagonals
-        e0x = px1 - px0; e0y = py1 - py0; e1x = px2 - px1; e1y = py2 - py1;
-        e2x = px3 - px2; e2y = py3 - py2; e3x = px0 - px3; e3y = py0 - py3;
-        const double s0 = e0x * e0x + e0y * e0y, s1 = e1x * e1x + e1y * e1y;
-        const double s2 = e2x * e2x + e2y * e2y, s3 = e3x * e3x + e3y * e3y;
-        double h2;                                  // diameter^2  basic_geom.hpp:288-305
-        {
-            const double d02x = px2 - px0, d02y = py2 - py0, d13x = px3 - px1, d13y = py3 - py1;
-            h2 = fmax(fmax(s0, s1), fmax(s2, s3));
-            h2 = fmax(h2, fmax(d02x * d02x + d02y * d02y, d13x * d13x + d13y * d13y));
-        }
-        const double rh = fast_rsqrt(h2);           // 1 / h_T
-        ih = 2.0 * rh;                              // bx = (x - bar)/(h/2), ih = 2/h  bases.hpp:98-99,142
-        double hinv = rh;                           // fancy: h = cell diameter  hho.hpp:201
-        if (C::NAIVE) {                             // naive: h = cell area      hho.hpp:119, basic_geom.hpp:317-334
-            const double ux = px1 - px0, uy = py1 - py0, vx = px2 - px0, vy = py2 - py0;
-            const double wx = px3 - px0, wy = py3 - py0;
-            hinv = fast_rcp(fabs(ux * vy - uy * vx) * 0.5 + fabs(vx * wy - vy * wx) * 0.5);
-        }
-        // lanes 0..3: sqrt(|F| / (2 h)) of local face l, shared through LDS
-        if (C::HAS_STAB && l < 4) {
-            const double sq = sel4(s0, s1, s2, s3, l);
-            const double len = sq * fast_rsqrt(sq);
-            S[C::oSU + l] = fast_sqrt(0.5 * len * hinv);
-        }
-        }
+        rec_issue(base + stride);
+        const double2 bb = lds_pair(S + C::oSU + 4), ihb = lds_pair(S + C::oSU + 6);
+        const double barx = bb.x, bary = bb.y, ih = ihb.x;
+        const int bad_pre = (int)ihb.y;
 
         PA_TICK(0);
         // ================= S1: evaluation points ======================================
@@ -1497,78 +930,28 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
                 for (int m = 0; m < RBS; ++m)
                     if (m < NR || !dnrow) dst[m] = out[m];
             }
-        } else
-        if (!(a.ablate & 1u)) {   // S1
+        } else if (!(a.ablate & 1u)) {
 #pragma unroll
-        for (int r = 0; r < C::PPL; ++r) {
-            const int p = l + r * G;
-            if (p < NP) {
-                double x, y, w, wnx = 0.0, wny = 0.0;
-                const bool is_cell = C::NQB > 0 && p < C::NQB;      // (the opaque lane index has no known sign)
-                if (is_cell) {
-                    if (C::QUAD == QUAD_TENSOR) {
-                        // bilinear map and |det J| (quadratures.hpp:331-352) with the shape functions
-                        // 0.25 (1 +- xi)(1 +- eta) factored once
-                        double xi = r0[r], eta = r1[r];
-                        asm volatile("" : "+v"(xi), "+v"(eta));      // keep the shape functions out of LICM's reach
-                        const double am = 0.25 * (1 - eta), ap = 0.25 * (1 + eta);
-                        const double bm = 0.25 * (1 - xi), bp = 0.25 * (1 + xi);
-                        const double n0 = (1 - xi) * am, n1 = (1 + xi) * am, n2 = (1 + xi) * ap, n3 = (1 - xi) * ap;
-                        x = n0 * px0 + n1 * px1 + n2 * px2 + n3 * px3;
-                        y = n0 * py0 + n1 * py1 + n2 * py2 + n3 * py3;
-                        const double j11 = e0x * am - e2x * ap, j12 = e0y * am - e2y * ap;
-                        const double j21 = e1x * bp - e3x * bm, j22 = e1y * bp - e3y * bm;
-                        w = rw[r] * fabs(j11 * j22 - j12 * j21);
-                    } else {
-                        const int t = p / C::NT;                   // fan triangle (p_t, p_{t+1}, bar)  quadratures.hpp:390-396
-                        const double ax = sel4(px0, px1, px2, px3, t), ay = sel4(py0, py1, py2, py3, t);
-                        const double bx = sel4(px1, px2, px3, px0, t), by = sel4(py1, py2, py3, py0, t);
-                        const double v0x = bx - ax, v0y = by - ay, v1x = barx - ax, v1y = bary - ay;
-                        const double tarea = fabs((v0x * v1y - v0y * v1x) * 0.5);      // quadratures.hpp:248-251
-                        x = ax * r0[r] + bx * r1[r] + barx * r2[r];
-                        y = ay * r0[r] + by * r1[r] + bary * r2[r];
-                        w = tarea * rw[r];
-                    }
-                } else {
-                    const int f = (p - C::NQB) / NFQ;
-                    double ax, ay, bx, by;
-                    bool descending;                               // the face's first vertex has the higher point id
-                    if (C::USE_PRE) {
-                        const double *sc = S + C::oSU;
-                        const double2 pa_ = lds_pair(sc + 8 + 2 * f), pb_ = lds_pair(sc + 8 + 2 * ((f + 1) & 3));
-                        ax = pa_.x; ay = pa_.y; bx = pb_.x; by = pb_.y;
-                        descending = (((int)sc[16]) >> f) & 1;
-                    } else {
-                        ax = sel4(px0, px1, px2, px3, f); ay = sel4(py0, py1, py2, py3, f);
-                        bx = sel4(px1, px2, px3, px0, f); by = sel4(py1, py2, py3, py0, f);
-                        const uint32_t ia = sel4u(idv.x, idv.y, idv.z, idv.w, f), ib = sel4u(idv.y, idv.z, idv.w, idv.x, f);
-                        descending = ia > ib;
-                    }
+            for (int r = 0; r < C::PPL; ++r) {
+                const int p = l + r * G;
+                if (p < NFP) {
+                    // scaled monomials and weighted normal derivatives  bases.hpp:93-184, hho.hpp:77-83
+                    const int f = p / NFQ;
+                    const double *sc = S + C::oSU;
+                    const double2 pa_ = lds_pair(sc + 8 + 2 * f), pb_ = lds_pair(sc + 8 + 2 * ((f + 1) & 3));
+                    const double ax = pa_.x, ay = pa_.y, bx = pb_.x, by = pb_.y;
+                    const bool descending = (((int)sc[16]) >> f) & 1;      // the face's first vertex has the higher point id
                     // w n = (w_q |F|/2) (e_y, -e_x)/|F|: the edge length cancels  (basic_geom.hpp:361-369,
                     // quadratures.hpp:426); rw holds w_q / 2
-                    wnx = rw[r] * (by - ay); wny = -rw[r] * (bx - ax);
+                    const double wnx = rw[r] * (by - ay), wny = -rw[r] * (bx - ax);
                     // the face runs from its LOWER-id endpoint (basic_geom.hpp:202-203, bases.hpp:260-261):
                     // its q-th point sits at -t_q in cell order when the ids are descending
                     const double t = descending ? -r0[r] : r0[r];
                     // quadratures.hpp:420-428 taken from the endpoint a (see the split S1 above)
                     const double cb = 0.5 * (1 + t);
-                    x = __builtin_fma(cb, bx - ax, ax);
-                    y = __builtin_fma(cb, by - ay, ay);
-                    w = 0.0;
-                }
-                const double bx_ = (x - barx) * ih, by_ = (y - bary) * ih;
-                if (is_cell) {
-                    // w * bx^e and by^e, e = 0..2 recdeg: the factors of every cell moment
-                    double vx = w, vy = 1.0;
-#pragma unroll
-                    for (int e = 0; e < NPW; ++e) {
-                        S[C::oWPX + p * NPW + e] = vx;
-                        S[C::oPY + p * NPW + e] = vy;
-                        vx *= bx_; vy *= by_;
-                    }
-                } else {
-                    // scaled monomials and weighted normal derivatives at a face point  bases.hpp:93-184, hho.hpp:77-83
-                    const int pf = p - C::NQB;
+                    const double x = __builtin_fma(cb, bx - ax, ax);
+                    const double y = __builtin_fma(cb, by - ay, ay);
+                    const double bx_ = (x - barx) * ih, by_ = (y - bary) * ih;
                     double pwx[RD + 1], pwy[RD + 1];
                     pwx[0] = 1.0; pwy[0] = 1.0;
 #pragma unroll
@@ -1580,260 +963,98 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
 #pragma unroll
                         for (int ii = 0; ii <= kk; ++ii, ++m) {
                             const int ex_ = kk - ii, ey_ = ii;      // (px,py) = (k-i, i)  bases.hpp:119-120
-                            S[C::oPHF + pf * RBS + m] = pwx[ex_] * pwy[ey_];
+                            S[C::oPHF + p * RBS + m] = pwx[ex_] * pwy[ey_];
                             if (m > 0) {
                                 const double gx = ex_ == 0 ? 0.0 : (ex_ * gnx) * pwx[ex_ > 0 ? ex_ - 1 : 0] * pwy[ey_];
                                 const double gy = ey_ == 0 ? 0.0 : (ey_ * gny) * pwx[ex_] * pwy[ey_ > 0 ? ey_ - 1 : 0];
-                                S[C::oDN + pf * NRP + (m - 1)] = gx + gy;
+                                S[C::oDN + p * NRP + (m - 1)] = gx + gy;
                             }
                         }
                     }
                 }
             }
         }
-        }
         wave_sync();
 
-        // ================= S2: cell moments ===========================================
+        // (S2, cell moments, and S3, stiffness and mass, belong to the pre-pass: hho_pre.hpp)
         PA_MARK("S2");
-        if (!C::USE_PRE) {
-        if (!(a.ablate & 2u)) {   // S2
-#pragma unroll
-        for (int t = 0; t < C::MPL; ++t) {
-            if (l + t * G < C::NMOM) {
-                double s = 0.0;
-#pragma unroll
-                for (int q = 0; q < NQ; ++q) s += S[mom_ox[t] + q * NPW] * S[mom_oy[t] + q * NPW];
-                S[C::oMOM + l + t * G] = s;
-            }
-        }
-        }
-        wave_sync();
-        }
-
-        // ================= S3: stiffness (+mass) from moments ========================
         PA_MARK("S3");
-        if (!C::USE_PRE) {
-            const double ih2 = ih * ih;
-#pragma unroll
-            for (int t = 0; t < C::SPL; ++t) {
-                const int e = l + t * G;
-                if (e < C::NSYM) {
-                    // decoded here, per cell: hoisted, the decoded offsets and coefficients would cost
-                    // six registers per entry for the whole kernel
-                    uint32_t code = st_code[t], ij = st_ij[t];
-                    asm volatile("" : "+v"(code), "+v"(ij));
-                    const double c1 = (double)((code >> 16) & 0xff), c2 = (double)(code >> 24);
-                    const double v = ih2 * (c1 * S[C::oMOM + (code & 0xff)] + c2 * S[C::oMOM + ((code >> 8) & 0xff)]);
-                    const int i = (int)(ij & 0xff), j = (int)(ij >> 8);
-                    S[C::oST + i + j * LD] = v;
-                    S[C::oST + j + i * LD] = v;
-                }
-            }
-            if (C::GENERAL_FANCY) {
-                for (int e = l; e < RBS * RBS; e += G) {
-                    int ai, bi, aj, bj;
-                    mono_exps(e % RBS, ai, bi);
-                    mono_exps(e / RBS, aj, bj);
-                    S[C::oMA + (e % RBS) + (e / RBS) * LD] = S[C::oMOM + mono_index(ai + aj, bi + bj)];
-                }
-            }
-            wave_sync();
-        }
-
         PA_TICK(1);
         // ================= S3b: column c of gr_rhs  hho.hpp:64-85 =====================
-        if (PA_PRIO_OUT >= 0 && PA_PRIO_S3B >= 0) __builtin_amdgcn_s_setprio(PA_PRIO_S3B >= 0 ? PA_PRIO_S3B : 0);
+        __builtin_amdgcn_s_setprio(PRIO_S3B);
         PA_MARK("S3b");
         const int c = l < MS ? l : 0;
         double col[NR];
 #pragma unroll
         for (int i = 0; i < NR; ++i) asm volatile("" : "=v"(col[i]));      // (every lane writes every row below; only a profiling build's skipped stage leaves them as they are -- a constant here cost a move per row and pass)
-        // Cell columns: stiff[1:, c] minus sum_pf (w dphi.n)[pf][:] phi_c(x_pf).  The NR rows of a column
-        // are split over SPC lanes (there are only CBS cell columns for G lanes); the pieces meet in
-        // the GRC scratch (on the dead quadrature tables) and the column owner reloads them after
-        // the barrier below.
-        constexpr int SPC = C::SPC, RPP = C::RPP;
-        // With the pre-pass the cell columns start from zero: -F = -DN^T PHF (NR x CBS, inner dimension the NFP face
-        // points) is one 16 x 16 tile of the matrix pipe per cell, NFP/4 instructions, each lane reading ONE element of
-        // either table per step (the vector form reads 4 per 3 FMAs, and the LDS pipeline is the busiest of the kernel).
-        // (measured: -5 % at k = 3; nothing at k = 2, where it costs the 4th wave its last registers)
-        constexpr bool GRC_MFMA = C::USE_PRE && SPC > 1 && PA_GRC_MFMA && NR >= PA_GRC_MFMA_MIN_NR && NR <= 16 && CBS <= 16;
         if (a.ablate & 4u) {
-        } else if (GRC_MFMA) {
-            typedef double v4d_ __attribute__((ext_vector_type(4)));
-            const int kk_ = lane >> 4, jj_ = lane & 15;
-#pragma unroll
-            for (int gi = 0; gi < C::CPW; ++gi) {
-                double *Sg = smem + gi * C::LDS_PER_CELL;
-                v4d_ f = v4d_{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                for (int ks = 0; ks < NFP / 4; ++ks) {
-                    const int pf = 4 * ks + kk_;
-                    const double av = Sg[C::oDN + pf * NRP + (jj_ < NR ? jj_ : 0)];
-                    const double bv = Sg[C::oPHF + pf * RBS + (jj_ < CBS ? jj_ : 0)];
-                    f = __builtin_amdgcn_mfma_f64_16x16x4f64(jj_ < NR ? av : 0.0, jj_ < CBS ? bv : 0.0, f, 0, 0, 0);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int row = kk_ + 4 * r;
-                    if (4 * r < NR && (4 * r + 3 < NR || row < NR) && jj_ < CBS) Sg[C::oGRC + jj_ * NRP + row] = -f[r];
-                }
-            }
-        } else if (SPC > 1) {
-            if (l < SPC * CBS) {
-                const int part = l / CBS, cc = l % CBS, r0 = part * RPP;
-                double acc[RPP];
-#pragma unroll
-                for (int r = 0; r < RPP; ++r)
-                    acc[r] = C::USE_PRE ? 0.0 : S[C::oST + 1 + (r0 + r < NR ? r0 + r : NR - 1) + cc * LD];
-#pragma unroll
-                for (int pf = 0; pf < NFP; ++pf) {
-                    const double ph = S[C::oPHF + pf * RBS + cc];
-                    const double *dn = S + C::oDN + pf * NRP + r0;
-#pragma unroll
-                    for (int r = 0; r < RPP; ++r) acc[r] = __builtin_fma(-dn[r], ph, acc[r]);      // rows >= NR: unused
-                }
-#pragma unroll
-                for (int r = 0; r < RPP; ++r)
-                    if (r0 + r < NR) S[C::oGRC + cc * NRP + r0 + r] = acc[r];
-            }
-        } else if (C::LAPG) {
-            if (l < CBS) {
-                // -int_T phi_c lap(phi_i) = -(2/h)^2 (a (a-1) MOM(a-2+a', b+b') + b (b-1) MOM(a+a', b-2+b')) for phi_i = bx^a by^b,
-                // phi_c = bx^a' by^b'.  In the graded ordering the moment of phi_c times the monomial m of degree d sits at
-                // c + d (a' + b') + m: one LDS read per monomial of degree <= recdeg - 2, the rest is in registers.
-                constexpr int NDM = RD >= 2 ? P2(RD - 2) : 1;
-                double mc[NDM];
-                int kcv = 0;                                 // a' + b' (per cell from the opaque lane index: no register held)
-#pragma unroll
-                for (int k = 1; k <= C::CD; ++k) kcv += l >= k * (k + 1) / 2 ? 1 : 0;
-                const double *mg = S + C::oMG + l;
-                mc[0] = 0.0;
-#pragma unroll
-                for (int d = 0; d + 2 <= RD; ++d)
-#pragma unroll
-                    for (int bm = 0; bm <= d; ++bm) mc[d * (d + 1) / 2 + bm] = mg[d * kcv + d * (d + 1) / 2 + bm];
-                const double nih2 = -(ih * ih);
-#pragma unroll
-                for (int ki = 1; ki <= RD; ++ki)
-#pragma unroll
-                    for (int ri = 0; ri <= ki; ++ri) {
-                        const int ai = ki - ri, bi = ri, row = ki * (ki + 1) / 2 + ri - 1;
-                        double v = 0.0;
-                        if (ai >= 2) v = (double)(ai * (ai - 1)) * mc[(ki - 2) * (ki - 1) / 2 + bi];
-                        if (bi >= 2) v = __builtin_fma((double)(bi * (bi - 1)), mc[(ki - 2) * (ki - 1) / 2 + bi - 2], v);
-                        col[row] = nih2 * v;
-                    }
-            }
         } else if (l < CBS) {
-            if (C::USE_PRE) {
+            // -int_T phi_c lap(phi_i) = -(2/h)^2 (a (a-1) MOM(a-2+a', b+b') + b (b-1) MOM(a+a', b-2+b')) for phi_i = bx^a by^b,
+            // phi_c = bx^a' by^b'.  In the graded ordering the moment of phi_c times the monomial m of degree d sits at
+            // c + d (a' + b') + m: one LDS read per monomial of degree <= recdeg - 2, the rest is in registers.
+            constexpr int NDM = RD >= 2 ? P2(RD - 2) : 1;
+            double mc[NDM];
+            int kcv = 0;                                 // a' + b' (per cell from the opaque lane index: no register held)
 #pragma unroll
-                for (int i = 0; i < NR; ++i) col[i] = 0.0;
-            } else {
-                const double *stc = S + C::oST + 1 + c * LD;
+            for (int k = 1; k <= C::CD; ++k) kcv += l >= k * (k + 1) / 2 ? 1 : 0;
+            const double *mg = S + C::oMG + l;
+            mc[0] = 0.0;
 #pragma unroll
-                for (int i = 0; i + 1 < NR; i += 2) {
-                    const double2 v = lds_pair(stc + i);
-                    col[i] = v.x; col[i + 1] = v.y;
+            for (int d = 0; d + 2 <= RD; ++d)
+#pragma unroll
+                for (int bm = 0; bm <= d; ++bm) mc[d * (d + 1) / 2 + bm] = mg[d * kcv + d * (d + 1) / 2 + bm];
+            const double nih2 = -(ih * ih);
+#pragma unroll
+            for (int ki = 1; ki <= RD; ++ki)
+#pragma unroll
+                for (int ri = 0; ri <= ki; ++ri) {
+                    const int ai = ki - ri, bi = ri, row = ki * (ki + 1) / 2 + ri - 1;
+                    double v = 0.0;
+                    if (ai >= 2) v = (double)(ai * (ai - 1)) * mc[(ki - 2) * (ki - 1) / 2 + bi];
+                    if (bi >= 2) v = __builtin_fma((double)(bi * (bi - 1)), mc[(ki - 2) * (ki - 1) / 2 + bi - 2], v);
+                    col[row] = nih2 * v;
                 }
-                if (NR & 1) col[NR - 1] = stc[NR - 1];
-            }
-#pragma unroll
-            for (int pf = 0; pf < NFP; ++pf) {
-                const double ph = S[C::oPHF + pf * RBS + c];
-                const double *dn = S + C::oDN + pf * NRP;
-#pragma unroll
-                for (int i = 0; i + 1 < NR; i += 2) {
-                    const double2 v = lds_pair(dn + i);
-                    col[i] = __builtin_fma(-v.x, ph, col[i]);
-                    col[i + 1] = __builtin_fma(-v.y, ph, col[i + 1]);
-                }
-                if (NR & 1) col[NR - 1] = __builtin_fma(-dn[NR - 1], ph, col[NR - 1]);
-            }
         }
         if (a.ablate & 4u) {
         } else if (l < CBS) {
         } else {
-            if (PA_S3B_BATCH) {
-                // the rows of the face's table in batches of QG points (<= 32 doubles), one LDS round trip each, then the products
-                typedef double v2d_ __attribute__((ext_vector_type(2)));
-                constexpr int QG = imax(1, imin(NFQ, 32 / NRP));
-#pragma unroll
-                for (int i = 0; i < NR; ++i) col[i] = 0.0;
-#pragma unroll
-                for (int q0 = 0; q0 < NFQ; q0 += QG) {
-                    v2d_ dnv[QG][NRP / 2];
-#pragma unroll
-                    for (int q = q0; q < q0 + QG; ++q)
-#pragma unroll
-                        for (int i = 0; i < NRP; i += 2)
-                            if (q < NFQ) dnv[q - q0][i / 2] = *reinterpret_cast<const v2d_ *>(S + C::oDN + (fc * NFQ + q) * NRP + i);
-#pragma unroll
-                    for (int i = 0; i < NR; ++i)
-#pragma unroll
-                        for (int q = q0; q < q0 + QG; ++q)
-                            if (q < NFQ) col[i] = __builtin_fma((i & 1) ? dnv[q - q0][i / 2].y : dnv[q - q0][i / 2].x, fbq[q], col[i]);
-                }
-            } else {
+            // the rows of the face's table in batches of QG points (<= 32 doubles), one LDS round trip each, then the products
+            typedef double v2d_ __attribute__((ext_vector_type(2)));
+            constexpr int QG = imax(1, imin(NFQ, 32 / NRP));
 #pragma unroll
             for (int i = 0; i < NR; ++i) col[i] = 0.0;
 #pragma unroll
-            for (int q = 0; q < NFQ; ++q) {
-                const double *dn = S + C::oDN + (fc * NFQ + q) * NRP;
+            for (int q0 = 0; q0 < NFQ; q0 += QG) {
+                v2d_ dnv[QG][NRP / 2];
 #pragma unroll
-                for (int i = 0; i + 1 < NR; i += 2) {
-                    const double2 v = lds_pair(dn + i);
-                    col[i] = __builtin_fma(v.x, fbq[q], col[i]);
-                    col[i + 1] = __builtin_fma(v.y, fbq[q], col[i + 1]);
-                }
-                if (NR & 1) col[NR - 1] = __builtin_fma(dn[NR - 1], fbq[q], col[NR - 1]);
-            }
+                for (int q = q0; q < q0 + QG; ++q)
+#pragma unroll
+                    for (int i = 0; i < NRP; i += 2)
+                        if (q < NFQ) dnv[q - q0][i / 2] = *reinterpret_cast<const v2d_ *>(S + C::oDN + (fc * NFQ + q) * NRP + i);
+#pragma unroll
+                for (int i = 0; i < NR; ++i)
+#pragma unroll
+                    for (int q = q0; q < q0 + QG; ++q)
+                        if (q < NFQ) col[i] = __builtin_fma((i & 1) ? dnv[q - q0][i / 2].y : dnv[q - q0][i / 2].x, fbq[q], col[i]);
             }
         }
         wave_sync();
-        if (SPC > 1 && l < CBS && !(a.ablate & 4u)) {
-            const double *gc = S + C::oGRC + c * NRP;
-#pragma unroll
-            for (int i = 0; i + 1 < NR; i += 2) {
-                const double2 v = lds_pair(gc + i);
-                col[i] = v.x; col[i + 1] = v.y;
-            }
-            if (NR & 1) col[NR - 1] = gc[NR - 1];
-        }
 
-        // ================= S4/S5: L L^T = gr_lhs (in place in ST[1:,1:]) ; Y = L^-1 gr_rhs  hho.hpp:63,92
+        // ================= S4/S5: Y = L^-1 gr_rhs, L = chol(gr_lhs) from the record  hho.hpp:63,92
         PA_TICK(2);
-        if (PA_PRIO_OUT >= 0 && PA_PRIO_MID >= 0) __builtin_amdgcn_s_setprio(PA_PRIO_MID >= 0 ? PA_PRIO_MID : 0);
+        __builtin_amdgcn_s_setprio(PRIO_MID);
         PA_MARK("S4");
-        double *LG = S + C::oLG;                 // without the pre-pass: stiff[1:,1:], symmetric: row-major == column-major
+        double *LG = S + C::oLG;                 // image of L (without DPPFWD)
         double lreg[C::NLR];                     // DPPFWD: [packed L | 1 / diagonal], element e in lane e mod 16 of a row, register e / 16
         int bad = bad_pre;
-        // blocked form where its extra registers are free (measured: -3 % at k = 1; +4 % at k = 2, where it
-        // pushes the kernel into spills)
-        if (!C::USE_PRE && !(a.ablate & 8u)) bad = NR <= 6 ? lds_cholesky_blocked<NR, LD, G>(LG, l) : lds_cholesky<NR, LD, G>(LG, l);
-        if (C::USE_PRE) {
-            if (!(a.ablate & 16u)) {
-                if (C::DPPFWD) {
+        if (!(a.ablate & 16u)) {
+            if (C::DPPFWD) {
 #pragma unroll
-                    for (int t = 0; t < C::NLR; ++t) lreg[t] = S[C::oREC + (lane & 15) + 16 * t];      // (reads past NL + NR stay inside the record)
-                    dpp_forward<NR, C::NLR>(lreg, col);
-                } else if (PA_FWD_CAP > 0) lds_forward_rd_batched<NR, LD, PA_FWD_CAP>(LG, S + C::oRCP, col);
-                else lds_forward_rd<NR, LD>(LG, S + C::oRCP, col);
-                if (!C::LAPG) {
-                // cell column c >= 1: gr_rhs[:, c] = stiff[1:, c] - F_c and L^-1 stiff[1:, c] = L^T e_(c-1): add row c-1 of L
-                // (the image is zero above the diagonal; the other columns add its zero row NR)
-                const double *lr = LG + ((l >= 1 && l < CBS) ? l - 1 : NR) * LD;
-#pragma unroll
-                for (int i = 0; i + 1 < NR; i += 2) {
-                    const double2 v = lds_pair(lr + i);
-                    col[i] += v.x;
-                    col[i + 1] += v.y;
-                }
-                if (NR & 1) col[NR - 1] += lr[NR - 1];
-                }
-            }
-        } else if (!(a.ablate & 16u)) lds_forward<NR, LD>(LG, col);
+                for (int t = 0; t < C::NLR; ++t) lreg[t] = S[C::oREC + (lane & 15) + 16 * t];      // (reads past NL + NR stay inside the record)
+                dpp_forward<NR, C::NLR>(lreg, col);
+            } else if (PA_FWD_CAP > 0) lds_forward_rd_batched<NR, LD, PA_FWD_CAP>(LG, S + C::oRCP, col);
+            else lds_forward_rd<NR, LD>(LG, S + C::oRCP, col);
+        }
         PA_TICK(11);
         // The trace columns are formed only now (not next to the gr_rhs columns in S3b): they stay
         // out of the register budget of the factorization.  They read the face tables of region Q,
@@ -1855,7 +1076,7 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
             for (int r = 0; r < UR; ++r) {
                 const double *ph = S + C::oPHF + (upk[r] & 0xfffu);
 #pragma unroll
-                for (int q = 0; q < NFQ; ++q) uph[r][q] = PA_LDS_NOPAIR ? lds_single(ph + q * RBS) : ph[q * RBS];
+                for (int q = 0; q < NFQ; ++q) uph[r][q] = ph[q * RBS];
                 usu[r] = S[C::oSU + (upk[r] >> 24)];
             }
             // (every read of the units first: one LDS round trip)
@@ -1906,8 +1127,7 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
         for (int k = 0; k < NR; ++k) ycol[k] = col[k];
         if (C::GENERAL_FANCY || a.oper != nullptr) {
             if (C::DPPFWD) dpp_backward<NR, C::NLR>(lreg, col);
-            else if (C::USE_PRE) lds_backward_rd<NR, LD>(LG, S + C::oRCP, col);
-            else lds_backward<NR, LD>(LG, col);            // col = oper[:, c]
+            else lds_backward_rd<NR, LD>(LG, S + C::oRCP, col);      // col = oper[:, c]
             if (a.oper != nullptr && valid && l < MS) {
                 double *dst = a.oper + rel(NR * MS) + (size_t)c * NR;
 #pragma unroll
@@ -1917,7 +1137,6 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
 
         PA_TICK(3);
         // ================= S6: column c of U ==========================================
-        if (PA_PRIO_OUT >= 0 && PA_PRIO_S6 >= 0) __builtin_amdgcn_s_setprio(PA_PRIO_S6 >= 0 ? PA_PRIO_S6 : 0);
         PA_MARK("S6");
         if (UNIT_U && !(a.ablate & 32u)) {
 #pragma unroll
@@ -1947,20 +1166,12 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
                     double s = 0.0;
 #pragma unroll
                     for (int k = 0; k < NR; ++k)
-                        s += (C::USE_PRE ? S[C::oMRl + (1 + k) * CBS + i] : S[C::oMA + i + (1 + k) * LD]) * col[k];
+                        s += S[C::oMRl + (1 + k) * CBS + i] * col[k];
                     pr[i] = s;
                 }
-                int badm;
-                if (C::USE_PRE) {          // chol(M1) comes with the record
-                    badm = (int)S[C::oSU + 17];
-                    lds_forward_rd<CBS, C::LDM>(S + C::oMCl, S + C::oMCRl, pr);
-                    lds_backward_rd<CBS, C::LDM>(S + C::oMCl, S + C::oMCRl, pr);
-                } else {
-                    wave_sync();
-                    badm = lds_cholesky<CBS, LD, G>(S + C::oMA, l);
-                    lds_forward<CBS, LD>(S + C::oMA, pr);
-                    lds_backward<CBS, LD>(S + C::oMA, pr);
-                }
+                const int badm = (int)S[C::oSU + 17];      // chol(M1) comes with the record
+                lds_forward_rd<CBS, C::LDM>(S + C::oMCl, S + C::oMCRl, pr);
+                lds_backward_rd<CBS, C::LDM>(S + C::oMCl, S + C::oMCRl, pr);
                 if (badm && !bad) bad = 100 + badm;
 #pragma unroll
                 for (int i = 0; i < CBS; ++i) pr[i] = (i == c ? 1.0 : 0.0) - pr[i];
@@ -2000,12 +1211,11 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
         }
         wave_sync();
         PA_TICK(4);
-        // region P is free (L, reciprocals, scalars all consumed): next cell's record -- in the condensed mode only after
-        // S9, whose image lies over P as well
+        // region P is free (L, reciprocals, scalars all consumed) once the face scales below are read: next cell's record
         // corner tile on the vector pipe, short form: its U term needs the face scale, which the next record is about to replace
         double cornerU = 0.0;
         int cic = 0, cjc = 0;
-        if (C::CORNER_VALU && !SPLIT && !PA_LC_VALU) {
+        if (C::CORNER_VALU && !SPLIT) {
             uint32_t cpk = corner_pk;
             asm volatile("" : "+v"(cpk));
             cic = (int)(cpk & 0xffu); cjc = (int)((cpk >> 8) & 0xffu);       // cic <= cjc
@@ -2022,7 +1232,7 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
                 t11s[gi] = su * su;
             }
         }
-        if (C::USE_PRE && (!COND || C::COND_OWN_P) && (!SELF || ib + 1 < nbc)) rec_deposit();
+        rec_deposit();
         // condensed mode: the cell's right-hand side (lanes < CBS) and, for the recovery, its face unknowns (lanes < NF),
         // one value per lane, in flight during the product
         double fT_l = 0.0, uF_l = 0.0;
@@ -2038,8 +1248,8 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
         // lane feeds 16 FMAs (the vector form reads one LDS double per FMA).  All 64 lanes work on one
         // cell at a time; the CPW cells of the wavefront are processed in turn.
         PA_TICK(5);
-        if (PA_PRIO_OUT >= 0) __builtin_amdgcn_s_setprio(PA_PRIO_OUT >= 0 ? PA_PRIO_OUT : 0);
-        if (!SPLIT && !PA_LC_VALU) {
+        __builtin_amdgcn_s_setprio(PRIO_OUT);
+        if (!SPLIT) {
             PA_MARK("S7m");
             constexpr int NTL = (MS + 15) / 16;              // column tiles
             constexpr int KS = (C::ZR + 3) / 4;              // k-steps
@@ -2047,14 +1257,13 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
             typedef double v4d __attribute__((ext_vector_type(4)));
             const int kk = lane >> 4, jj = lane & 15;
             constexpr bool DIRECT = C::DIRECT_STORE && !COND;      // condensed mode: always through the LDS image
-            constexpr bool EARLY_OUT = PA_EARLY_OUT && !DIRECT && !COND && C::CPW > 1;
             constexpr int OS = COND ? C::LDI : MS;                 // stride of the image
             // Through the image with an even stride: the columns of Z are fed to the tiles in the order pi(i) = 4 (i & 3) + (i >> 2),
             // both operands alike, so that the lane's four accumulators D[kk + 4 r][jj] are lc[16 I + 4 kk + r][16 J + pi(jj)], r = 0..3:
             // FOUR CONSECUTIVE rows of one column of the image -- two 16-byte LDS writes instead of four 8-byte ones, and the 16 lanes
             // of a write cycle (kk fixed, pi(jj) = all 16 columns) fall on 16 different bank quads where the 8-byte column writes at
             // stride 22 met two by two.  The mirror copy of an off-diagonal tile stays 8-byte writes.
-            constexpr bool ACC_PERM = PA_ACC_PERM && !DIRECT && !COND && OS % 2 == 0;      // (condensed k = 2: 8 spilled registers with it, and no gain)
+            constexpr bool ACC_PERM = !DIRECT && !COND && OS % 2 == 0;      // (condensed k = 2: 8 spilled registers with it, and no gain)
             const int pj = ACC_PERM ? 4 * (jj & 3) + (jj >> 2) : jj;
             static_assert(!T11_SHORT || ACC_PERM == ACC_PERM_, "the per-lane constants of tile (1,1) assume this tile's lane -> (row, column) map");
             const bool want_image = COND || a.lc != nullptr;
@@ -2105,13 +1314,11 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
                             const int col = 16 * t + pj;
                             // (decided at compile time wherever the whole tile row / k-step is inside Z)
                             const bool rok = 4 * ks + 3 < C::ZR || k < C::ZR, cok = 16 * t + 15 < MS || col < MS;
-                            // (a volatile read stays ONE ds_read_b64 -- 64 banks, two groups of 32 lanes, 2 cycles --; the compiler otherwise pairs the
-                            // reads of two k-steps into ds_read2_b64: 32 banks, groups of 16 lanes, 8 cycles, and columns j, j + 8 on one bank at this stride)
-                            const double v = PA_LDS_NOPAIR ? lds_single(Zg + ((rok && cok) ? k + col * ZS : 0)) : Zg[(rok && cok) ? k + col * ZS : 0];
+                            const double v = Zg[(rok && cok) ? k + col * ZS : 0];
                             // A lane beyond the last COLUMN of Z feeds only the rows / columns >= MS of the tiles (D[i][j] takes row i of
                             // A and column j of B), which are never stored: whatever it read (element 0 of Z) may stay.  A lane beyond the
                             // last ROW of Z would add to entries that are.
-                            z[t] = (PA_ZCOL_NOSEL ? rok : (rok && cok)) ? v : 0.0;
+                            z[t] = rok ? v : 0.0;
                         }
                         // tile (1,1), short form: rows of Y only (the last of their k-steps may also hold rows of U: masked)
                         constexpr int KSY = cdiv(NRP, 4);
@@ -2201,36 +1408,10 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
                             }
                         }
                 }
-                // lc only: the image of cell gi goes out at once, all 64 lanes on it (1 KB per store instruction), while the
-                // matrix instructions of the next cell run -- not both cells in one burst of stores at the end of the pass
-                if (EARLY_OUT && a.lc != nullptr && !(a.ablate & 128u)) {
-                    if (C::CORNER_VALU && g == gi && l < C::NCORNER * (C::NCORNER + 1) / 2) {
-                        Og[(16 + cic) + (16 + cjc) * OS] = corner;
-                        Og[(16 + cjc) + (16 + cic) * OS] = corner;
-                    }
-                    wave_sync();
-                    if (base + gi < a.n) {
-                        double *o = a.lc + ((a.ablate & 1024u) ? lblock * C::CPW + gi : base + gi) * (size_t)(MS * MS);
-                        constexpr int NPAIR = MS * MS / 2, NIT = cdiv(NPAIR, 64);
-                        typedef double v2d_ __attribute__((ext_vector_type(2)));
-                        v2d_ img[NIT];
-#pragma unroll
-                        for (int it = 0; it < NIT; ++it) {
-                            const int e = it * 64 + lane;
-                            img[it] = *reinterpret_cast<const v2d_ *>(Og + 2 * (((it + 1) * 64 <= NPAIR || e < NPAIR) ? e : 0));
-                        }
-#pragma unroll
-                        for (int it = 0; it < NIT; ++it) {
-                            const int e = it * 64 + lane;
-                            if ((it + 1) * 64 <= NPAIR || e < NPAIR) *reinterpret_cast<v2d_ *>(o + 2 * e) = img[it];
-                        }
-                        if (((MS * MS) & 1) && lane == 0) o[MS * MS - 1] = Og[MS * MS - 1];
-                    }
-                }
                 }
                 PA_TICK(7 + 2 * (gi & 1));
             }
-            if (C::CORNER_VALU && want_image && !EARLY_OUT && !(a.ablate & 128u) && l < C::NCORNER * (C::NCORNER + 1) / 2) {
+            if (C::CORNER_VALU && want_image && !(a.ablate & 128u) && l < C::NCORNER * (C::NCORNER + 1) / 2) {
                 if (DIRECT) {
                     if (valid) {
                         double *o = a.lc + rel(MS * MS);
@@ -2253,7 +1434,6 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
                                                       a.lc != nullptr ? a.lc + rel(MS * MS) : nullptr);
                 PA_TICK(13);
                 wave_sync();      // every read of the image is done
-                if (C::USE_PRE && !C::COND_OWN_P && (!SELF || ib + 1 < nbc)) { rec_deposit(); wave_sync(); }
             } else if (COND) {
                 // ================= S9 (condensed mode): eliminate the cell unknowns in the LDS image ==================
                 // Row i of the symmetric (MS + 1) x (MS + 1) matrix  M = [A_TT A_TF f_T; A_FT A_FF 0; f_T^T 0 0]  belongs to
@@ -2277,7 +1457,7 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
                 }
                 if (NPV & 1) row[NPV - 1] = A[i * LDI + NPV - 1];
                 int badc = 0;
-                constexpr bool COND_DPP = PA_COND_DPP && NPV <= 16 && MS + 1 <= 32 && G <= 32;
+                constexpr bool COND_DPP = NPV <= 16 && MS + 1 <= 32 && G <= 32;
                 if (COND_DPP) {
                     // The chain in registers: lane q of each row of 16 lanes holds image rows q and q + 16 (both rows of 16 lanes
                     // of a 32-lane group hold the same pairs), so every pivot row -- there are at most 16 -- sits in lane j of the
@@ -2295,7 +1475,7 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
                         if (TWO) { const double2 vb = lds_pair(A + iB * LDI + k); rB[k] = vb.x; rB[k + 1] = vb.y; }
                     }
                     if (NPV & 1) { rA[NPV - 1] = A[iA * LDI + NPV - 1]; if (TWO) rB[NPV - 1] = A[iB * LDI + NPV - 1]; }
-                    if (NPV >= PA_COND_RL_MIN) cond_dpp_chain_rl<NPV, TWO>(rA, rB, rdiag, badc, q);
+                    if (NPV >= COND_RL_MIN) cond_dpp_chain_rl<NPV, TWO>(rA, rB, rdiag, badc, q);
                     else cond_dpp_chain<NPV, TWO>(rA, rB, rdiag, badc, q);
                     // back to the image (the diagonal holds 1 / L[j][j]); one row of 16 lanes writes
                     if ((G == 16 || l < 16)) {
@@ -2309,8 +1489,6 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
                     for (int k = 0; k < NPV; ++k) row[k] = (TWO && l >= 16) ? rB[TWO ? k : 0] : rA[k];
                     wave_sync();
                     }
-                } else if (PA_COND_NB > 1) {
-                    if (!(a.ablate & 256u)) badc = lds_partial_cholesky<NPV, MS + 1, PA_COND_NB, LDI>(A, l, row);
                 } else if (!(a.ablate & 256u)) {
 #pragma unroll
                 for (int j = 0; j < NPV; ++j) {
@@ -2332,7 +1510,7 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
                     double *stg = S + C::oOUT + C::oSTG;
                     const int ip = l - CBS;
                     const bool frow = l >= CBS && l < MS;
-                    constexpr bool SCHUR_MFMA = NF >= PA_COND_SCHUR_MFMA_MIN && NF <= 16;
+                    constexpr bool SCHUR_MFMA = NF >= COND_SCHUR_MFMA_MIN && NF <= 16;
                     if (a.ablate & 512u) {
                     } else if (SCHUR_MFMA) {
                         // W^T W on the matrix pipe, all 64 lanes on one cell at a time: W[k][j] = L[CBS + j][k] is both
@@ -2406,11 +1584,8 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
                     if (valid && a.uT != nullptr && l < CBS) a.uT[rel(CBS) + l] = t;
                 }
                 wave_sync();      // every read of the image is done
-                if (C::USE_PRE && !C::COND_OWN_P && (!SELF || ib + 1 < nbc)) { rec_deposit(); wave_sync(); }      // the next cell's record, into its place in region P
             } else if (DIRECT) {
                 wave_sync();      // the next cell's tables overwrite Z
-            } else if (EARLY_OUT) {
-                wave_sync();      // the next cell's tables overwrite the images
             } else {
                 if (a.lc != nullptr && !(a.ablate & 128u)) {
                     wave_sync();
@@ -2442,27 +1617,21 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
                 wave_sync();
             }
         } else {
-        // ================= S7: lc = Z^T Z, entries (c, c + d mod MS) ==================
+        // ================= S7 (data and stab apart): Z^T Z, entries (c, c + d mod MS) ==
         PA_MARK("S7");
-        double acc_d[ND], acc_s[SPLIT ? ND : 1];
+        double acc_d[ND], acc_s[ND];
 #pragma unroll
-        for (int d = 0; d < ND; ++d) { acc_d[d] = 1.0; if (SPLIT) acc_s[d] = 1.0; }
+        for (int d = 0; d < ND; ++d) { acc_d[d] = 1.0; acc_s[d] = 1.0; }
         if (!(a.ablate & 64u)) {
             int cp = c;
 #pragma unroll
             for (int d = 0; d < ND; ++d) {
                 const double *zc = S + C::oZ + cp * ZS;
                 double s = lds_dotadd<NR>(0.0, zc, ycol);
-                if (SPLIT) {
-                    double u = 0.0;
-                    if (C::HAS_STAB) u = lds_dotadd<NF>(0.0, zc + NRP, ucol);
-                    asm volatile("" : "+v"(s), "+v"(u));     // pin: keep the FMAs next to their LDS reads
-                    acc_d[d] = s; acc_s[d] = u;
-                } else {
-                    if (C::HAS_STAB) s = lds_dotadd<NF>(s, zc + NRP, ucol);
-                    asm volatile("" : "+v"(s));
-                    acc_d[d] = s;
-                }
+                double u = 0.0;
+                if (C::HAS_STAB) u = lds_dotadd<NF>(0.0, zc + NRP, ucol);
+                asm volatile("" : "+v"(s), "+v"(u));     // pin: keep the FMAs next to their LDS reads
+                acc_d[d] = s; acc_s[d] = u;
                 cp = (cp + 1 == MS) ? 0 : cp + 1;
             }
         }
@@ -2471,15 +1640,14 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
         // ================= S8: mirror through LDS, stream to HBM ======================
         PA_MARK("S8");
 #pragma unroll
-        for (int which = 0; which < (SPLIT ? 3 : 1); ++which) {
+        for (int which = 0; which < 3; ++which) {
             double *dst = which == 0 ? a.lc : which == 1 ? a.data : a.stab;
             if (dst == nullptr || (a.ablate & 128u)) continue;
             if (l < MS) {
                 int cp = c;
 #pragma unroll
                 for (int d = 0; d < ND; ++d) {
-                    double v = acc_d[d];
-                    if (SPLIT) v = which == 0 ? acc_d[d] + acc_s[d] : which == 1 ? acc_d[d] : acc_s[d];
+                    const double v = which == 0 ? acc_d[d] + acc_s[d] : which == 1 ? acc_d[d] : acc_s[d];
                     S[C::oOUT + c + cp * MS] = v;
                     S[C::oOUT + cp + c * MS] = v;
                     cp = (cp + 1 == MS) ? 0 : cp + 1;
@@ -2511,9 +1679,6 @@ __global__ __launch_bounds__(64, (MODE == MODE_SPLIT && C::WAVES > 3) ? 3 : C::W
         if (valid && a.info != nullptr && l == 0) a.info[rel(1)] = bad;
         PA_TICK(10);
     }
-#if PA_SELF_PRE
-    }
-#endif
 #ifdef PA_STAGE_CLOCK
     if (a.dbg != nullptr && lane == 0)
         for (int i = 0; i < PA_NSTAGE; ++i) a.dbg[(size_t)blockIdx.x * PA_NSTAGE + i] = tk_sum[i];

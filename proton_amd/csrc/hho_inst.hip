@@ -31,6 +31,8 @@
 #else
 #define PA_SMALL_OF(STAB, G) nullptr
 #endif
+// (the static_cast resolves the address of launch_pre where it stands, so that the pre-pass kernel is instantiated right behind the
+// lc-only kernel of its configuration: the order of the kernels in the code object)
 #define PA_ENTRY(STAB, G, COND)                                                                    \
     {PA_CD, PA_FD, PA_QUAD, STAB, G, &pa::launch_local_ops<pa::Cfg<PA_CD, PA_FD, PA_QUAD, STAB, G>, pa::MODE_LC>, \
      &pa::launch_local_ops<pa::Cfg<PA_CD, PA_FD, PA_QUAD, STAB, G>, pa::MODE_SPLIT>,                 \
@@ -38,10 +40,10 @@
      (int)(pa::Cfg<PA_CD, PA_FD, PA_QUAD, STAB, G>::LDS_DOUBLES * sizeof(double)),                  \
      "hho_local_ops<cd=" PA_STR(PA_CD) ",fd=" PA_STR(PA_FD) ",quad=" PA_STR(PA_QUAD) ",stab=" #STAB ",G=" #G ">",                \
      pa::Cfg<PA_CD, PA_FD, PA_QUAD, STAB, G>::WAVES,                                                \
-     pa::Cfg<PA_CD, PA_FD, PA_QUAD, STAB, G>::USE_PRE ? &pa::launch_pre<pa::Cfg<PA_CD, PA_FD, PA_QUAD, STAB, G>> : nullptr, \
+     static_cast<pa::pre_launcher>(&pa::launch_pre<pa::Cfg<PA_CD, PA_FD, PA_QUAD, STAB, G>>),       \
      pa::Cfg<PA_CD, PA_FD, PA_QUAD, STAB, G>::Pre::NPRE,                                            \
      PA_SMALL_OF(STAB, G), "hho_small_ops<cd=" PA_STR(PA_CD) ",fd=" PA_STR(PA_FD) ",quad=" PA_STR(PA_QUAD) ",stab=" #STAB ">", \
-     pa::Cfg<PA_CD, PA_FD, PA_QUAD, STAB, G>::SELF_PRE ? 1 : 0, COND}
+     COND}
 #define PA_ENTRIES_G(G) PA_ENTRY(0, G, PA_COND_NONE), PA_ENTRY(1, G, PA_COND_OF(1, G)), PA_ENTRY(2, G, PA_COND_OF(2, G))
 
 static const pa::KernelEntry k_entries[] = {

@@ -21,12 +21,17 @@
 #endif
 namespace pa {
 
+struct PreArgs {
+    const QuadTables *tab;
+    const double *points;
+    const uint32_t *ptids;
+    size_t first, n;           // cells first .. first+n-1; record of cell first+i: tile i / 8, slot i % 8 (see the kernel)
+    double *pre;
+};
 
 // The head of ONE cell, all of it in the registers of the calling lane; `out` = where pair 0 of the cell's record goes, the
 // other 16-byte pairs follow at a stride of 16 doubles (the tiles of 8 records described below).  Called by the pre-pass
-// kernel (one thread per cell of a piece) and, in the instances built with PA_SELF_PRE, by the cooperative kernel itself: there a
-// wavefront stops every 64 / CPW passes and forms the heads of the 64 cells it will visit next, one per lane, into a ring of 64
-// records of its own (hho_device.hpp).
+// kernel (one thread per cell of a piece).
 template <class C>
 __device__ __forceinline__ void cell_pre_record(const PreArgs &a, size_t cell, double *out)
 {
@@ -134,7 +139,7 @@ __device__ __forceinline__ void cell_pre_record(const PreArgs &a, size_t cell, d
         }
     }
 
-    // the moments of degree <= recdeg - 2 + celdeg travel: the consumer forms the cell columns of gr_rhs from them (Cfg::LAPG)
+    // the moments of degree <= recdeg - 2 + celdeg travel: the consumer forms the cell columns of gr_rhs from them (hho_device.hpp, S3b)
 #pragma unroll
     for (int e = 0; e < C::NMG; e += 2) put(PL::oSCAL + 18 + e, double2{mom[e], e + 1 < C::NMG ? mom[e + 1 < NMOM ? e + 1 : 0] : 0.0});
 
