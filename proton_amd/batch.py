@@ -274,14 +274,16 @@ class BatchAssembler:
         self.ctx.take_local_data(di, first, n, solution.data_ptr(), _ptr(g), out.data_ptr())
         return out
 
-    def project_function(self, cd, fd, fn, quad=capi.QUAD_TENSOR, dinc=0, cell_fvals=None, face_fvals=None, first=0, n=None):
-        """project_function(msh, cl, hdi, f, di) (utils.hpp:199-227) -> n x msize."""
+    def project_function(self, cd, fd, fn, quad=capi.QUAD_TENSOR, dinc=0, cell_fvals=None, face_fvals=None, first=0, n=None,
+                         want_info=False):
+        """project_function(msh, cl, hdi, f, di) (utils.hpp:199-227) -> n x msize [, info: n, the cell mass matrix's pivot flag]."""
         di, _ = capi.degree_info(cd, fd)
         n = self.ncells - first if n is None else n
         ms = (di.cell_deg + 1) * (di.cell_deg + 2) // 2 + 4 * (di.face_deg + 1)
         out = torch.empty((n, ms), dtype=torch.float64, device=self.device)
-        self.ctx.project_function(di, quad, dinc, fn, _ptr(cell_fvals), _ptr(face_fvals), first, n, out.data_ptr(), None)
-        return out
+        info = torch.empty(n, dtype=torch.int32, device=self.device) if want_info else None
+        self.ctx.project_function(di, quad, dinc, fn, _ptr(cell_fvals), _ptr(face_fvals), first, n, out.data_ptr(), _ptr(info))
+        return (out, info) if want_info else out
 
     def energy_form(self, cd, fd, lc, u, v=None):
         """per-cell (u - v)^T lc (u - v)."""

@@ -63,8 +63,8 @@ __global__ __launch_bounds__(256) void dirichlet_data_kernel(const QuadTables *t
 #pragma unroll
         for (int q = 0; q < NFQ; ++q) {
             const double tq = tab->gauss_x[NFQ][q];
-            const double px = 0.5 * (1 - tq) * a.x + 0.5 * (1 + tq) * b.x;    // quadratures.hpp:420-428
-            const double py = 0.5 * (1 - tq) * a.y + 0.5 * (1 + tq) * b.y;
+            double px, py;
+            face_point(a, b, tq, px, py);                                     // quadratures.hpp:420-428
             const double fv = fn == FN_SAMPLED ? fvals[(size_t)t * NFQ + q] : builtin_fn(fn, px, py);
 #pragma unroll
             for (int k = 0; k < FBS; ++k) x[k] += ft.cw[q][k] * fv;
@@ -100,8 +100,7 @@ static __global__ void face_qpoints_kernel(const QuadTables *tab, const double *
     for (int q = 0; q < nfq; ++q) {
         const double tq = tab->gauss_x[nfq][q];
         double *dst = xyw + ((size_t)t * nfq + q) * 3;
-        dst[0] = 0.5 * (1 - tq) * a.x + 0.5 * (1 + tq) * b.x;
-        dst[1] = 0.5 * (1 - tq) * a.y + 0.5 * (1 + tq) * b.y;
+        face_point(a, b, tq, dst[0], dst[1]);
         dst[2] = tab->gauss_w[nfq][q] * len * 0.5;
     }
 }
@@ -225,8 +224,8 @@ __global__ __launch_bounds__(256) void face_project_kernel(const QuadTables *tab
     }
     for (int q = 0; q < nfq; ++q) {
         const double tq = tab->gauss_x[nfq][q], wq = tab->gauss_w[nfq][q];
-        const double px = 0.5 * (1 - tq) * a.x + 0.5 * (1 + tq) * b.x;
-        const double py = 0.5 * (1 - tq) * a.y + 0.5 * (1 + tq) * b.y;
+        double px, py;
+        face_point(a, b, tq, px, py);
         const double fv = fn == FN_SAMPLED ? fvals[(size_t)f * nfq + q] : builtin_fn(fn, px, py);
         double phi[FBS];
         phi[0] = 1.0;

@@ -88,6 +88,18 @@ __device__ __forceinline__ void bilinear_point(const CellGeom &c, double xi, dou
     y = c.py[0] + __builtin_fma(n3, c.py[3] - c.py[0], __builtin_fma(n2, c.py[2] - c.py[0], n1 * (c.py[1] - c.py[0])));
 }
 
+// The face point of quadratures.hpp:420-428, 0.5 (1 - t) a + 0.5 (1 + t) b, taken from the endpoint a for the same reason: b - a
+// is exact for a face far from the origin, the point is within half an ulp and cannot leave an axis-parallel face.  (The two-term
+// sum, contracted, put a Gauss point of the face y = 1000 of a cell of side 1e-3 two ulps along the face off its place: 1.1e-10 in
+// the face projection of a function that varies across the cell, against 3.5e-12 from the vertex.)  S1 of hho_device.hpp and
+// hho_small.hpp form their points the same way.
+__device__ __forceinline__ void face_point(const double2 a, const double2 b, double t, double &x, double &y)
+{
+    const double cb = 0.5 * (1 + t);
+    x = __builtin_fma(cb, b.x - a.x, a.x);
+    y = __builtin_fma(cb, b.y - a.y, a.y);
+}
+
 // q-th point of integrate(msh, cl, degree): tensor Gauss (quadratures.hpp:311-375) or fan (:377-402)
 template <int QUAD>
 __device__ __forceinline__ void cell_qp(const QuadTables *tab, const CellGeom &c, int degree, int q,

@@ -268,7 +268,7 @@ def cell_rhs(pts, quad, degree, di, fn):
 def project_function(pts, ids, di, fn, quad=QUAD_TENSOR, dinc=0):
     pts, ids = _prep(pts, ids)
     out = np.zeros(di.msize)
-    cb = SCALAR_FN(lambda x, y, u: fn(x, y))
+    cb = lib().hho_builtin_fn(fn) if isinstance(fn, int) else SCALAR_FN(lambda x, y, u: fn(x, y))
     st = lib().hho_project_function(_dp(pts), _u64p(ids), di, quad, cb, None, dinc, _dp(out))
     return st, out
 
