@@ -588,6 +588,38 @@ int pa_fictdom_csr_assemble(pa_context *ctx, int face_deg, int where,
                             const double *d_cut_lc, const double *d_cut_rhs,
                             double *d_values, double *d_RHS,
                             double *d_lc /* may be NULL */, int32_t *d_info /* may be NULL */);
+/* The same system (assembly loop apps/cuthho/cuthho_square.cpp:881-905, solve :915-919, take_local_data :959-962) condensed to
+ * its face unknowns.  It is assembler<Mesh>'s over all cells, so numbering, pattern, fill, halo and expansion are the plain
+ * mesh's: pa_condensed_query / _csr_pattern / _csr_fill / _halo_pack / _expand_solution with hho_degree_info(face_deg + 1,
+ * face_deg) take the records this call writes.  d_cond: ncells x (nf(nf+1)/2 + nf), pa_condensed_ops_batch's layout
+ * (nf = 4 fbs).  An uncut cell's row is the fused condensed pass's (PA_QUAD_FAN, PA_STAB_NAIVE), BIT-IDENTICAL to
+ * pa_condensed_ops_batch fed the same right-hand side; an uncut cell outside `where` takes a zero right-hand side whatever
+ * d_rhs holds there (pa_fictdom_csr_assemble's rule).  A cut cell's row comes from d_cut_lc / d_cut_rhs
+ * (pa_cut_local_ops_batch) by an elimination in double-double -- Cholesky of A_TT, S = A_FF - A_FT A_TT^-1 A_TF and
+ * g = -A_FT A_TT^-1 f_T rounded to double once -- because A_TT of a sliver cell has condition numbers to 1e8, which cost the
+ * plain-double route (pa_static_condensation_packed_batch + pa_cut_merge_condensed) up to 7 digits.  d_rhs ncells x cbs or
+ * NULL = 0; d_cut_rhs ncut x cbs or NULL = 0; d_info ncells (may be NULL: the flags of the uncut formulas, for every cell);
+ * d_info_cut ncut (may be NULL): 200 + j + 1 for a failed pivot j of a cut cell's A_TT, else 0.  A cut kernel still out on the
+ * side stream (pa_context_set_cut_overlap) is joined first.  Deterministic call to call.  A slab context
+ * (pa_cut_preprocess_rows) is accepted: the work is cell-local.
+ * Refused before any buffer is touched, in pa_fictdom_csr_assemble's order: NULL ctx / d_cond, `where` not PA_LOC_NEGATIVE /
+ * PA_LOC_POSITIVE: PA_ERR_INVALID_ARG; no cut preprocessing: PA_ERR_NO_MESH; face_deg > 2: PA_ERR_QUADRATURE; cut cells without
+ * d_cut_lc: PA_ERR_INVALID_ARG. */
+int pa_fictdom_condensed_ops_batch(pa_context *ctx, int face_deg, int where,
+                                   const double *d_rhs, const double *d_cut_lc, const double *d_cut_rhs,
+                                   double *d_cond, int32_t *d_info /* may be NULL */, int32_t *d_info_cut /* may be NULL */);
+/* The cell unknowns of that system from its face solution (apps/cuthho/cuthho_square.cpp:881-905 assembled it, :915-919 solved
+ * it, :959-962 take_local_data reads it): u_T = A_TT^-1 (f_T - A_TF u_F) for every cell of the context.  Uncut cells: the pass
+ * of pa_condensed_recover_batch on the face values of pa_condensed_take_faces, bit-identical to those calls; cut cells: in
+ * double-double from d_cut_lc / d_cut_rhs.  u_F of a Dirichlet face is d_g (NULL = 0) for cut and uncut cells alike -- the plain
+ * assembler's rule; a cut cell on the boundary occurs with the line level set.  d_xF: the face solution (system_size of
+ * pa_condensed_query); d_full: the reference's full solution vector, cbs ncells_global + system_size, cells first -- the
+ * context's own cells (a slab: its rows, as pa_condensed_expand_solution) and a bit copy of d_xF behind the cells.  d_rhs,
+ * d_cut_lc, d_cut_rhs, `where`, the side stream and the refusals as pa_fictdom_condensed_ops_batch (d_full in place of d_cond;
+ * NULL d_xF: PA_ERR_INVALID_ARG). */
+int pa_fictdom_condensed_recover(pa_context *ctx, int face_deg, int where,
+                                 const double *d_rhs, const double *d_cut_lc, const double *d_cut_rhs,
+                                 const double *d_g, const double *d_xF, double *d_full);
 
 /* ---- cutHHO two-sided interface problem (`cuthho_square -i`, run_cuthho_interface
  * cuthho_square.cpp:1625-1846).  hho_degree_info(face_deg + 1, face_deg) (:1662). */

@@ -506,6 +506,58 @@ class BatchAssembler:
             self.ctx.cut_merge_condensed(fd, Sp.data_ptr(), g.data_ptr(), rec.data_ptr())
         return rec, rhs
 
+    def fictdom_condensed_records(self, fd, where=capi.LOC_NEGATIVE, rhs=None, cut_lc=None, cut_rhs=None, out=None):
+        """pa_fictdom_condensed_ops_batch on caller tensors: rhs [ncells, cbs] (uncut cells; those outside `where` count as
+        zero), cut_lc [ncut, msize, msize] / cut_rhs [ncut, cbs] (cut cells, eliminated in double-double)
+        -> dict(cond [ncells, nf(nf+1)/2 + nf] in condensed_ops' layout, info [ncells], info_cut [ncut])"""
+        nf = 4 * (fd + 1)
+        if out is None:
+            out = torch.empty((self.ncells, nf * (nf + 1) // 2 + nf), dtype=torch.float64, device=self.device)
+        info = torch.empty(max(self.ncells, 1), dtype=torch.int32, device=self.device)
+        info_cut = torch.empty(max(self.ncut, 1), dtype=torch.int32, device=self.device)
+        self.ctx.fictdom_condensed_ops(fd, where, _ptr(rhs), _ptr(cut_lc), _ptr(cut_rhs), out.data_ptr(), info.data_ptr(),
+                                       info_cut.data_ptr())
+        return {"cond": out, "info": info[:self.ncells], "info_cut": info_cut[:self.ncut]}
+
+    def fictdom_condensed_recover(self, fd, xF, where=capi.LOC_NEGATIVE, rhs=None, cut_lc=None, cut_rhs=None, g=None, full=None):
+        """pa_fictdom_condensed_recover: u_T of every cell of the context from the face solution xF (Dirichlet faces: g)
+        -> the full solution vector [cbs ncells_global + system_size], cells first (a slab fills its own cells)"""
+        di, _ = capi.degree_info(fd + 1, fd)
+        if full is None:
+            full = torch.zeros(self.ctx.assembler_query(di).system_size, dtype=torch.float64, device=self.device)
+        self.ctx.fictdom_condensed_recover(fd, where, _ptr(rhs), _ptr(cut_lc), _ptr(cut_rhs), _ptr(g), xF.data_ptr(), full.data_ptr())
+        return full
+
+    def fictdom_condensed_solve(self, fd, where=capi.LOC_NEGATIVE, rhs_fn=capi.FN_SIN_SIN_RHS, bcs_fn=capi.FN_SIN_SIN_SOL, tol=1e-13,
+                                g=None, max_iter=None, precond=True, overlap=False):
+        """cuthho_square.cpp:881-919 and :959-962 on the face-only system: the operators (pa_cut_uncut_rhs_batch,
+        pa_cut_local_ops_batch; overlap: on the context's side stream), the records, condensed_csr_pattern / condensed_csr_fill,
+        conjugated_gradient and the recovery -> (full solution vector, iterations, exit reason).  g: the boundary data
+        (default: dirichlet_data of bcs_fn).  Whole-mesh contexts."""
+        cd = fd + 1
+        if g is None:
+            g = self.dirichlet_data(fd, bcs_fn)
+        cut = None
+        if overlap:
+            self.ctx.set_cut_overlap(True)
+        try:
+            if self.ncut:
+                cut = self.cut_local_ops(fd, where, rhs_fn, bcs_fn, want=("lc", "rhs"))
+            rhs = torch.empty((self.ncells, (cd + 1) * (cd + 2) // 2), dtype=torch.float64, device=self.device)
+            self.ctx.cut_uncut_rhs(cd, where, rhs_fn, rhs.data_ptr())
+            cut_lc, cut_rhs = (None, None) if cut is None else (cut["lc"], cut["rhs"])
+            rec = self.fictdom_condensed_records(fd, where, rhs, cut_lc, cut_rhs)
+        finally:
+            if overlap:
+                self.ctx.set_cut_overlap(False)
+        rowptr, colind = self.condensed_csr_pattern(cd, fd)
+        values, b = self.condensed_csr_fill(cd, fd, rec["cond"], g)
+        if max_iter is None:
+            max_iter = 4 * b.numel()
+        xF, reason, iters, _ = self.conjugated_gradient(rowptr, colind, values, b, tol=tol, max_iter=max_iter, precond=precond)
+        full = self.fictdom_condensed_recover(fd, xF, where, rhs, cut_lc, cut_rhs, g)
+        return full, iters, reason
+
     # ---- cutHHO two-sided interface problem (cuthho_square -i) ------------------------------
     def interface_local_ops(self, fd, kappa=(1.0, 1.0), eta=5.0, rhs_fn=capi.FN_SIN_SIN_RHS, want_oper=False):
         """-> dict(lc, rhs: all cells, uncut formulas; lc_cut, rhs_cut [, oper_cut, data_cut]: cut cells)."""

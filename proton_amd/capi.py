@@ -47,6 +47,7 @@ EXPORTS = [
     "pa_comm_halo_exchange_start", "pa_comm_allgather_start", "pa_comm_allreduce_sum_start", "pa_comm_wait",
     "pa_comm_neighbour_exchange_start", "pa_conjugated_gradient_rows", "pa_comm_cg_transport", "pa_copy_to_host", "pa_copy_to_device", "pa_cut_uncut_rhs_batch",
     "pa_mesh_set_points", "pa_cut_preprocess_rows", "pa_cut_merge_condensed", "pa_fictdom_csr_assemble",
+    "pa_fictdom_condensed_ops_batch", "pa_fictdom_condensed_recover",
 ]
 
 
@@ -227,6 +228,8 @@ def lib():
     L.pa_cut_merge.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp]
     L.pa_cut_uncut_rhs_batch.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp]
     L.pa_fictdom_csr_assemble.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp]
+    L.pa_fictdom_condensed_ops_batch.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp]
+    L.pa_fictdom_condensed_recover.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp]
     L.pa_cut_query_tags.argtypes = [vp, vp, vp, vp]
     L.pa_cut_preprocess_agglomeration.argtypes = [vp, sz, sz, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(LevelSet), C.c_int]
     L.pa_cut_agglo_query.argtypes = [vp, vp, vp]
@@ -703,6 +706,16 @@ class Context:
         """the fictitious-domain system's CSR values / RHS in one pass: uncut cells from the operator kernel, cut cells from cut_lc / cut_rhs"""
         self._ck(self._L.pa_fictdom_csr_assemble(self.h, face_deg, where, rhs, g, cut_lc, cut_rhs, values, RHS, lc, info),
                  "pa_fictdom_csr_assemble")
+
+    def fictdom_condensed_ops(self, face_deg, where, rhs, cut_lc, cut_rhs, cond, info=None, info_cut=None):
+        """the fictitious-domain system's packed condensed records: uncut cells from the fused pass, cut cells in double-double"""
+        self._ck(self._L.pa_fictdom_condensed_ops_batch(self.h, face_deg, where, rhs, cut_lc, cut_rhs, cond, info, info_cut),
+                 "pa_fictdom_condensed_ops_batch")
+
+    def fictdom_condensed_recover(self, face_deg, where, rhs, cut_lc, cut_rhs, g, xF, full):
+        """the cell unknowns of every cell from the face solution, and xF behind them -> the full solution vector"""
+        self._ck(self._L.pa_fictdom_condensed_recover(self.h, face_deg, where, rhs, cut_lc, cut_rhs, g, xF, full),
+                 "pa_fictdom_condensed_recover")
 
     # ---- condensed mode --------------------------------------------------------------
     def condensed_ops(self, di, quad, stab, first, n, rhs, cond, info=None):

@@ -1,5 +1,5 @@
 // capi_cut.hip -- the C ABI of cutHHO on one side of the interface: preprocessing, the cut quadrature lists, the cut cells' local
-// operators, the merge into the uncut batches, and the fictitious-domain system in one pass.
+// operators, the merge into the uncut batches, and the fictitious-domain system in one pass or condensed to its face unknowns.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -12,6 +12,7 @@
 
 #include "context.hpp"
 #include "cut_device.hpp"
+#include "fictdom_condensed.hpp"
 
 // ---- cutHHO -----------------------------------------------------------------------------------
 static int cut_preprocess_impl(pa_context *ctx, size_t Nx, size_t Ny, double min_x, double max_x, double min_y, double max_y,
@@ -411,5 +412,75 @@ int pa_fictdom_csr_assemble(pa_context *ctx, int face_deg, int where, const doub
     st = run_local_ops(ctx, di, PA_QUAD_FAN, PA_STAB_NAIVE, 0, ctx->mesh.ncells, o);
     if (st != PA_OK) return st;
     PA_HIP(ctx, pa::asm_cut_scatter(ctx->stream, face_deg, o.scatter, ncut, ctx->cut.cut_cells.get(), d_cut_lc, d_cut_rhs, d_lc));
+    return PA_OK;
+}
+
+// ---- the same system condensed to its face unknowns: the cut cells' dense work in fictdom_condensed.hip -------------------------
+// The refusals of pa_fictdom_csr_assemble in its order (a slab is let through: the work is cell-local), then the side stream
+// joined.  `out`: the call's output buffer.
+static int fdcond_prepare(pa_context *ctx, int face_deg, int where, const void *out, const double *d_cut_lc, const pa::KernelEntry **e)
+{
+    if (!ctx || !out || (where != PA_LOC_NEGATIVE && where != PA_LOC_POSITIVE)) return PA_ERR_INVALID_ARG;
+    (void)hipSetDevice(ctx->device);
+    if (!ctx->cut.host || !ctx->mesh.points || !ctx->cut.cell_loc.get()) return PA_ERR_NO_MESH;
+    if (face_deg < 0) return PA_ERR_INVALID_DEGREE;
+    if (face_deg > 2) return PA_ERR_QUADRATURE;            // as the cut entries: 2*recdeg = 8 selects the empty rules[8]
+    if (!ctx->cut.host->cut_cells.empty() && !d_cut_lc) return PA_ERR_INVALID_ARG;
+    const pa_degree_info di = {face_deg + 1, face_deg, face_deg + 1};                  // cuthho_square.cpp:871
+    int grid = 0;
+    const int st = select_kernel(ctx, di, PA_QUAD_FAN, PA_STAB_NAIVE, ctx->mesh.ncells, e, &grid, true);
+    if (st != PA_OK) return st;
+    PA_HIP(ctx, join_side_stream(ctx));      // d_cut_lc may come from the cut kernel on the side stream
+    return PA_OK;
+}
+
+int pa_fictdom_condensed_ops_batch(pa_context *ctx, int face_deg, int where, const double *d_rhs, const double *d_cut_lc,
+                                   const double *d_cut_rhs, double *d_cond, int32_t *d_info, int32_t *d_info_cut)
+{
+    const pa::KernelEntry *e = nullptr;
+    int st = fdcond_prepare(ctx, face_deg, where, d_cond, d_cut_lc, &e);
+    if (st != PA_OK) return st;
+    const size_t nc = ctx->mesh.ncells;
+    const uint32_t ncut = (uint32_t)ctx->cut.host->cut_cells.size();
+    const pa_degree_info di = {face_deg + 1, face_deg, face_deg + 1};
+    const int cbs = pa::P2(di.cell_deg);
+    // the uncut formulas over every cell (the cut cells' rows are overwritten below), with the masked right-hand side
+    PA_HIP(ctx, ctx->cut.fd_scratch.grow(nc * (size_t)cbs, ctx->stream));
+    double *rhs = ctx->cut.fd_scratch.get();
+    PA_HIP(ctx, pa::fdcond_masked_rhs(ctx->stream, nc, cbs, ctx->cut.cell_loc.get(), where, d_rhs, rhs));
+    LocalOpsOut o;
+    o.cond = true; o.rhs = rhs; o.cond_out = d_cond; o.info = d_info;
+    st = run_local_ops(ctx, di, PA_QUAD_FAN, PA_STAB_NAIVE, 0, nc, o);
+    if (st != PA_OK) return st;
+    PA_HIP(ctx, pa::fdcond_cut_records(ctx->stream, face_deg, ctx->num_cus * 8, ncut, ctx->cut.cut_cells.get(), d_cut_lc, d_cut_rhs, d_cond,
+                                       d_info_cut));
+    return PA_OK;
+}
+
+int pa_fictdom_condensed_recover(pa_context *ctx, int face_deg, int where, const double *d_rhs, const double *d_cut_lc,
+                                 const double *d_cut_rhs, const double *d_g, const double *d_xF, double *d_full)
+{
+    const pa::KernelEntry *e = nullptr;
+    int st = fdcond_prepare(ctx, face_deg, where, d_full, d_cut_lc, &e);
+    if (st != PA_OK) return st;
+    if (!d_xF) return PA_ERR_INVALID_ARG;
+    if (!ctx->faces.cell_faces.get()) return PA_ERR_NO_MESH;
+    const size_t nc = ctx->mesh.ncells;
+    const uint32_t ncut = (uint32_t)ctx->cut.host->cut_cells.size();
+    const pa_degree_info di = {face_deg + 1, face_deg, face_deg + 1};
+    const int cbs = pa::P2(di.cell_deg), nf = 4 * (face_deg + 1);
+    PA_HIP(ctx, ctx->cut.fd_scratch.grow(nc * (size_t)(cbs + nf), ctx->stream));
+    double *rhs = ctx->cut.fd_scratch.get(), *uF = rhs + nc * (size_t)cbs;
+    double *uT = d_full + ctx->mesh.cell_base * (size_t)cbs;              // the context's cells, cells first
+    PA_HIP(ctx, pa::fdcond_masked_rhs(ctx->stream, nc, cbs, ctx->cut.cell_loc.get(), where, d_rhs, rhs));
+    st = pa_condensed_take_faces(ctx, di, 0, nc, d_xF, d_g, uF);           // Dirichlet faces: d_g, for cut and uncut cells alike
+    if (st != PA_OK) return st;
+    LocalOpsOut o;
+    o.cond = true; o.rhs = rhs; o.uF = uF; o.uT = uT;
+    st = run_local_ops(ctx, di, PA_QUAD_FAN, PA_STAB_NAIVE, 0, nc, o);
+    if (st != PA_OK) return st;
+    PA_HIP(ctx, pa::fdcond_cut_recover(ctx->stream, face_deg, ctx->num_cus * 8, ncut, ctx->cut.cut_cells.get(), d_cut_lc, d_cut_rhs, uF, uT));
+    PA_HIP(ctx, pa::fdcond_copy(ctx->stream, (size_t)(face_deg + 1) * ctx->faces.num_other_faces, d_xF,
+                                d_full + ctx->mesh.ncells_global * (size_t)cbs));
     return PA_OK;
 }

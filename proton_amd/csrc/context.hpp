@@ -105,6 +105,8 @@ struct CutState {
     IfRowsDev ifrows;
     // scratch of pa_cut_interface_ops_batch ([data | stab- | stab+] of the cut cells), kept between calls
     DeviceBuf<double> if_scratch;
+    // scratch of pa_fictdom_condensed_* (the masked right-hand sides, the cells' face values), kept between calls
+    DeviceBuf<double> fd_scratch;
 };
 
 // records of the per-cell pre-pass (hho_pre.hpp), grown on demand, reused by every local-operator call

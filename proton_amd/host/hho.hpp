@@ -885,6 +885,18 @@ inline std::array<size_t, 4> face_offsets(const Mesh &msh, const typename Mesh::
 
 }  // namespace proton_amd
 
+// solver_cg.hpp:38-61: the parameters and exit reasons of conjugated_gradient (below; assembler::solve_condensed_fictdom takes them)
+enum class cg_exit_reason { CONVERGED, DIVERGED, MAX_ITER_REACHED };
+
+template <typename T>
+struct cg_params {
+    T convergence_threshold, divergence_threshold;
+    size_t max_iter;
+    bool verbose, apply_preconditioner;
+    std::string histfile;
+    cg_params() : convergence_threshold(1e-9), divergence_threshold(100), max_iter(1000), verbose(false), apply_preconditioner(false) {}
+};
+
 // hho.hpp:252-463
 template <typename Mesh>
 class assembler {
@@ -1078,6 +1090,59 @@ class assembler {
         if (!RHS.empty()) d_RHS.download(RHS.data(), RHS.size());
         device_csr_ = true;
     }
+
+    // The same loop (cuthho_square.cpp:881-905), its solve (:915-919) and what take_local_data (:959-962) reads, with the cell
+    // unknowns eliminated on the device: the operators as assemble_all_fictdom, every cell's packed condensed record
+    // (pa_fictdom_condensed_ops_batch: cut cells in double-double), the face-only system directly in CSR (pa_condensed_csr_*),
+    // pa_conjugated_gradient on it and the cell unknowns recovered (pa_fictdom_condensed_recover).  Returns the full solution
+    // vector in the reference's numbering -- what solver.solve(RHS) leaves in `sol` -- for take_local_data; LHS / RHS are left
+    // untouched.
+    template <typename LevelSet, typename Location>
+    std::vector<T> solve_condensed_fictdom(const Mesh &msh, const LevelSet & /*level_set_function*/, Location where, int rhs_fn, int dirichlet_fn,
+                                           const cg_params<T> &cgp, size_t *iterations = nullptr, cg_exit_reason *exit_reason = nullptr)
+    {
+        if (!msh.preprocessed) throw std::logic_error("cutHHO mesh not preprocessed");
+        auto &dev = proton_amd::device::instance();
+        pa_sizes sz;
+        dev.check(pa_sizes_for(di.c_abi(), PA_QUAD_FAN, &sz), "pa_sizes_for");
+        const int fd = (int)di.face_degree();
+        if (di.cell_degree() != di.face_degree() + 1) throw std::invalid_argument("solve_condensed_fictdom: hho_degree_info(k + 1, k) expected");
+        const size_t n = msh.cells.size(), ncut = msh.num_cut_cells, mm = (size_t)sz.msize * sz.msize;
+        pa_condensed_info info;
+        dev.check(pa_condensed_query(dev.ctx(), di.c_abi(), &info), "pa_condensed_query");
+        const size_t nF = info.system_size;
+        if (n * sz.cbs + nF != RHS.size()) throw std::runtime_error("solve_condensed_fictdom: the device numbers another system than this assembler");
+        proton_amd::device_buffer<double> d_rhs(n * sz.cbs), d_g(msh.faces.size() * sz.fbs), d_cut_lc(ncut * mm + 1), d_cut_rhs(ncut * sz.cbs + 1),
+            d_cond(n * (size_t)info.cond_doubles + 1);
+        dev.check(pa_dirichlet_data_batch(dev.ctx(), fd, dirichlet_fn, nullptr, d_g.get()), "pa_dirichlet_data_batch");
+        dev.check(pa_cut_uncut_rhs_batch(dev.ctx(), (int)di.cell_degree(), (int)where, rhs_fn, d_rhs.get()), "pa_cut_uncut_rhs_batch");
+        if (ncut)
+            dev.check(pa_cut_local_ops_batch(dev.ctx(), fd, &msh.level_set, (int)where, rhs_fn, dirichlet_fn, nullptr, nullptr, nullptr,
+                                             d_cut_lc.get(), d_cut_rhs.get(), nullptr), "pa_cut_local_ops_batch");
+        const double *cut_lc = ncut ? d_cut_lc.get() : nullptr, *cut_rhs = ncut ? d_cut_rhs.get() : nullptr;
+        dev.check(pa_fictdom_condensed_ops_batch(dev.ctx(), fd, (int)where, d_rhs.get(), cut_lc, cut_rhs, d_cond.get(), nullptr, nullptr),
+                  "pa_fictdom_condensed_ops_batch");
+        proton_amd::device_buffer<int64_t> d_rowptr(nF + 1);
+        proton_amd::device_buffer<int32_t> d_colind(info.nnz_owned + 1);
+        proton_amd::device_buffer<double> d_values(info.nnz_owned + 1), d_b(nF + 1), d_xF(nF + 1), d_full(RHS.size() + 1);
+        dev.check(pa_condensed_csr_pattern(dev.ctx(), di.c_abi(), d_rowptr.get(), d_colind.get()), "pa_condensed_csr_pattern");
+        dev.check(pa_condensed_csr_fill(dev.ctx(), di.c_abi(), d_cond.get(), d_g.get(), nullptr, d_values.get(), d_b.get()), "pa_condensed_csr_fill");
+        int32_t reason = 0;
+        size_t iters = 0;
+        double rr = 0.0;
+        dev.check(pa_conjugated_gradient(dev.ctx(), nF, d_rowptr.get(), d_colind.get(), d_values.get(), d_b.get(), d_xF.get(),
+                                         cgp.convergence_threshold, cgp.divergence_threshold, cgp.max_iter, cgp.apply_preconditioner ? 1 : 0,
+                                         &reason, &iters, &rr), "pa_conjugated_gradient");
+        if (cgp.verbose) std::cout << " -> Iteration " << iters << ", rr = " << rr << std::endl;
+        if (iterations) *iterations = iters;
+        if (exit_reason)
+            *exit_reason = reason == 0 ? cg_exit_reason::CONVERGED : reason == 1 ? cg_exit_reason::DIVERGED : cg_exit_reason::MAX_ITER_REACHED;
+        dev.check(pa_fictdom_condensed_recover(dev.ctx(), fd, (int)where, d_rhs.get(), cut_lc, cut_rhs, d_g.get(), d_xF.get(), d_full.get()),
+                  "pa_fictdom_condensed_recover");
+        std::vector<T> sol(RHS.size());
+        if (!sol.empty()) d_full.download(sol.data(), sol.size());
+        return sol;
+    }
 };
 
 template <typename Mesh>
@@ -1086,19 +1151,8 @@ auto make_assembler(const Mesh &msh, hho_degree_info hdi)
     return assembler<Mesh>(msh, hdi);
 }
 
-// solver_cg.hpp:38-144: the reference's (optionally Jacobi-preconditioned) conjugate gradient,
+// solver_cg.hpp:63-144: the reference's (optionally Jacobi-preconditioned) conjugate gradient,
 // run on the device over the CSR matrix (pa_conjugated_gradient)
-enum class cg_exit_reason { CONVERGED, DIVERGED, MAX_ITER_REACHED };
-
-template <typename T>
-struct cg_params {
-    T convergence_threshold, divergence_threshold;
-    size_t max_iter;
-    bool verbose, apply_preconditioner;
-    std::string histfile;
-    cg_params() : convergence_threshold(1e-9), divergence_threshold(100), max_iter(1000), verbose(false), apply_preconditioner(false) {}
-};
-
 template <typename T>
 cg_exit_reason conjugated_gradient(const proton_amd::sparse_matrix<T> &A, const std::vector<T> &b, std::vector<T> &x,
                                    const cg_params<T> &parms = cg_params<T>(), size_t *iterations = nullptr)
