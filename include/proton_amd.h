@@ -487,6 +487,61 @@ int pa_conjugated_gradient(pa_context *ctx, size_t nrows, const int64_t *d_rowpt
                            double convergence_threshold, double divergence_threshold, size_t max_iter,
                            int apply_preconditioner, int32_t *exit_reason, size_t *iterations, double *relative_residual);
 
+/* ---- a patch preconditioner for that conjugate gradient --------------------------------------------------
+ * Where solver_cg.hpp:77-80 keeps 1 / diag(A) and solver_cg.hpp:63-144 multiplies the residual by it, these keep the inverse
+ * of the dense diagonal block of every PATCH of rows and apply the additive Schwarz sum
+ *     z = sum_p R_p^T (R_p A R_p^T)^-1 R_p r
+ * (the solve they serve: cuthho_square.cpp:915-919 on the face-only system).  The patch table is a CSR-like pair:
+ * d_patch_ptr (npatches + 1, int64, starting at 0) and d_patch_rows (d_patch_ptr[npatches] global row indices, int32).
+ * A patch holds 1 to PA_PATCH_MAX_ROWS rows, none twice; a row may lie in several patches and every row lies in at least
+ * one.  A table that breaks one of these -- an index out of range, a repeated row, a patch size outside 1..16, an uncovered
+ * row -- is refused with PA_ERR_INVALID_ARG and text in pa_last_error(), checked on the device before anything is indexed
+ * with it, and no output buffer is touched (d_scratch is no output).  Callers own the device memory. */
+#define PA_PATCH_MAX_ROWS 16
+typedef struct {
+    uint64_t entries;            /* d_patch_ptr[npatches]                                                        */
+    int32_t max_patch_rows;      /* the largest patch; every factor takes max_patch_rows (max_patch_rows + 1) / 2 */
+    int32_t lanes_per_patch;     /* 4, 8 or 16: the lanes that share a patch in the factor and apply kernels      */
+    uint64_t factor_doubles;     /* doubles of d_factors                                                          */
+    uint64_t slot_ints;          /* int32 of d_slots: nrows + 1 + entries                                         */
+    uint64_t scratch_bytes;      /* bytes of d_scratch (the patch-major results of an apply, the build's counters) */
+} pa_patch_precond_info;
+/* solver_cg.hpp:63-144, cuthho_square.cpp:915-919: what a table needs; reads d_patch_ptr only (sizes within 1..16, else
+ * PA_ERR_INVALID_ARG).  Waits for the stream. */
+int pa_patch_precond_query(pa_context *ctx, size_t nrows, size_t npatches, const int64_t *d_patch_ptr, pa_patch_precond_info *out);
+/* The set-up of solver_cg.hpp:63-144 (its lines 77-80) for patches (cuthho_square.cpp:915-919): validates the table, builds d_slots (per row the places of
+ * its contributions in the patch-major buffer, ascending = in patch order) and factors every patch: A_p gathered from the
+ * CSR arrays (columns ascending within a row; an absent entry is zero), Cholesky in plain double, the packed lower triangle
+ * of L^-1 into d_factors.  d_info (npatches): 0, or j + 1 for the first non-positive pivot j of the patch; *failed_patches
+ * (host, may be NULL) counts them, and any makes the call return PA_ERR_NOT_SPD.  Waits for the stream. */
+int pa_patch_precond_factor(pa_context *ctx, size_t nrows, const int64_t *d_rowptr, const int32_t *d_colind, const double *d_values,
+                            size_t npatches, const int64_t *d_patch_ptr, const int32_t *d_patch_rows, double *d_factors,
+                            int32_t *d_slots, void *d_scratch, int32_t *d_info, size_t *failed_patches);
+/* The preconditioner's product of solver_cg.hpp:63-144 (its lines 84 and 126) for patches (cuthho_square.cpp:915-919): d_z = sum_p R_p^T A_p^-1 R_p d_r with
+ * the table, d_factors, d_slots and d_scratch of a pa_patch_precond_factor that returned PA_OK.  Every patch writes its
+ * results to a patch-major buffer and every row sums its contributions in ascending patch order: no floating-point atomics,
+ * the same bits from call to call. */
+int pa_patch_precond_apply(pa_context *ctx, size_t nrows, size_t npatches, const int64_t *d_patch_ptr, const int32_t *d_patch_rows,
+                           const double *d_factors, const int32_t *d_slots, void *d_scratch, const double *d_r, double *d_z);
+/* conjugated_gradient (solver_cg.hpp:63-144; the solve of cuthho_square.cpp:915-919) with the patch preconditioner: the
+ * arguments and the three results of pa_conjugated_gradient with the patch table in place of apply_preconditioner; the same
+ * recurrences, exit tests and exit order, z an explicit vector.  The factors live for the call.  A refused table:
+ * PA_ERR_INVALID_ARG; a patch with a failed pivot: PA_ERR_NOT_SPD before the first iteration; d_x is untouched by both. */
+int pa_conjugated_gradient_patch(pa_context *ctx, size_t nrows, const int64_t *d_rowptr, const int32_t *d_colind,
+                                 const double *d_values, const double *d_b, double *d_x,
+                                 size_t npatches, const int64_t *d_patch_ptr, const int32_t *d_patch_rows,
+                                 double convergence_threshold, double divergence_threshold, size_t max_iter,
+                                 int32_t *exit_reason, size_t *iterations, double *relative_residual);
+/* The patch tables of the face-only system of pa_condensed_csr_pattern (the Poisson and the fictitious-domain systems;
+ * assembler::assemble hho.hpp:344-406 numbers its faces, the solve is cuthho_square.cpp:915-919 / solver_cg.hpp:63-144).
+ * PA_PATCH_FACE: one patch per non-Dirichlet face, its fbs rows.  PA_PATCH_CELL: one patch per cell with at least one
+ * non-Dirichlet face, in cell order, the rows of its non-Dirichlet faces in the cell's face order bottom, right, top, left
+ * (up to 4 fbs, overlapping).  Whole-mesh contexts; a slab is refused with PA_ERR_INVALID_ARG as pa_assembler_csr_fill
+ * refuses one.  The query gives the sizes of d_patch_ptr (*npatches + 1) and d_patch_rows (*entries). */
+enum { PA_PATCH_FACE = 0, PA_PATCH_CELL = 1 };
+int pa_condensed_patches_query(pa_context *ctx, pa_degree_info di, int kind, size_t *npatches, size_t *entries);
+int pa_condensed_patches(pa_context *ctx, pa_degree_info di, int kind, int64_t *d_patch_ptr, int32_t *d_patch_rows);
+
 /* ---- cutHHO (fictitious domain, `cuthho_square -f`) -----------------------------------------
  * circle_level_set / line_level_set, apps/cuthho/cuthho_square.cpp:56-124 */
 typedef struct { int32_t kind; double radius, alpha, beta, cut_y; } pa_level_set;   /* kind 0 circle, 1 line */

@@ -265,6 +265,64 @@ class BatchAssembler:
                                                          b.data_ptr(), x.data_ptr(), tol, div, max_iter, precond)
         return x, reason, iters, rr
 
+    # ---- the patch preconditioner (patch_precond.hip) -----------------------------------
+    def condensed_patches(self, cd, fd, kind):
+        """the patch table of the face-only system of condensed_csr_pattern: kind "face" (one patch per non-Dirichlet face) or
+        "cell" (one per cell, the rows of its non-Dirichlet faces) -> (patch_ptr int64 [npatches + 1], patch_rows int32)"""
+        di, _ = capi.degree_info(cd, fd)
+        kind = {"face": capi.PATCH_FACE, "cell": capi.PATCH_CELL}.get(kind, kind)
+        npatches, entries = self.ctx.condensed_patches_query(di, kind)
+        ptr = torch.empty(npatches + 1, dtype=torch.int64, device=self.device)
+        rows = torch.empty(max(entries, 1), dtype=torch.int32, device=self.device)
+        self.ctx.condensed_patches(di, kind, ptr.data_ptr(), rows.data_ptr())
+        return ptr, rows[:entries]
+
+    def patch_precond_factor(self, rowptr, colind, values, patches):
+        """pa_patch_precond_query + pa_patch_precond_factor -> dict(factors, slots, scratch, info [npatches], failed, sizes,
+        patches): what patch_precond_apply takes.  failed > 0: some patch has a non-positive pivot (info says which)."""
+        ptr, rows = patches
+        n, npatches = rowptr.numel() - 1, ptr.numel() - 1
+        sz = self.ctx.patch_precond_query(n, npatches, ptr.data_ptr())
+        factors = torch.empty(max(sz.factor_doubles, 1), dtype=torch.float64, device=self.device)
+        slots = torch.empty(max(sz.slot_ints, 1), dtype=torch.int32, device=self.device)
+        scratch = torch.empty(max(sz.scratch_bytes, 1), dtype=torch.uint8, device=self.device)
+        info = torch.empty(max(npatches, 1), dtype=torch.int32, device=self.device)
+        failed = self.ctx.patch_precond_factor(n, rowptr.data_ptr(), colind.data_ptr(), values.data_ptr(), npatches, ptr.data_ptr(),
+                                               rows.data_ptr(), factors.data_ptr(), slots.data_ptr(), scratch.data_ptr(), info.data_ptr())
+        return {"factors": factors, "slots": slots, "scratch": scratch, "info": info[:npatches], "failed": failed, "sizes": sz,
+                "patches": (ptr, rows), "n": n}
+
+    def patch_precond_apply(self, pre, r, z=None):
+        """z = sum_p R_p^T A_p^-1 R_p r with what patch_precond_factor returned"""
+        ptr, rows = pre["patches"]
+        if z is None:
+            z = torch.empty_like(r)
+        self.ctx.patch_precond_apply(pre["n"], ptr.numel() - 1, ptr.data_ptr(), rows.data_ptr(), pre["factors"].data_ptr(),
+                                     pre["slots"].data_ptr(), pre["scratch"].data_ptr(), r.data_ptr(), z.data_ptr())
+        return z
+
+    def conjugated_gradient_patch(self, rowptr, colind, values, b, patches, tol=1e-9, div=100.0, max_iter=1000, x=None):
+        """solver_cg.hpp:63-144 with the patch preconditioner -> (x, exit_reason, iterations, relative residual)"""
+        ptr, rows = patches
+        if x is None:
+            x = torch.empty_like(b)
+        reason, iters, rr = self.ctx.conjugated_gradient_patch(b.numel(), rowptr.data_ptr(), colind.data_ptr(), values.data_ptr(), b.data_ptr(),
+                                                               x.data_ptr(), ptr.numel() - 1, ptr.data_ptr(), rows.data_ptr(), tol, div, max_iter)
+        return x, reason, iters, rr
+
+    def condensed_solve(self, cd, fd, cond, g=None, tol=1e-9, div=100.0, max_iter=None, precond=True, patches=None):
+        """the face-only system of the records `cond` (condensed_ops) assembled (condensed_csr_pattern / condensed_csr_fill) and
+        solved: patches None = conjugated_gradient (precond: Jacobi), "face" / "cell" = conjugated_gradient_patch on that table
+        -> (xF, exit_reason, iterations, relative residual).  Whole-mesh contexts."""
+        rowptr, colind = self.condensed_csr_pattern(cd, fd)
+        values, b = self.condensed_csr_fill(cd, fd, cond, g)
+        if max_iter is None:
+            max_iter = 4 * b.numel()
+        if patches is None:
+            return self.conjugated_gradient(rowptr, colind, values, b, tol=tol, div=div, max_iter=max_iter, precond=precond)
+        return self.conjugated_gradient_patch(rowptr, colind, values, b, self.condensed_patches(cd, fd, patches), tol=tol, div=div,
+                                              max_iter=max_iter)
+
     def take_local_data(self, cd, fd, solution, g=None, first=0, n=None):
         """assembler::take_local_data (hho.hpp:408-449) for cells [first, first+n) -> n x msize."""
         di, _ = capi.degree_info(cd, fd)
@@ -529,11 +587,12 @@ class BatchAssembler:
         return full
 
     def fictdom_condensed_solve(self, fd, where=capi.LOC_NEGATIVE, rhs_fn=capi.FN_SIN_SIN_RHS, bcs_fn=capi.FN_SIN_SIN_SOL, tol=1e-13,
-                                g=None, max_iter=None, precond=True, overlap=False):
+                                g=None, max_iter=None, precond=True, overlap=False, patches=None):
         """cuthho_square.cpp:881-919 and :959-962 on the face-only system: the operators (pa_cut_uncut_rhs_batch,
         pa_cut_local_ops_batch; overlap: on the context's side stream), the records, condensed_csr_pattern / condensed_csr_fill,
         conjugated_gradient and the recovery -> (full solution vector, iterations, exit reason).  g: the boundary data
-        (default: dirichlet_data of bcs_fn).  Whole-mesh contexts."""
+        (default: dirichlet_data of bcs_fn).  patches "face" / "cell": conjugated_gradient_patch on that table of condensed_patches
+        in place of conjugated_gradient.  Whole-mesh contexts."""
         cd = fd + 1
         if g is None:
             g = self.dirichlet_data(fd, bcs_fn)
@@ -554,7 +613,11 @@ class BatchAssembler:
         values, b = self.condensed_csr_fill(cd, fd, rec["cond"], g)
         if max_iter is None:
             max_iter = 4 * b.numel()
-        xF, reason, iters, _ = self.conjugated_gradient(rowptr, colind, values, b, tol=tol, max_iter=max_iter, precond=precond)
+        if patches is None:
+            xF, reason, iters, _ = self.conjugated_gradient(rowptr, colind, values, b, tol=tol, max_iter=max_iter, precond=precond)
+        else:
+            xF, reason, iters, _ = self.conjugated_gradient_patch(rowptr, colind, values, b, self.condensed_patches(cd, fd, patches), tol=tol,
+                                                                  max_iter=max_iter)
         full = self.fictdom_condensed_recover(fd, xF, where, rhs, cut_lc, cut_rhs, g)
         return full, iters, reason
 

@@ -48,6 +48,8 @@ EXPORTS = [
     "pa_comm_neighbour_exchange_start", "pa_conjugated_gradient_rows", "pa_comm_cg_transport", "pa_copy_to_host", "pa_copy_to_device", "pa_cut_uncut_rhs_batch",
     "pa_mesh_set_points", "pa_cut_preprocess_rows", "pa_cut_merge_condensed", "pa_fictdom_csr_assemble",
     "pa_fictdom_condensed_ops_batch", "pa_fictdom_condensed_recover",
+    "pa_patch_precond_query", "pa_patch_precond_factor", "pa_patch_precond_apply", "pa_conjugated_gradient_patch",
+    "pa_condensed_patches_query", "pa_condensed_patches",
 ]
 
 
@@ -128,6 +130,15 @@ class CondensedInfo(C.Structure):
                 ("halo_doubles", C.c_int32), ("has_below", C.c_int32)]
 
 
+class PatchPrecondInfo(C.Structure):
+    _fields_ = [("entries", C.c_uint64), ("max_patch_rows", C.c_int32), ("lanes_per_patch", C.c_int32), ("factor_doubles", C.c_uint64),
+                ("slot_ints", C.c_uint64), ("scratch_bytes", C.c_uint64)]
+
+
+PATCH_FACE, PATCH_CELL = 0, 1
+PATCH_MAX_ROWS = 16
+
+
 class LevelSet(C.Structure):
     _fields_ = [("kind", C.c_int32), ("radius", C.c_double), ("alpha", C.c_double), ("beta", C.c_double),
                 ("cut_y", C.c_double)]
@@ -199,6 +210,13 @@ def lib():
     L.pa_csr_from_triplets.argtypes = [vp, sz, dp, dp, dp, sz, dp, dp, dp, C.POINTER(sz)]
     L.pa_conjugated_gradient.argtypes = [vp, sz, dp, dp, dp, dp, dp, C.c_double, C.c_double, sz, C.c_int,
                                          C.POINTER(C.c_int32), C.POINTER(sz), C.POINTER(C.c_double)]
+    L.pa_patch_precond_query.argtypes = [vp, sz, sz, dp, C.POINTER(PatchPrecondInfo)]
+    L.pa_patch_precond_factor.argtypes = [vp, sz, dp, dp, dp, sz, dp, dp, dp, dp, dp, dp, C.POINTER(sz)]
+    L.pa_patch_precond_apply.argtypes = [vp, sz, sz, dp, dp, dp, dp, dp, dp, dp]
+    L.pa_conjugated_gradient_patch.argtypes = [vp, sz, dp, dp, dp, dp, dp, sz, dp, dp, C.c_double, C.c_double, sz,
+                                               C.POINTER(C.c_int32), C.POINTER(sz), C.POINTER(C.c_double)]
+    L.pa_condensed_patches_query.argtypes = [vp, DegreeInfo, C.c_int, C.POINTER(sz), C.POINTER(sz)]
+    L.pa_condensed_patches.argtypes = [vp, DegreeInfo, C.c_int, dp, dp]
     L.pa_conjugated_gradient_rows.argtypes = [vp, C.POINTER(CgTransport), C.c_int64, C.c_int64, dp, dp, dp, dp, dp, C.c_double, C.c_double, sz,
                                               C.c_int, C.POINTER(C.c_int32), C.POINTER(sz), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
     L.pa_comm_cg_transport.argtypes = [vp, C.POINTER(CgTransport)]
@@ -496,6 +514,39 @@ class Context:
         self._ck(self._L.pa_conjugated_gradient(self.h, nrows, rowptr, colind, values, b, x, tol, div, max_iter, int(precond),
                                                 C.byref(reason), C.byref(iters), C.byref(rr)), "pa_conjugated_gradient")
         return reason.value, iters.value, rr.value
+
+    def patch_precond_query(self, nrows, npatches, patch_ptr):
+        out = PatchPrecondInfo()
+        self._ck(self._L.pa_patch_precond_query(self.h, nrows, npatches, patch_ptr, C.byref(out)), "pa_patch_precond_query")
+        return out
+
+    def patch_precond_factor(self, nrows, rowptr, colind, values, npatches, patch_ptr, patch_rows, factors, slots, scratch, info):
+        """-> the number of patches with a failed pivot (their info words say where); other refusals raise"""
+        failed = C.c_size_t(0)
+        st = self._L.pa_patch_precond_factor(self.h, nrows, rowptr, colind, values, npatches, patch_ptr, patch_rows, factors, slots, scratch,
+                                             info, C.byref(failed))
+        if st != 6:                                   # PA_ERR_NOT_SPD: the caller reads info
+            self._ck(st, "pa_patch_precond_factor")
+        return failed.value
+
+    def patch_precond_apply(self, nrows, npatches, patch_ptr, patch_rows, factors, slots, scratch, r, z):
+        self._ck(self._L.pa_patch_precond_apply(self.h, nrows, npatches, patch_ptr, patch_rows, factors, slots, scratch, r, z),
+                 "pa_patch_precond_apply")
+
+    def conjugated_gradient_patch(self, nrows, rowptr, colind, values, b, x, npatches, patch_ptr, patch_rows, tol=1e-9, div=100.0,
+                                  max_iter=1000):
+        reason, iters, rr = C.c_int32(0), C.c_size_t(0), C.c_double(0.0)
+        self._ck(self._L.pa_conjugated_gradient_patch(self.h, nrows, rowptr, colind, values, b, x, npatches, patch_ptr, patch_rows, tol, div,
+                                                      max_iter, C.byref(reason), C.byref(iters), C.byref(rr)), "pa_conjugated_gradient_patch")
+        return reason.value, iters.value, rr.value
+
+    def condensed_patches_query(self, di, kind):
+        npatches, entries = C.c_size_t(0), C.c_size_t(0)
+        self._ck(self._L.pa_condensed_patches_query(self.h, di, kind, C.byref(npatches), C.byref(entries)), "pa_condensed_patches_query")
+        return npatches.value, entries.value
+
+    def condensed_patches(self, di, kind, patch_ptr, patch_rows):
+        self._ck(self._L.pa_condensed_patches(self.h, di, kind, patch_ptr, patch_rows), "pa_condensed_patches")
 
     def copy_to_host(self, host_dst, d_src, nbytes):
         self._ck(self._L.pa_copy_to_host(self.h, host_dst, d_src, nbytes), "pa_copy_to_host")

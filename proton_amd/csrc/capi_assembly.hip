@@ -1,5 +1,5 @@
 // capi_assembly.hip -- the C ABI of the global systems of an uncut mesh: the assembler's triplets and local data, the energy form,
-// the condensed (face-only) system, the assembler's own system directly in CSR, triplets to CSR, and the conjugate gradient.
+// the condensed (face-only) system, the assembler's own system directly in CSR, triplets to CSR, the conjugate gradient, and the patch preconditioner with its tables.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -7,7 +7,10 @@
 #include "cg.hpp"
 #include "context.hpp"
 #include "csr.hpp"
+#include "device_tmp.hpp"
 #include "hho_assembly.hpp"
+#include "patch_precond.hpp"
+#include "scan.hpp"
 
 int pa_triplets_batch(pa_context *ctx, pa_degree_info di, size_t first, size_t n, const double *d_lc,
                       const double *d_rhs, const double *d_g, int32_t *d_rows, int32_t *d_cols, double *d_vals,
@@ -409,4 +412,148 @@ int pa_conjugated_gradient_rows(pa_context *ctx, const pa_cg_transport *transpor
     if (he != hipSuccess) { ctx->last_error = std::string("pa_conjugated_gradient_rows: ") + hipGetErrorString(he); return PA_ERR_HIP; }
     if (tstat == 3) ctx->last_error = "pa_conjugated_gradient_rows: another rank failed; every rank left the solve at the same reduction";
     return (tstat == 1 || tstat == 3) ? PA_ERR_COMM : (tstat == 2 ? PA_ERR_INVALID_ARG : PA_OK);
+}
+
+// ---- the patch preconditioner and the conjugate gradient with it: patch_precond.hip -----------------------------------
+static int patch_refused(pa_context *ctx, const char *who, int refusal)
+{
+    ctx->last_error = std::string(who) + ": " + pa::patch_refusal_text(refusal);
+    return PA_ERR_INVALID_ARG;
+}
+
+static void patch_info_out(const pa::PatchSizes &sz, pa_patch_precond_info *out)
+{
+    out->entries = sz.entries; out->max_patch_rows = sz.max_rows; out->lanes_per_patch = sz.lanes;
+    out->factor_doubles = sz.factor_doubles; out->slot_ints = sz.slot_ints; out->scratch_bytes = sz.scratch_bytes;
+}
+
+int pa_patch_precond_query(pa_context *ctx, size_t nrows, size_t npatches, const int64_t *d_patch_ptr, pa_patch_precond_info *out)
+{
+    if (!ctx || !d_patch_ptr || !out) return PA_ERR_INVALID_ARG;
+    PA_HIP(ctx, hipSetDevice(ctx->device));
+    pa::PatchSizes sz;
+    int refusal = 0;
+    PA_HIP(ctx, pa::patch_query(ctx->stream, nrows, npatches, d_patch_ptr, &sz, &refusal));
+    if (refusal) return patch_refused(ctx, "pa_patch_precond_query", refusal);
+    patch_info_out(sz, out);
+    return PA_OK;
+}
+
+int pa_patch_precond_factor(pa_context *ctx, size_t nrows, const int64_t *d_rowptr, const int32_t *d_colind, const double *d_values,
+                            size_t npatches, const int64_t *d_patch_ptr, const int32_t *d_patch_rows, double *d_factors,
+                            int32_t *d_slots, void *d_scratch, int32_t *d_info, size_t *failed_patches)
+{
+    if (!ctx || !d_rowptr || !d_patch_ptr || !d_slots || !d_scratch) return PA_ERR_INVALID_ARG;
+    if (npatches && (!d_colind || !d_values || !d_patch_rows || !d_factors || !d_info)) return PA_ERR_INVALID_ARG;
+    PA_HIP(ctx, hipSetDevice(ctx->device));
+    pa::PatchSizes sz;
+    int refusal = 0;
+    PA_HIP(ctx, pa::patch_query(ctx->stream, nrows, npatches, d_patch_ptr, &sz, &refusal));
+    if (refusal) return patch_refused(ctx, "pa_patch_precond_factor", refusal);
+    size_t failed = 0;
+    const pa::PatchTable t{nrows, npatches, d_patch_ptr, d_patch_rows};
+    PA_HIP(ctx, pa::patch_factor(ctx->stream, d_rowptr, d_colind, d_values, t, sz, d_factors, d_slots, d_scratch, d_info, &refusal, &failed));
+    if (refusal) return patch_refused(ctx, "pa_patch_precond_factor", refusal);
+    if (failed_patches) *failed_patches = failed;
+    return failed ? PA_ERR_NOT_SPD : PA_OK;
+}
+
+int pa_patch_precond_apply(pa_context *ctx, size_t nrows, size_t npatches, const int64_t *d_patch_ptr, const int32_t *d_patch_rows,
+                           const double *d_factors, const int32_t *d_slots, void *d_scratch, const double *d_r, double *d_z)
+{
+    if (!ctx || !d_patch_ptr || !d_slots || !d_scratch) return PA_ERR_INVALID_ARG;
+    if (nrows && (!d_patch_rows || !d_factors || !d_r || !d_z)) return PA_ERR_INVALID_ARG;
+    PA_HIP(ctx, hipSetDevice(ctx->device));
+    pa::PatchSizes sz;
+    int refusal = 0;
+    PA_HIP(ctx, pa::patch_query(ctx->stream, nrows, npatches, d_patch_ptr, &sz, &refusal));
+    if (refusal) return patch_refused(ctx, "pa_patch_precond_apply", refusal);
+    const pa::PatchTable t{nrows, npatches, d_patch_ptr, d_patch_rows};
+    pa::patch_apply(ctx->stream, t, sz, d_factors, d_slots, d_scratch, d_r, d_z, nullptr);
+    PA_HIP(ctx, hipGetLastError());
+    return PA_OK;
+}
+
+int pa_conjugated_gradient_patch(pa_context *ctx, size_t nrows, const int64_t *d_rowptr, const int32_t *d_colind, const double *d_values,
+                                 const double *d_b, double *d_x, size_t npatches, const int64_t *d_patch_ptr, const int32_t *d_patch_rows,
+                                 double convergence_threshold, double divergence_threshold, size_t max_iter, int32_t *exit_reason,
+                                 size_t *iterations, double *relative_residual)
+{
+    if (!ctx || !d_rowptr || (nrows && (!d_colind || !d_values || !d_b || !d_x || !d_patch_ptr || !d_patch_rows))) return PA_ERR_INVALID_ARG;
+    PA_HIP(ctx, hipSetDevice(ctx->device));
+    int reason = 0, status = 0, refusal = 0;
+    PA_HIP(ctx, pa::conjugated_gradient_patch(ctx->stream, nrows, d_rowptr, d_colind, d_values, d_b, d_x, npatches, d_patch_ptr, d_patch_rows,
+                                              convergence_threshold, divergence_threshold, max_iter, &reason, iterations, relative_residual,
+                                              &status, &refusal));
+    if (status == 1) return patch_refused(ctx, "pa_conjugated_gradient_patch", refusal);
+    if (status == 2) { ctx->last_error = "pa_conjugated_gradient_patch: a patch matrix is not positive definite (pa_patch_precond_factor says which)"; return PA_ERR_NOT_SPD; }
+    if (exit_reason) *exit_reason = reason;
+    return PA_OK;
+}
+
+// the cells with a non-Dirichlet face: their count and (index given) per cell its rank among them, -1 none
+static int cell_patch_index(pa_context *ctx, pa::DeviceTmp &tmp, uint32_t *count, int32_t **index)
+{
+    const uint32_t nc = (uint32_t)ctx->mesh.ncells;
+    const uint32_t nblocks = (nc + pa::SCAN_TILE - 1) / pa::SCAN_TILE;
+    uint8_t *flags = nullptr;
+    uint32_t *counts = nullptr;
+    int32_t *unused = nullptr, *idx = nullptr;
+    if (!tmp.alloc(&flags, nc) || !tmp.alloc(&counts, (size_t)nblocks + 1) || !tmp.alloc(&unused, nc) || !tmp.alloc(&idx, nc)) PA_HIP(ctx, tmp.error());
+    pa::cell_patch_flags(ctx->stream, nc, ctx->asmb.cprefix.get(), flags);
+    *count = 0;
+    if (nc) {
+        hipLaunchKernelGGL(pa::active_count_kernel, dim3(nblocks), dim3(pa::SCAN_BLOCK), 0, ctx->stream, flags, nc, counts);
+        hipLaunchKernelGGL(pa::active_block_scan_kernel, dim3(1), dim3(pa::SCAN_BLOCK), 0, ctx->stream, counts, nblocks);
+        hipLaunchKernelGGL(pa::active_tables_kernel, dim3(nblocks), dim3(pa::SCAN_BLOCK), 0, ctx->stream, flags, nc, counts, unused, idx);
+        if (!tmp.ok(hipMemcpyAsync(count, counts + nblocks, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream)) ||
+            !tmp.ok(hipStreamSynchronize(ctx->stream)))
+            PA_HIP(ctx, tmp.error());
+    }
+    if (index) *index = idx;
+    return PA_OK;
+}
+
+int pa_condensed_patches_query(pa_context *ctx, pa_degree_info di, int kind, size_t *npatches, size_t *entries)
+{
+    if (!ctx || !npatches || !entries || !degree_ok(di) || (kind != PA_PATCH_FACE && kind != PA_PATCH_CELL)) return PA_ERR_INVALID_ARG;
+    PA_HIP(ctx, hipSetDevice(ctx->device));
+    const int st = asm_prepare(ctx);                     // whole-mesh contexts only, as pa_assembler_csr_fill
+    if (st != PA_OK) return st;
+    const pa::FaceSystemView v = face_system_view(ctx);
+    const size_t fbs = (size_t)di.face_deg + 1;
+    if (kind == PA_PATCH_FACE) { *npatches = v.nown; *entries = fbs * v.nown; return PA_OK; }
+    pa::DeviceTmp tmp(ctx->stream);
+    uint32_t count = 0;
+    const int sc = cell_patch_index(ctx, tmp, &count, nullptr);
+    if (sc != PA_OK) return sc;
+    *npatches = count;
+    *entries = fbs * v.cell_faces_total;                 // cprefix[ncells] of face_system.hpp
+    return PA_OK;
+}
+
+int pa_condensed_patches(pa_context *ctx, pa_degree_info di, int kind, int64_t *d_patch_ptr, int32_t *d_patch_rows)
+{
+    if (!ctx || !d_patch_ptr || !degree_ok(di) || (kind != PA_PATCH_FACE && kind != PA_PATCH_CELL)) return PA_ERR_INVALID_ARG;
+    PA_HIP(ctx, hipSetDevice(ctx->device));
+    const int st = asm_prepare(ctx);
+    if (st != PA_OK) return st;
+    const pa::FaceSystemView v = face_system_view(ctx);
+    const int fbs = di.face_deg + 1;
+    if ((uint64_t)fbs * v.cell_faces_total >= ((uint64_t)1 << 31)) return PA_ERR_INVALID_ARG;      // int32 slots
+    if (v.nown && !d_patch_rows) return PA_ERR_INVALID_ARG;
+    if (kind == PA_PATCH_FACE) {
+        pa::face_patches(ctx->stream, v.nown, fbs, d_patch_ptr, d_patch_rows);
+        PA_HIP(ctx, hipGetLastError());
+        return PA_OK;
+    }
+    pa::DeviceTmp tmp(ctx->stream);
+    uint32_t count = 0;
+    int32_t *index = nullptr;
+    const int sc = cell_patch_index(ctx, tmp, &count, &index);
+    if (sc != PA_OK) return sc;
+    pa::cell_patches(ctx->stream, v.ncells, count, v.cell_faces, v.face_compress, v.cprefix, index, fbs, d_patch_ptr, d_patch_rows);
+    PA_HIP(ctx, hipGetLastError());
+    PA_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the index lives until the kernel has read it
+    return PA_OK;
 }

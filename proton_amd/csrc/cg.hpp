@@ -47,6 +47,15 @@ struct CgWorkspace {
 hipError_t cg_workspace_reserve(CgWorkspace *ws, size_t rows);
 void cg_workspace_release(CgWorkspace *ws);
 
+// What a solver with an explicit preconditioned residual (patch_precond.hip) shares with this one: the device-resident scalars of
+// the iteration, the one-block reduction of the per-block partials with the scalar algebra of the step (cg_reduce_kernel: mode 0
+// after the first residual, 1 after the product, 2 after the update), and the plain CSR matrix behind CgMatrixOps (m must outlive
+// the ops).
+struct CgScalars { double rho, dy, nr2, rho_new, alpha, beta; };
+void cg_launch_reduce(hipStream_t stream, int mode, size_t nparts, const double *part_a, const double *part_b, void *scalars);
+struct CgCsr { const int64_t *rowptr; const int32_t *colind; const double *values; };
+CgMatrixOps cg_csr_ops(const CgCsr *m);
+
 // conjugated_gradient on the matrix `ops` describes.  ws: NULL = vectors of this call's own, gone on every path out; otherwise
 // a workspace reserved for n rows at least, which the call leaves as it found it.
 hipError_t conjugated_gradient_ops(hipStream_t stream, size_t n, const CgMatrixOps &ops, CgWorkspace *ws, const double *b, double *x,

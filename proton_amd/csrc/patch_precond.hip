@@ -1,0 +1,518 @@
+// patch_precond.hip -- an additive Schwarz preconditioner over patches of rows for the device conjugate gradient
+// (solver_cg.hpp:63-144 with  z = sum_p R_p^T (R_p A R_p^T)^-1 R_p r  where the reference multiplies by 1 / diag(A); the solve of
+// cuthho_square.cpp:915-919 on the face-only system), and the patch tables of that system: one patch per face, or per cell.
+//
+// A patch holds 1..16 rows.  P = 4, 8 or 16 consecutive lanes share a patch (the smallest P that holds the table's largest patch),
+// lane l owning row l: a 16-row patch fills a quarter of a wavefront, four patches a wavefront, and everything the lanes of a patch
+// exchange goes through __shfl of width P -- no LDS, no barrier, no divergence (a patch of m < P rows is padded by identity rows).
+//   factor: lane l gathers row l of A_p from the CSR arrays (binary search: columns are ascending), the group runs a right-looking
+//           Cholesky on the rows in registers, then lane l forms column l of W = L^-1 by forward substitution and stores it into the
+//           packed lower triangle of W (row i at i (i + 1) / 2).
+//   apply:  t = W r_p (lane l reads row l of W), z_p = W^T t (lane l reads column l): two triangular products without a dependent
+//           chain, symmetric by construction.  z_p goes to a patch-major buffer (slot = position in patch_rows); a second kernel
+//           sums each row's slots in ascending order (= ascending patch order) and forms the block partials of r . z.  No
+//           floating-point atomics: z is the same bits from call to call.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+#include "cg.hpp"
+#include "device_tmp.hpp"
+#include "patch_precond.hpp"
+#include "scan.hpp"
+
+namespace pa {
+
+namespace {
+
+constexpr int FLAG_REFUSAL = 0, FLAG_MAX_ROWS = 1, FLAG_FAILED = 2, NFLAGS = 4;
+
+inline size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// the parts of the scratch buffer
+struct Scratch {
+    double *zbuf;          // entries: the patches' results, patch-major
+    uint32_t *counts;      // n + 1: patches per row, then the fill cursor
+    uint32_t *blk;         // row blocks + 1: their totals, scanned
+    int32_t *flags;        // NFLAGS
+};
+inline uint32_t row_blocks(size_t n) { return (uint32_t)((n + SCAN_BLOCK - 1) / SCAN_BLOCK); }
+inline size_t scratch_bytes(size_t n, size_t entries)
+{
+    return round256(entries * 8) + round256((n + 1) * 4) + round256(((size_t)row_blocks(n) + 2) * 4) + round256(NFLAGS * 4);
+}
+inline Scratch scratch_parts(void *base, size_t n, size_t entries)
+{
+    char *p = (char *)base;
+    Scratch s;
+    s.zbuf = (double *)p; p += round256(entries * 8);
+    s.counts = (uint32_t *)p; p += round256((n + 1) * 4);
+    s.blk = (uint32_t *)p; p += round256(((size_t)row_blocks(n) + 2) * 4);
+    s.flags = (int32_t *)p;
+    return s;
+}
+
+}  // namespace
+
+const char *patch_refusal_text(int refusal)
+{
+    switch (refusal) {
+    case PATCH_BAD_SIZE: return "patch table: patch_ptr must start at 0 and every patch must hold 1 to 16 rows";
+    case PATCH_BAD_INDEX: return "patch table: a row index lies outside the system";
+    case PATCH_REPEATED_ROW: return "patch table: a patch names a row twice";
+    case PATCH_UNCOVERED_ROW: return "patch table: a row of the system lies in no patch";
+    case PATCH_TOO_LARGE: return "patch table: 2^31 rows or entries and more";
+    default: return "";
+    }
+}
+
+// ---- validation -------------------------------------------------------------------------------------------------------------------
+// ptr alone: ptr[0] = 0 and every difference within 1..16 (so ptr ascends and every offset is below ptr[npatches])
+__global__ __launch_bounds__(RB) void patch_ptr_check_kernel(size_t npatches, const int64_t *ptr, int32_t *flags)
+{
+    const size_t p = (size_t)blockIdx.x * RB + threadIdx.x;
+    if (p == 0 && ptr[0] != 0) atomicMax(&flags[FLAG_REFUSAL], (int32_t)PATCH_BAD_SIZE);
+    if (p >= npatches) return;
+    const int64_t m = ptr[p + 1] - ptr[p];
+    if (m < 1 || m > PATCH_MAX_ROWS) atomicMax(&flags[FLAG_REFUSAL], (int32_t)PATCH_BAD_SIZE);
+    else atomicMax(&flags[FLAG_MAX_ROWS], (int32_t)m);
+}
+
+// the rows of every patch (ptr has passed): in range, no repeats; counts[row] = patches that hold it
+__global__ __launch_bounds__(RB) void patch_rows_check_kernel(size_t n, size_t npatches, const int64_t *ptr, const int32_t *rows,
+                                                              uint32_t *counts, int32_t *flags)
+{
+    const size_t p = (size_t)blockIdx.x * RB + threadIdx.x;
+    if (p >= npatches) return;
+    const int64_t p0 = ptr[p];
+    const int m = (int)(ptr[p + 1] - p0);
+    for (int l = 0; l < m; ++l) {
+        const int32_t row = rows[p0 + l];
+        if (row < 0 || (size_t)row >= n) { atomicMax(&flags[FLAG_REFUSAL], (int32_t)PATCH_BAD_INDEX); continue; }
+        bool repeated = false;
+        for (int q = 0; q < l; ++q) repeated |= rows[p0 + q] == row;
+        if (repeated) atomicMax(&flags[FLAG_REFUSAL], (int32_t)PATCH_REPEATED_ROW);
+        atomicAdd(&counts[row], 1u);
+    }
+}
+
+// every row is covered; the totals of the row blocks
+__global__ __launch_bounds__(SCAN_BLOCK) void patch_cover_kernel(size_t n, const uint32_t *counts, uint32_t *blk, int32_t *flags)
+{
+    __shared__ uint32_t sh[SCAN_BLOCK / 64];
+    const size_t i = (size_t)blockIdx.x * SCAN_BLOCK + threadIdx.x;
+    const uint32_t c = i < n ? counts[i] : 0;
+    if (i < n && c == 0) atomicMax(&flags[FLAG_REFUSAL], (int32_t)PATCH_UNCOVERED_ROW);
+    uint32_t total;
+    block_exclusive_scan(c, sh, total);
+    if (threadIdx.x == 0) blk[blockIdx.x] = total;
+}
+
+// ---- the row-to-slots table: slot_ptr (n + 1) and behind it slot_idx (entries) ------------------------------------------------------
+__global__ __launch_bounds__(SCAN_BLOCK) void patch_slot_ptr_kernel(size_t n, uint32_t entries, uint32_t *counts, const uint32_t *blk,
+                                                                    int32_t *slot_ptr)
+{
+    __shared__ uint32_t sh[SCAN_BLOCK / 64];
+    const size_t i = (size_t)blockIdx.x * SCAN_BLOCK + threadIdx.x;
+    const uint32_t c = i < n ? counts[i] : 0;
+    uint32_t total;
+    const uint32_t at = blk[blockIdx.x] + block_exclusive_scan(c, sh, total);
+    if (i < n) { slot_ptr[i] = (int32_t)at; counts[i] = at; }
+    if (i == 0) slot_ptr[n] = (int32_t)entries;
+}
+
+__global__ __launch_bounds__(RB) void patch_slot_fill_kernel(size_t npatches, const int64_t *ptr, const int32_t *rows, uint32_t *cursor,
+                                                             int32_t *slot_idx)
+{
+    const size_t p = (size_t)blockIdx.x * RB + threadIdx.x;
+    if (p >= npatches) return;
+    const int64_t p0 = ptr[p];
+    const int m = (int)(ptr[p + 1] - p0);
+    for (int l = 0; l < m; ++l) slot_idx[atomicAdd(&cursor[rows[p0 + l]], 1u)] = (int32_t)(p0 + l);
+}
+
+// a row's slots ascending: the order of its patches, whatever order the fill reached them in
+__global__ __launch_bounds__(RB) void patch_slot_sort_kernel(size_t n, const int32_t *slot_ptr, int32_t *slot_idx)
+{
+    const size_t i = (size_t)blockIdx.x * RB + threadIdx.x;
+    if (i >= n) return;
+    const int32_t s0 = slot_ptr[i], s1 = slot_ptr[i + 1];
+    for (int32_t a = s0 + 1; a < s1; ++a) {
+        const int32_t v = slot_idx[a];
+        int32_t b = a;
+        for (; b > s0 && slot_idx[b - 1] > v; --b) slot_idx[b] = slot_idx[b - 1];
+        slot_idx[b] = v;
+    }
+}
+
+// ---- factor -------------------------------------------------------------------------------------------------------------------------
+// A(row, col) of a CSR matrix with ascending columns; an absent entry is zero
+__device__ __forceinline__ double csr_entry(const int64_t *rowptr, const int32_t *colind, const double *values, int32_t row, int32_t col)
+{
+    const int64_t end = rowptr[row + 1];
+    int64_t lo = rowptr[row], hi = end;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (colind[mid] < col) lo = mid + 1; else hi = mid;
+    }
+    return (lo < end && colind[lo] == col) ? values[lo] : 0.0;
+}
+
+template <int P>
+__global__ __launch_bounds__(RB) void patch_factor_kernel(size_t npatches, const int64_t *ptr, const int32_t *rows, const int64_t *rowptr,
+                                                          const int32_t *colind, const double *values, int stride, double *factors,
+                                                          int32_t *info, int32_t *flags)
+{
+    const size_t p = ((size_t)blockIdx.x * RB + threadIdx.x) / P;
+    const int l = threadIdx.x % P;
+    int64_t p0 = 0;
+    int m = 0;
+    if (p < npatches) { p0 = ptr[p]; m = (int)(ptr[p + 1] - p0); }
+    const bool act = l < m;
+    const int32_t gl = act ? rows[p0 + l] : -1;
+    // row l of A_p; the rows beyond the patch are the identity's
+    double a[P];
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+        const int32_t gj = __shfl(gl, j, P);
+        a[j] = (act && gj >= 0) ? csr_entry(rowptr, colind, values, gl, gj) : (l == j ? 1.0 : 0.0);
+    }
+    // Cholesky, right-looking: after step j, a[j] of lane i >= j is L(i, j)
+    int bad = 0;
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+        const double djj = __shfl(a[j], j, P);
+        if (!(djj > 0.0) && bad == 0) bad = j + 1;
+        const double ljj = sqrt(djj);
+        a[j] = l == j ? ljj : a[j] / ljj;
+#pragma unroll
+        for (int k = j + 1; k < P; ++k) {
+            const double lkj = __shfl(a[j], k, P);
+            a[k] -= a[j] * lkj;
+        }
+    }
+    // column l of W = L^-1: W(i, l) = (delta_il - sum_{k < i} L(i, k) W(k, l)) / L(i, i)
+    double w[P];
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+        double s = i == l ? 1.0 : 0.0;
+#pragma unroll
+        for (int k = 0; k < i; ++k) s -= __shfl(a[k], i, P) * w[k];
+        w[i] = s / __shfl(a[i], i, P);
+    }
+    if (p < npatches) {
+        double *W = factors + p * (size_t)stride;
+#pragma unroll
+        for (int i = 0; i < P; ++i)
+            if (act && i >= l && i < m) W[i * (i + 1) / 2 + l] = w[i];
+        for (int q = m * (m + 1) / 2 + l; q < stride; q += P) W[q] = 0.0;      // a smaller patch leaves the rest of its stride zero
+        if (l == 0) {
+            info[p] = bad;
+            if (bad) atomicAdd(&flags[FLAG_FAILED], 1);
+        }
+    }
+}
+
+// ---- apply --------------------------------------------------------------------------------------------------------------------------
+template <int P>
+__global__ __launch_bounds__(RB) void patch_apply_kernel(size_t npatches, const int64_t *ptr, const int32_t *rows, const double *factors,
+                                                         int stride, const double *r, double *zbuf)
+{
+    const size_t p = ((size_t)blockIdx.x * RB + threadIdx.x) / P;
+    const int l = threadIdx.x % P;
+    int64_t p0 = 0;
+    int m = 0;
+    if (p < npatches) { p0 = ptr[p]; m = (int)(ptr[p + 1] - p0); }
+    const bool act = l < m;
+    const double rl = act ? r[rows[p0 + l]] : 0.0;
+    const double *W = factors + (p < npatches ? p : 0) * (size_t)stride;
+    double t = 0.0;
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+        const double rj = __shfl(rl, j, P);
+        if (act && j <= l) t += W[l * (l + 1) / 2 + j] * rj;
+    }
+    double z = 0.0;
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+        const double ti = __shfl(t, i, P);
+        if (act && i >= l && i < m) z += W[i * (i + 1) / 2 + l] * ti;
+    }
+    if (act) zbuf[p0 + l] = z;
+}
+
+// z_i = the sum of row i's slots in ascending order; the block partials of r . z
+__global__ __launch_bounds__(RB) void patch_sum_kernel(size_t n, const int32_t *slot_ptr, const int32_t *slot_idx, const double *zbuf,
+                                                       const double *r, double *z, double *part_rz)
+{
+    __shared__ double sh[RB / 64];
+    const size_t i = (size_t)blockIdx.x * RB + threadIdx.x;
+    double rz = 0.0;
+    if (i < n) {
+        double zi = 0.0;
+        for (int32_t s = slot_ptr[i]; s < slot_ptr[i + 1]; ++s) zi += zbuf[slot_idx[s]];
+        z[i] = zi;
+        rz = r[i] * zi;
+    }
+    const double tot = block_sum(rz, sh);
+    if (part_rz != nullptr && threadIdx.x == 0) part_rz[blockIdx.x] = tot;
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------------------------
+hipError_t patch_query(hipStream_t stream, size_t n, size_t npatches, const int64_t *ptr, PatchSizes *out, int *refusal)
+{
+    *out = PatchSizes();
+    *refusal = PATCH_OK;
+    if (n >= ((size_t)1 << 31) || npatches >= ((size_t)1 << 31)) { *refusal = PATCH_TOO_LARGE; return hipSuccess; }
+    int32_t *d_flags = nullptr;
+    hipError_t e = hipMalloc((void **)&d_flags, NFLAGS * 4);
+    if (e != hipSuccess) return e;
+    int32_t h[NFLAGS] = {0, 0, 0, 0};
+    int64_t entries = 0;
+    e = hipMemsetAsync(d_flags, 0, NFLAGS * 4, stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(patch_ptr_check_kernel, dim3((unsigned)((npatches + RB) / RB)), dim3(RB), 0, stream, npatches, ptr, d_flags);
+        e = hipMemcpyAsync(h, d_flags, NFLAGS * 4, hipMemcpyDeviceToHost, stream);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&entries, ptr + npatches, 8, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    (void)hipFree(d_flags);
+    if (e != hipSuccess) return e;
+    if (h[FLAG_REFUSAL]) { *refusal = h[FLAG_REFUSAL]; return hipSuccess; }
+    if (entries >= ((int64_t)1 << 31)) { *refusal = PATCH_TOO_LARGE; return hipSuccess; }
+    out->entries = (uint64_t)entries;
+    out->max_rows = h[FLAG_MAX_ROWS];
+    out->lanes = out->max_rows <= 4 ? 4 : out->max_rows <= 8 ? 8 : 16;
+    out->factor_doubles = (uint64_t)npatches * (uint64_t)(out->max_rows * (out->max_rows + 1) / 2);
+    out->slot_ints = (uint64_t)n + 1 + out->entries;
+    out->scratch_bytes = scratch_bytes(n, out->entries);
+    return hipSuccess;
+}
+
+hipError_t patch_factor(hipStream_t stream, const int64_t *rowptr, const int32_t *colind, const double *values, const PatchTable &t,
+                        const PatchSizes &sz, double *factors, int32_t *slots, void *scratch, int32_t *info, int *refusal, size_t *failed)
+{
+    *refusal = PATCH_OK;
+    *failed = 0;
+    if (t.n == 0 && t.npatches == 0) return hipSuccess;
+    const Scratch s = scratch_parts(scratch, t.n, sz.entries);
+    const uint32_t nb = row_blocks(t.n);
+    const unsigned gp = (unsigned)((t.npatches + RB - 1) / RB), gr = (unsigned)((t.n + RB - 1) / RB);
+    int32_t h[NFLAGS] = {0, 0, 0, 0};
+    hipError_t e = hipMemsetAsync(s.counts, 0, (t.n + 1) * 4, stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s.flags, 0, NFLAGS * 4, stream);
+    if (e != hipSuccess) return e;
+    if (t.npatches) hipLaunchKernelGGL(patch_rows_check_kernel, dim3(gp), dim3(RB), 0, stream, t.n, t.npatches, t.ptr, t.rows, s.counts, s.flags);
+    if (t.n) hipLaunchKernelGGL(patch_cover_kernel, dim3(nb), dim3(SCAN_BLOCK), 0, stream, t.n, s.counts, s.blk, s.flags);
+    e = hipMemcpyAsync(h, s.flags, NFLAGS * 4, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return e;
+    if (h[FLAG_REFUSAL]) { *refusal = h[FLAG_REFUSAL]; return hipSuccess; }      // (a table with patches and no rows: a bad index)
+    // the table holds: from here on it is indexed with
+    int32_t *slot_ptr = slots, *slot_idx = slots + t.n + 1;
+    hipLaunchKernelGGL(active_block_scan_kernel, dim3(1), dim3(SCAN_BLOCK), 0, stream, s.blk, nb);
+    hipLaunchKernelGGL(patch_slot_ptr_kernel, dim3(nb), dim3(SCAN_BLOCK), 0, stream, t.n, (uint32_t)sz.entries, s.counts, s.blk, slot_ptr);
+    hipLaunchKernelGGL(patch_slot_fill_kernel, dim3(gp), dim3(RB), 0, stream, t.npatches, t.ptr, t.rows, s.counts, slot_idx);
+    hipLaunchKernelGGL(patch_slot_sort_kernel, dim3(gr), dim3(RB), 0, stream, t.n, slot_ptr, slot_idx);
+    const int stride = sz.max_rows * (sz.max_rows + 1) / 2;
+    const unsigned gf = (unsigned)((t.npatches * (size_t)sz.lanes + RB - 1) / RB);
+    if (sz.lanes == 4)
+        hipLaunchKernelGGL(patch_factor_kernel<4>, dim3(gf), dim3(RB), 0, stream, t.npatches, t.ptr, t.rows, rowptr, colind, values, stride, factors, info, s.flags);
+    else if (sz.lanes == 8)
+        hipLaunchKernelGGL(patch_factor_kernel<8>, dim3(gf), dim3(RB), 0, stream, t.npatches, t.ptr, t.rows, rowptr, colind, values, stride, factors, info, s.flags);
+    else
+        hipLaunchKernelGGL(patch_factor_kernel<16>, dim3(gf), dim3(RB), 0, stream, t.npatches, t.ptr, t.rows, rowptr, colind, values, stride, factors, info, s.flags);
+    e = hipMemcpyAsync(h, s.flags, NFLAGS * 4, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    *failed = (size_t)h[FLAG_FAILED];
+    return hipSuccess;
+}
+
+void patch_apply(hipStream_t stream, const PatchTable &t, const PatchSizes &sz, const double *factors, const int32_t *slots,
+                 void *scratch, const double *r, double *z, double *part_rz)
+{
+    if (t.n == 0) return;
+    const Scratch s = scratch_parts(scratch, t.n, sz.entries);
+    const int stride = sz.max_rows * (sz.max_rows + 1) / 2;
+    const unsigned ga = (unsigned)((t.npatches * (size_t)sz.lanes + RB - 1) / RB);
+    if (sz.lanes == 4)
+        hipLaunchKernelGGL(patch_apply_kernel<4>, dim3(ga), dim3(RB), 0, stream, t.npatches, t.ptr, t.rows, factors, stride, r, s.zbuf);
+    else if (sz.lanes == 8)
+        hipLaunchKernelGGL(patch_apply_kernel<8>, dim3(ga), dim3(RB), 0, stream, t.npatches, t.ptr, t.rows, factors, stride, r, s.zbuf);
+    else
+        hipLaunchKernelGGL(patch_apply_kernel<16>, dim3(ga), dim3(RB), 0, stream, t.npatches, t.ptr, t.rows, factors, stride, r, s.zbuf);
+    hipLaunchKernelGGL(patch_sum_kernel, dim3((unsigned)((t.n + RB - 1) / RB)), dim3(RB), 0, stream, t.n, slots, slots + t.n + 1, s.zbuf, r, z,
+                       part_rz);
+}
+
+// ---- the solver ---------------------------------------------------------------------------------------------------------------------
+// x = 0, r = b; partials of r . r   (solver_cg.hpp:73-84)
+__global__ __launch_bounds__(RB) void pcg_init_kernel(size_t n, const double *b, double *x, double *r, double *part_a)
+{
+    __shared__ double sh[RB / 64];
+    const size_t i = (size_t)blockIdx.x * RB + threadIdx.x;
+    double rr = 0.0;
+    if (i < n) {
+        const double ri = b[i];
+        x[i] = 0.0; r[i] = ri;
+        rr = ri * ri;
+    }
+    const double t0 = block_sum(rr, sh);
+    if (threadIdx.x == 0) part_a[blockIdx.x] = t0;
+}
+
+// x += alpha d, r -= alpha y; partials of r . r   (solver_cg.hpp:103-109)
+__global__ __launch_bounds__(RB) void pcg_update_kernel(size_t n, const CgScalars *sc, const double *d, const double *y, double *x, double *r,
+                                                        double *part_a)
+{
+    __shared__ double sh[RB / 64];
+    const size_t i = (size_t)blockIdx.x * RB + threadIdx.x;
+    const double alpha = sc->alpha;
+    double rr = 0.0;
+    if (i < n) {
+        x[i] += alpha * d[i];
+        const double ri = r[i] - alpha * y[i];
+        r[i] = ri;
+        rr = ri * ri;
+    }
+    const double t0 = block_sum(rr, sh);
+    if (threadIdx.x == 0) part_a[blockIdx.x] = t0;
+}
+
+// d = z + beta d   (solver_cg.hpp:128); first = 1: d = z
+__global__ __launch_bounds__(RB) void pcg_direction_kernel(size_t n, const CgScalars *sc, int first, const double *z, double *d)
+{
+    const size_t i = (size_t)blockIdx.x * RB + threadIdx.x;
+    if (i >= n) return;
+    d[i] = first ? z[i] : z[i] + sc->beta * d[i];
+}
+
+hipError_t conjugated_gradient_patch(hipStream_t stream, size_t n, const int64_t *rowptr, const int32_t *colind, const double *values,
+                                     const double *b, double *x, size_t npatches, const int64_t *patch_ptr, const int32_t *patch_rows,
+                                     double convergence_threshold, double divergence_threshold, size_t max_iter, int *exit_reason,
+                                     size_t *iterations, double *relative_residual, int *status, int *refusal)
+{
+    *status = 0;
+    *refusal = PATCH_OK;
+    size_t iter = 0;
+    int reason = 0;
+    double rr = 0.0;
+    hipError_t e = hipSuccess;
+    if (n) {
+        PatchSizes sz;
+        e = patch_query(stream, n, npatches, patch_ptr, &sz, refusal);
+        if (e != hipSuccess) return e;
+        if (*refusal) { *status = 1; return hipSuccess; }
+        const PatchTable t{n, npatches, patch_ptr, patch_rows};
+        DeviceTmp tmp(stream);
+        double *factors = nullptr, *z = nullptr;
+        int32_t *slots = nullptr, *info = nullptr;
+        char *scratch = nullptr;
+        if (!tmp.alloc(&factors, (size_t)sz.factor_doubles + 1) || !tmp.alloc(&z, n) || !tmp.alloc(&slots, (size_t)sz.slot_ints) ||
+            !tmp.alloc(&info, npatches + 1) || !tmp.alloc(&scratch, (size_t)sz.scratch_bytes))
+            return tmp.error();
+        size_t failed = 0;
+        e = patch_factor(stream, rowptr, colind, values, t, sz, factors, slots, scratch, info, refusal, &failed);
+        if (e != hipSuccess) return e;
+        if (*refusal) { *status = 1; return hipSuccess; }
+        if (failed) { *status = 2; return hipSuccess; }
+        CgWorkspace ws;
+        e = cg_workspace_reserve(&ws, n);
+        if (e != hipSuccess) return e;
+#define PCG_TRY(call) do { e = (call); if (e != hipSuccess) { cg_workspace_release(&ws); return e; } } while (0)
+        const CgCsr m{rowptr, colind, values};
+        const CgMatrixOps ops = cg_csr_ops(&m);
+        const unsigned gv = (unsigned)((n + RB - 1) / RB), gs = (unsigned)((n * ROW_LANES + RB - 1) / RB);
+        double *r = ws.r, *d = ws.d, *y = ws.y, *pa_ = ws.part_a, *pb_ = ws.part_b;
+        CgScalars *sc = (CgScalars *)ws.scalars;
+        CgScalars h{};
+        reason = 2;
+        hipLaunchKernelGGL(pcg_init_kernel, dim3(gv), dim3(RB), 0, stream, n, b, x, r, pa_);                                  // :73-84
+        patch_apply(stream, t, sz, factors, slots, scratch, r, z, pb_);
+        hipLaunchKernelGGL(pcg_direction_kernel, dim3(gv), dim3(RB), 0, stream, n, sc, 1, z, d);
+        cg_launch_reduce(stream, 0, (size_t)gv, pa_, pb_, sc);
+        PCG_TRY(hipMemcpyAsync(&h, sc, sizeof(h), hipMemcpyDeviceToHost, stream));
+        PCG_TRY(hipStreamSynchronize(stream));
+        const double nr0 = sqrt(h.nr2);
+        if (!(nr0 > 0.0)) { reason = 0; }                       // b = 0: x = 0 is the solution
+        else
+            for (;;) {
+                ops.spmv(ops.user, stream, n, d, y, pa_);                                                                     // :99
+                cg_launch_reduce(stream, 1, (size_t)gs, pa_, nullptr, sc);                                                    // :101-102
+                hipLaunchKernelGGL(pcg_update_kernel, dim3(gv), dim3(RB), 0, stream, n, sc, d, y, x, r, pa_);                // :103-105
+                patch_apply(stream, t, sz, factors, slots, scratch, r, z, pb_);
+                cg_launch_reduce(stream, 2, (size_t)gv, pa_, pb_, sc);
+                PCG_TRY(hipMemcpyAsync(&h, sc, sizeof(h), hipMemcpyDeviceToHost, stream));
+                PCG_TRY(hipStreamSynchronize(stream));
+                rr = sqrt(h.nr2) / nr0;
+                if (rr < convergence_threshold) { reason = 0; break; }      // :107-110
+                if (iter > max_iter) { reason = 2; break; }                  // :112-115
+                if (rr > divergence_threshold) { reason = 1; break; }        // :117-120
+                if (!(rr == rr)) { reason = 1; break; }                      // NaN: stop instead of spinning
+                hipLaunchKernelGGL(pcg_direction_kernel, dim3(gv), dim3(RB), 0, stream, n, sc, 0, z, d);                     // :126-128
+                iter++;
+            }
+        PCG_TRY(hipGetLastError());
+#undef PCG_TRY
+        cg_workspace_release(&ws);
+    }
+    if (exit_reason) *exit_reason = reason;
+    if (iterations) *iterations = iter;
+    if (relative_residual) *relative_residual = rr;
+    return hipSuccess;
+}
+
+// ---- the patch tables of the face-only system ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(RB) void face_patches_kernel(uint32_t nfaces, int fbs, int64_t *ptr, int32_t *rows)
+{
+    const size_t i = (size_t)blockIdx.x * RB + threadIdx.x;
+    if (i <= nfaces) ptr[i] = (int64_t)i * fbs;
+    if (i < (size_t)nfaces * fbs) rows[i] = (int32_t)i;
+}
+
+__global__ __launch_bounds__(RB) void cell_patch_flags_kernel(uint32_t ncells, const uint32_t *cprefix, uint8_t *flags)
+{
+    const size_t c = (size_t)blockIdx.x * RB + threadIdx.x;
+    if (c < ncells) flags[c] = cprefix[c + 1] > cprefix[c] ? 1 : 0;
+}
+
+__global__ __launch_bounds__(RB) void cell_patches_kernel(uint32_t ncells, uint32_t npatches, const uint32_t *cell_faces,
+                                                          const int32_t *face_compress, const uint32_t *cprefix, const int32_t *index, int fbs,
+                                                          int64_t *ptr, int32_t *rows)
+{
+    const size_t c = (size_t)blockIdx.x * RB + threadIdx.x;
+    if (c == 0) ptr[npatches] = (int64_t)cprefix[ncells] * fbs;
+    if (c >= ncells) return;
+    const int32_t p = index[c];
+    if (p < 0) return;
+    int64_t at = (int64_t)cprefix[c] * fbs;
+    ptr[p] = at;
+    for (int lf = 0; lf < 4; ++lf) {                     // bottom, right, top, left
+        const int32_t comp = face_compress[cell_faces[4 * c + lf]];
+        if (comp < 0) continue;
+        for (int k = 0; k < fbs; ++k) rows[at++] = comp * fbs + k;
+    }
+}
+
+void face_patches(hipStream_t stream, uint32_t nfaces, int fbs, int64_t *ptr, int32_t *rows)
+{
+    const size_t total = (size_t)nfaces * fbs + 1;
+    hipLaunchKernelGGL(face_patches_kernel, dim3((unsigned)((total + RB - 1) / RB)), dim3(RB), 0, stream, nfaces, fbs, ptr, rows);
+}
+
+void cell_patch_flags(hipStream_t stream, uint32_t ncells, const uint32_t *cprefix, uint8_t *flags)
+{
+    if (ncells) hipLaunchKernelGGL(cell_patch_flags_kernel, dim3((ncells + RB - 1) / RB), dim3(RB), 0, stream, ncells, cprefix, flags);
+}
+
+void cell_patches(hipStream_t stream, uint32_t ncells, uint32_t npatches, const uint32_t *cell_faces, const int32_t *face_compress,
+                  const uint32_t *cprefix, const int32_t *index, int fbs, int64_t *ptr, int32_t *rows)
+{
+    hipLaunchKernelGGL(cell_patches_kernel, dim3((ncells + RB) / RB), dim3(RB), 0, stream, ncells, npatches, cell_faces, face_compress, cprefix,
+                       index, fbs, ptr, rows);
+}
+
+}  // namespace pa

@@ -11,10 +11,6 @@
 
 namespace pa {
 
-struct CgScalars {                 // device-resident scalars of the iteration
-    double rho, dy, nr2, rho_new, alpha, beta;
-};
-
 // iA = 1 / diag(A)   (solver_cg.hpp:77-80)
 __global__ __launch_bounds__(RB) void cg_inv_diag_kernel(size_t n, const int64_t *rowptr, const int32_t *colind, const double *values,
                                                          double *iA)
@@ -192,9 +188,14 @@ hipError_t conjugated_gradient_ops(hipStream_t stream, size_t n, const CgMatrixO
     return hipSuccess;
 }
 
+void cg_launch_reduce(hipStream_t stream, int mode, size_t nparts, const double *part_a, const double *part_b, void *scalars)
+{
+    hipLaunchKernelGGL(cg_reduce_kernel, dim3(1), dim3(RB), 0, stream, mode, nparts, part_a, part_b, (CgScalars *)scalars);
+}
+
 // the plain CSR matrix pa_csr_from_triplets builds
 namespace {
-struct CsrMatrix { const int64_t *rowptr; const int32_t *colind; const double *values; };
+using CsrMatrix = CgCsr;
 void csr_inv_diag(void *user, hipStream_t stream, size_t n, double *iA)
 {
     const CsrMatrix *m = (const CsrMatrix *)user;
@@ -207,6 +208,8 @@ void csr_spmv(void *user, hipStream_t stream, size_t n, const double *d, double 
                        m->values, d, y, part_dy);
 }
 }  // namespace
+
+CgMatrixOps cg_csr_ops(const CgCsr *m) { return CgMatrixOps{(void *)m, csr_inv_diag, csr_spmv}; }
 
 hipError_t conjugated_gradient(hipStream_t stream, size_t n, const int64_t *rowptr, const int32_t *colind, const double *values,
                                const double *b, double *x, double convergence_threshold, double divergence_threshold,

@@ -1094,12 +1094,14 @@ class assembler {
     // The same loop (cuthho_square.cpp:881-905), its solve (:915-919) and what take_local_data (:959-962) reads, with the cell
     // unknowns eliminated on the device: the operators as assemble_all_fictdom, every cell's packed condensed record
     // (pa_fictdom_condensed_ops_batch: cut cells in double-double), the face-only system directly in CSR (pa_condensed_csr_*),
-    // pa_conjugated_gradient on it and the cell unknowns recovered (pa_fictdom_condensed_recover).  Returns the full solution
+    // pa_conjugated_gradient on it (patches = PA_PATCH_FACE / PA_PATCH_CELL: pa_conjugated_gradient_patch on the table of
+    // pa_condensed_patches) and the cell unknowns recovered (pa_fictdom_condensed_recover).  Returns the full solution
     // vector in the reference's numbering -- what solver.solve(RHS) leaves in `sol` -- for take_local_data; LHS / RHS are left
     // untouched.
     template <typename LevelSet, typename Location>
     std::vector<T> solve_condensed_fictdom(const Mesh &msh, const LevelSet & /*level_set_function*/, Location where, int rhs_fn, int dirichlet_fn,
-                                           const cg_params<T> &cgp, size_t *iterations = nullptr, cg_exit_reason *exit_reason = nullptr)
+                                           const cg_params<T> &cgp, size_t *iterations = nullptr, cg_exit_reason *exit_reason = nullptr,
+                                           int patches = -1)
     {
         if (!msh.preprocessed) throw std::logic_error("cutHHO mesh not preprocessed");
         auto &dev = proton_amd::device::instance();
@@ -1130,9 +1132,21 @@ class assembler {
         int32_t reason = 0;
         size_t iters = 0;
         double rr = 0.0;
-        dev.check(pa_conjugated_gradient(dev.ctx(), nF, d_rowptr.get(), d_colind.get(), d_values.get(), d_b.get(), d_xF.get(),
-                                         cgp.convergence_threshold, cgp.divergence_threshold, cgp.max_iter, cgp.apply_preconditioner ? 1 : 0,
-                                         &reason, &iters, &rr), "pa_conjugated_gradient");
+        if (patches < 0)
+            dev.check(pa_conjugated_gradient(dev.ctx(), nF, d_rowptr.get(), d_colind.get(), d_values.get(), d_b.get(), d_xF.get(),
+                                             cgp.convergence_threshold, cgp.divergence_threshold, cgp.max_iter, cgp.apply_preconditioner ? 1 : 0,
+                                             &reason, &iters, &rr), "pa_conjugated_gradient");
+        else {
+            // patches = PA_PATCH_FACE / PA_PATCH_CELL: the patch preconditioner in place of the point Jacobi
+            size_t npatches = 0, entries = 0;
+            dev.check(pa_condensed_patches_query(dev.ctx(), di.c_abi(), patches, &npatches, &entries), "pa_condensed_patches_query");
+            proton_amd::device_buffer<int64_t> d_pptr(npatches + 1);
+            proton_amd::device_buffer<int32_t> d_prows(entries + 1);
+            dev.check(pa_condensed_patches(dev.ctx(), di.c_abi(), patches, d_pptr.get(), d_prows.get()), "pa_condensed_patches");
+            dev.check(pa_conjugated_gradient_patch(dev.ctx(), nF, d_rowptr.get(), d_colind.get(), d_values.get(), d_b.get(), d_xF.get(), npatches,
+                                                   d_pptr.get(), d_prows.get(), cgp.convergence_threshold, cgp.divergence_threshold,
+                                                   cgp.max_iter, &reason, &iters, &rr), "pa_conjugated_gradient_patch");
+        }
         if (cgp.verbose) std::cout << " -> Iteration " << iters << ", rr = " << rr << std::endl;
         if (iterations) *iterations = iters;
         if (exit_reason)
