@@ -1,7 +1,10 @@
-// cg.hpp -- what another translation unit needs to run solver.hip's conjugate gradient on a matrix it does not hold as a plain
-// CSR: the two launches that read the matrix (inverse diagonal, product with the search direction) behind two callbacks, and
-// the solver's device vectors as a workspace that outlives one solve.  Everything else -- the vector kernels, the reductions,
-// the exit tests and their order (solver_cg.hpp:63-144) -- is solver.hip's and runs unchanged.
+// cg.hpp -- the conjugate gradient of solver.hip as its other translation units see it.  The six kernels of the iteration
+// (inverse diagonal, product with the search direction, first residual, update, new direction, reduction of the block partials)
+// are stated once, in solver.hip, as templates over the small device-side structs declared here: where a row of the matrix is
+// stored and how a column finds its place in the vector (CgRows*), how the preconditioned residual is had (CgJacobi, CgStoredZ),
+// and where the scalar of a step comes from (CgStep).  Two host loops launch them: the one-rank loop (conjugated_gradient_one_rank:
+// one host read per iteration) and the row-partitioned loop (conjugated_gradient_rows: the sums go over the ranks).  The exit tests
+// and their order are solver_cg.hpp:63-144's in both.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -13,6 +16,10 @@ namespace pa {
 
 constexpr int RB = 256;            // threads per block of the vector kernels
 constexpr int ROW_LANES = 16;      // lanes that share a row in the SpMV (HHO rows hold 20-130 entries)
+
+// the two grids of the solver: one thread per row, ROW_LANES lanes per row
+inline unsigned cg_vector_grid(size_t n) { return (unsigned)((n + RB - 1) / RB); }
+inline unsigned cg_row_grid(size_t n) { return (unsigned)((n * ROW_LANES + RB - 1) / RB); }
 
 // sum of v over the block (RB threads), the same value in every thread; sh holds RB / 64 doubles
 __device__ inline double block_sum(double v, double *sh)
@@ -29,38 +36,92 @@ __device__ inline double block_sum(double v, double *sh)
     return s;
 }
 
-// The matrix of a solve.  inv_diag: iA[i] = 1 / A_ii, i < n, one thread per row.  spmv: y = A d and part_dy[blk] = the sum of
-// d[row] y[row] over the rows of block blk, for the grid of cg_spmv_kernel -- (n ROW_LANES + RB - 1) / RB blocks of RB threads,
-// ROW_LANES consecutive lanes per row, block_sum over the block -- so that the iterates do not depend on who formed the product.
-struct CgMatrixOps {
-    void *user;
-    void (*inv_diag)(void *user, hipStream_t stream, size_t n, double *iA);
-    void (*spmv)(void *user, hipStream_t stream, size_t n, const double *d, double *y, double *part_dy);
+// ---- row views: the matrix kernels ask a view where row r of the system is stored, whether entry (r, c) is the diagonal's, whether
+// column c is read at all, where it is in the vector, and where the row's own entry of the vector is.
+// plain: the CSR arrays are the system
+struct CgRowsPlain {
+    __device__ int64_t storage(size_t r) const { return (int64_t)r; }
+    __device__ bool diagonal(int32_t c, size_t r) const { return (size_t)c == r; }
+    __device__ bool reads(int32_t, size_t) const { return true; }
+    __device__ double at(const double *d, int32_t c) const { return d[c]; }
+    __device__ double own(const double *d, size_t r) const { return d[r]; }
+};
+// window: rows [row_begin, row_begin + n) of a larger system with global column indices; the vector is a window that starts at
+// column col0 and holds the rows' own entries from own0 on
+struct CgRowsWindow {
+    int64_t row_begin, col0;
+    size_t own0;
+    __device__ int64_t storage(size_t r) const { return (int64_t)r; }
+    __device__ bool diagonal(int32_t c, size_t r) const { return (int64_t)c == row_begin + (int64_t)r; }
+    __device__ bool reads(int32_t, size_t) const { return true; }
+    __device__ double at(const double *d, int32_t c) const { return d[(int64_t)c - col0]; }
+    __device__ double own(const double *d, size_t r) const { return d[own0 + r]; }
+};
+// mapped: row r is CSR row rowmap[r], and the columns at n and beyond are not the system's
+struct CgRowsMapped {
+    const int32_t *rowmap;
+    __device__ int64_t storage(size_t r) const { return rowmap[r]; }
+    __device__ bool diagonal(int32_t c, size_t r) const { return (size_t)c == r; }
+    __device__ bool reads(int32_t c, size_t n) const { return (size_t)c < n; }
+    __device__ double at(const double *d, int32_t c) const { return d[(size_t)c]; }
+    __device__ double own(const double *d, size_t r) const { return d[r]; }
 };
 
-// The device vectors of a solve of up to `rows` unknowns.  cg_workspace_reserve leaves the workspace empty when it fails.
+// ---- the preconditioned residual z = M^-1 r of the vector kernels
+// Jacobi or none: z_i = iA_i r_i or r_i, formed where it is used
+struct CgJacobi {
+    static constexpr bool stored = false;
+    const double *iA;
+    int precond;
+    __device__ double z(size_t i, double ri) const { return precond ? iA[i] * ri : ri; }
+};
+// a vector somebody else wrote, with the partials of r . z: the first residual and the update form no r . z and leave d alone;
+// first: the direction is z itself
+struct CgStoredZ {
+    static constexpr bool stored = true;
+    const double *zv;
+    int first;
+    __device__ double z(size_t i, double) const { return zv[i]; }
+};
+
+// the scalar of a step (alpha of the update, beta of the direction): on the device where the reduction left it, or by value
+struct CgStep {
+    const double *on_device;
+    double value;
+    __device__ double get() const { return on_device ? *on_device : value; }
+};
+
+// The matrix of a one-rank solve: CSR arrays, and rowmap = NULL (the arrays are the system) or the storage row of every row of
+// the system (CgRowsMapped).
+struct CgCsr { const int64_t *rowptr; const int32_t *colind; const double *values; const int32_t *rowmap; };
+
+// The scalars of the iteration, resident on the device, and the modes of cg_reduce_kernel that fill them (solver.hip).
+struct CgScalars { double rho, dy, nr2, rho_new, alpha, beta; };
+
+// The device vectors of a solve of up to `rows` unknowns, with d_len >= rows entries for the search direction (the row-partitioned
+// solve keeps a window there).  cg_workspace_reserve leaves the workspace empty when it fails.
 struct CgWorkspace {
     size_t rows = 0;
     double *r = nullptr, *d = nullptr, *y = nullptr, *iA = nullptr, *part_a = nullptr, *part_b = nullptr;
-    void *scalars = nullptr;
+    CgScalars *scalars = nullptr;
 };
-hipError_t cg_workspace_reserve(CgWorkspace *ws, size_t rows);
+hipError_t cg_workspace_reserve(CgWorkspace *ws, size_t rows, size_t d_len);
 void cg_workspace_release(CgWorkspace *ws);
 
-// What a solver with an explicit preconditioned residual (patch_precond.hip) shares with this one: the device-resident scalars of
-// the iteration, the one-block reduction of the per-block partials with the scalar algebra of the step (cg_reduce_kernel: mode 0
-// after the first residual, 1 after the product, 2 after the update), and the plain CSR matrix behind CgMatrixOps (m must outlive
-// the ops).
-struct CgScalars { double rho, dy, nr2, rho_new, alpha, beta; };
-void cg_launch_reduce(hipStream_t stream, int mode, size_t nparts, const double *part_a, const double *part_b, void *scalars);
-struct CgCsr { const int64_t *rowptr; const int32_t *colind; const double *values; };
-CgMatrixOps cg_csr_ops(const CgCsr *m);
+// A preconditioner with an explicit z: apply writes z = M^-1 r and the block partials of r . z (cg_vector_grid(n) of them, in the
+// blocks of the vector kernels) on the stream.  z holds n doubles and is the caller's.
+struct CgPreconditioner {
+    void *user;
+    void (*apply)(void *user, hipStream_t stream, const double *r, double *z, double *part_rz);
+    double *z;
+};
 
-// conjugated_gradient on the matrix `ops` describes.  ws: NULL = vectors of this call's own, gone on every path out; otherwise
-// a workspace reserved for n rows at least, which the call leaves as it found it.
-hipError_t conjugated_gradient_ops(hipStream_t stream, size_t n, const CgMatrixOps &ops, CgWorkspace *ws, const double *b, double *x,
-                                   double convergence_threshold, double divergence_threshold, size_t max_iter, int precond,
-                                   int *exit_reason, size_t *iterations, double *relative_residual);
+// conjugated_gradient on one rank.  pre: NULL = Jacobi (precond != 0) or none, fused into the vector kernels; otherwise z comes from
+// pre->apply and precond is not read.  ws: NULL = vectors of this call's own, gone on every path out; otherwise a workspace
+// reserved for n rows at least, which the call leaves as it found it.
+hipError_t conjugated_gradient_one_rank(hipStream_t stream, size_t n, const CgCsr &m, const CgPreconditioner *pre, CgWorkspace *ws,
+                                        const double *b, double *x, double convergence_threshold, double divergence_threshold,
+                                        size_t max_iter, int precond, int *exit_reason, size_t *iterations, double *relative_residual);
 
 // conjugated_gradient on a plain CSR matrix (solver_cg.hpp:63-144)
 hipError_t conjugated_gradient(hipStream_t stream, size_t n, const int64_t *rowptr, const int32_t *colind, const double *values,

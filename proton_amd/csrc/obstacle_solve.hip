@@ -10,9 +10,10 @@
 // reference's own conjugate gradient (solver.hip) and the multipliers follow from their rows.
 //
 // K is never formed.  Row r of K is CSR row rowmap[r]: the inverse of A_ct for r < num_I (one scatter), r + num_A for the face
-// rows.  Only the two kernels that read the matrix -- inverse diagonal and SpMV -- go through the map; they visit the entries of
-// a row in the order, with the lane assignment and the block partials (indexed by K's row number) of solver.hip's kernels on K
-// extracted into arrays of its own, so the iterates are the same bit for bit.
+// rows.  The map goes to solver.hip with the CSR arrays (CgCsr::rowmap): its two kernels that read the matrix -- inverse diagonal
+// and SpMV -- are instantiated for the mapped row view (CgRowsMapped, cg.hpp), one body with the plain one, so the iterates are
+// those of the solver on K extracted into arrays of its own, bit for bit.  A kept row holds no column at or beyond nk; the view's
+// test keeps a system that is not obstacle_csr.hip's from reading past d.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -42,44 +43,6 @@ __global__ __launch_bounds__(RB) void obstacle_gather_rhs_kernel(size_t n, const
 {
     const size_t i = (size_t)blockIdx.x * RB + threadIdx.x;
     if (i < n) bk[i] = RHS[rowmap[i]];
-}
-
-// iA = 1 / diag(K)   (cg_inv_diag_kernel through the map)
-__global__ __launch_bounds__(RB) void obstacle_inv_diag_kernel(size_t n, const int32_t *rowmap, const int64_t *rowptr,
-                                                               const int32_t *colind, const double *values, double *iA)
-{
-    const size_t i = (size_t)blockIdx.x * RB + threadIdx.x;
-    if (i >= n) return;
-    const int64_t R = rowmap[i];
-    double d = 0.0;
-    for (int64_t k = rowptr[R]; k < rowptr[R + 1]; ++k)
-        if ((size_t)colind[k] == i) d = values[k];
-    iA[i] = 1.0 / d;
-}
-
-// y = K d and the per-block partial of d . y   (cg_spmv_kernel through the map: 16 lanes per row, rows of 1 + 4 fbs entries or
-// fewer for a cell, 2 + 7 fbs for a face).  A kept row holds no column at or beyond n; the test keeps a system that is not
-// obstacle_csr.hip's from reading past d.
-__global__ __launch_bounds__(RB) void obstacle_spmv_kernel(size_t n, const int32_t *rowmap, const int64_t *rowptr, const int32_t *colind,
-                                                           const double *values, const double *d, double *y, double *part_dy)
-{
-    __shared__ double sh[RB / 64];
-    const size_t row = ((size_t)blockIdx.x * RB + threadIdx.x) / ROW_LANES;
-    const int sub = threadIdx.x % ROW_LANES;
-    double s = 0.0;
-    if (row < n) {
-        const int64_t R = rowmap[row];
-        for (int64_t k = rowptr[R] + sub; k < rowptr[R + 1]; k += ROW_LANES) {
-            const size_t col = (size_t)colind[k];
-            if (col < n) s += values[k] * d[col];
-        }
-    }
-#pragma unroll
-    for (int o = ROW_LANES / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, ROW_LANES);
-    double dyp = 0.0;
-    if (row < n && sub == 0) { y[row] = s; dyp = d[row] * s; }
-    const double t = block_sum(dyp, sh);
-    if (threadIdx.x == 0) part_dy[blockIdx.x] = t;
 }
 
 // x[nk + B_ct[c]] = b_c - sum_j A_cj x_j over the columns below nk, for every active cell c: 16 lanes per cell row
@@ -185,7 +148,7 @@ hipError_t obstacle_workspace_reserve(ObstacleSolveWorkspace *ws, size_t rows, s
 {
     obstacle_workspace_release(ws);
     const size_t nn = rows ? rows : 1, nb = update_blocks(update_elements);
-    hipError_t e = cg_workspace_reserve(&ws->cg, nn);
+    hipError_t e = cg_workspace_reserve(&ws->cg, nn, nn);
     if (e == hipSuccess) e = hipMalloc((void **)&ws->rowmap, nn * sizeof(int32_t));
     if (e == hipSuccess) e = hipMalloc((void **)&ws->bk, nn * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void **)&ws->part_step, nb * sizeof(double));
@@ -205,22 +168,6 @@ void obstacle_workspace_release(ObstacleSolveWorkspace *ws)
 }
 
 namespace {
-
-struct MappedMatrix { const int32_t *rowmap; const int64_t *rowptr; const int32_t *colind; const double *values; };
-
-void mapped_inv_diag(void *user, hipStream_t stream, size_t n, double *iA)
-{
-    const MappedMatrix *m = (const MappedMatrix *)user;
-    hipLaunchKernelGGL(obstacle_inv_diag_kernel, dim3((unsigned)((n + RB - 1) / RB)), dim3(RB), 0, stream, n, m->rowmap, m->rowptr,
-                       m->colind, m->values, iA);
-}
-
-void mapped_spmv(void *user, hipStream_t stream, size_t n, const double *d, double *y, double *part_dy)
-{
-    const MappedMatrix *m = (const MappedMatrix *)user;
-    hipLaunchKernelGGL(obstacle_spmv_kernel, dim3((unsigned)((n * ROW_LANES + RB - 1) / RB)), dim3(RB), 0, stream, n, m->rowmap, m->rowptr,
-                       m->colind, m->values, d, y, part_dy);
-}
 
 // a workspace of the call's own where the caller brought none; gone with the scope, after the stream has drained
 struct WorkspaceScope {
@@ -265,10 +212,8 @@ hipError_t obstacle_block_solve(hipStream_t stream, const ObstacleBlockArgs &a, 
                            ws->bk);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
-        MappedMatrix m{ws->rowmap, a.rowptr, a.colind, a.values};
-        const CgMatrixOps ops{&m, mapped_inv_diag, mapped_spmv};
-        e = conjugated_gradient_ops(stream, (size_t)nk, ops, &ws->cg, ws->bk, a.x, convergence_threshold, divergence_threshold, max_iter,
-                                    precond, &reason, &iters, &rr);
+        e = conjugated_gradient_one_rank(stream, (size_t)nk, CgCsr{a.rowptr, a.colind, a.values, ws->rowmap}, nullptr, &ws->cg, ws->bk, a.x,
+                                         convergence_threshold, divergence_threshold, max_iter, precond, &reason, &iters, &rr);
         if (e != hipSuccess) return e;
     }
     if (num_A > 0) {

@@ -42,7 +42,7 @@ struct ObstacleBlockArgs {
 };
 
 // x = A^-1 RHS.  The kept rows (inactive cells in A_ct order, then the face rows) against the columns below nk are solved by
-// conjugated_gradient_ops through a row map, in place; every active cell's row then gives its multiplier.  ws: NULL = a
+// conjugated_gradient_one_rank through a row map, in place; every active cell's row then gives its multiplier.  ws: NULL = a
 // workspace of this call's own.  Returns after the stream has drained.
 hipError_t obstacle_block_solve(hipStream_t stream, const ObstacleBlockArgs &args, ObstacleSolveWorkspace *ws,
                                 double convergence_threshold, double divergence_threshold, size_t max_iter, int precond,

@@ -12,6 +12,8 @@
 //           chain, symmetric by construction.  z_p goes to a patch-major buffer (slot = position in patch_rows); a second kernel
 //           sums each row's slots in ascending order (= ascending patch order) and forms the block partials of r . z.  No
 //           floating-point atomics: z is the same bits from call to call.
+//   solve:  conjugated_gradient_patch validates and factors the table, then hands patch_apply to the one-rank loop of solver.hip as
+//           its preconditioner (CgPreconditioner, cg.hpp).  The iteration has no kernel and no loop of its own here.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -349,47 +351,7 @@ void patch_apply(hipStream_t stream, const PatchTable &t, const PatchSizes &sz, 
 }
 
 // ---- the solver ---------------------------------------------------------------------------------------------------------------------
-// x = 0, r = b; partials of r . r   (solver_cg.hpp:73-84)
-__global__ __launch_bounds__(RB) void pcg_init_kernel(size_t n, const double *b, double *x, double *r, double *part_a)
-{
-    __shared__ double sh[RB / 64];
-    const size_t i = (size_t)blockIdx.x * RB + threadIdx.x;
-    double rr = 0.0;
-    if (i < n) {
-        const double ri = b[i];
-        x[i] = 0.0; r[i] = ri;
-        rr = ri * ri;
-    }
-    const double t0 = block_sum(rr, sh);
-    if (threadIdx.x == 0) part_a[blockIdx.x] = t0;
-}
-
-// x += alpha d, r -= alpha y; partials of r . r   (solver_cg.hpp:103-109)
-__global__ __launch_bounds__(RB) void pcg_update_kernel(size_t n, const CgScalars *sc, const double *d, const double *y, double *x, double *r,
-                                                        double *part_a)
-{
-    __shared__ double sh[RB / 64];
-    const size_t i = (size_t)blockIdx.x * RB + threadIdx.x;
-    const double alpha = sc->alpha;
-    double rr = 0.0;
-    if (i < n) {
-        x[i] += alpha * d[i];
-        const double ri = r[i] - alpha * y[i];
-        r[i] = ri;
-        rr = ri * ri;
-    }
-    const double t0 = block_sum(rr, sh);
-    if (threadIdx.x == 0) part_a[blockIdx.x] = t0;
-}
-
-// d = z + beta d   (solver_cg.hpp:128); first = 1: d = z
-__global__ __launch_bounds__(RB) void pcg_direction_kernel(size_t n, const CgScalars *sc, int first, const double *z, double *d)
-{
-    const size_t i = (size_t)blockIdx.x * RB + threadIdx.x;
-    if (i >= n) return;
-    d[i] = first ? z[i] : z[i] + sc->beta * d[i];
-}
-
+// the table is validated and factored here; the iteration is solver.hip's one-rank loop with patch_apply as its preconditioner
 hipError_t conjugated_gradient_patch(hipStream_t stream, size_t n, const int64_t *rowptr, const int32_t *colind, const double *values,
                                      const double *b, double *x, size_t npatches, const int64_t *patch_ptr, const int32_t *patch_rows,
                                      double convergence_threshold, double divergence_threshold, size_t max_iter, int *exit_reason,
@@ -419,45 +381,16 @@ hipError_t conjugated_gradient_patch(hipStream_t stream, size_t n, const int64_t
         if (e != hipSuccess) return e;
         if (*refusal) { *status = 1; return hipSuccess; }
         if (failed) { *status = 2; return hipSuccess; }
-        CgWorkspace ws;
-        e = cg_workspace_reserve(&ws, n);
+        struct Applied { const PatchTable &t; const PatchSizes &sz; const double *factors; const int32_t *slots; void *scratch; };
+        Applied ap{t, sz, factors, slots, scratch};
+        auto apply = [](void *user, hipStream_t s, const double *r, double *zr, double *part_rz) {
+            const Applied &a = *(const Applied *)user;
+            patch_apply(s, a.t, a.sz, a.factors, a.slots, a.scratch, r, zr, part_rz);
+        };
+        const CgPreconditioner pre{&ap, apply, z};
+        e = conjugated_gradient_one_rank(stream, n, CgCsr{rowptr, colind, values, nullptr}, &pre, nullptr, b, x, convergence_threshold,
+                                         divergence_threshold, max_iter, 0, &reason, &iter, &rr);
         if (e != hipSuccess) return e;
-#define PCG_TRY(call) do { e = (call); if (e != hipSuccess) { cg_workspace_release(&ws); return e; } } while (0)
-        const CgCsr m{rowptr, colind, values};
-        const CgMatrixOps ops = cg_csr_ops(&m);
-        const unsigned gv = (unsigned)((n + RB - 1) / RB), gs = (unsigned)((n * ROW_LANES + RB - 1) / RB);
-        double *r = ws.r, *d = ws.d, *y = ws.y, *pa_ = ws.part_a, *pb_ = ws.part_b;
-        CgScalars *sc = (CgScalars *)ws.scalars;
-        CgScalars h{};
-        reason = 2;
-        hipLaunchKernelGGL(pcg_init_kernel, dim3(gv), dim3(RB), 0, stream, n, b, x, r, pa_);                                  // :73-84
-        patch_apply(stream, t, sz, factors, slots, scratch, r, z, pb_);
-        hipLaunchKernelGGL(pcg_direction_kernel, dim3(gv), dim3(RB), 0, stream, n, sc, 1, z, d);
-        cg_launch_reduce(stream, 0, (size_t)gv, pa_, pb_, sc);
-        PCG_TRY(hipMemcpyAsync(&h, sc, sizeof(h), hipMemcpyDeviceToHost, stream));
-        PCG_TRY(hipStreamSynchronize(stream));
-        const double nr0 = sqrt(h.nr2);
-        if (!(nr0 > 0.0)) { reason = 0; }                       // b = 0: x = 0 is the solution
-        else
-            for (;;) {
-                ops.spmv(ops.user, stream, n, d, y, pa_);                                                                     // :99
-                cg_launch_reduce(stream, 1, (size_t)gs, pa_, nullptr, sc);                                                    // :101-102
-                hipLaunchKernelGGL(pcg_update_kernel, dim3(gv), dim3(RB), 0, stream, n, sc, d, y, x, r, pa_);                // :103-105
-                patch_apply(stream, t, sz, factors, slots, scratch, r, z, pb_);
-                cg_launch_reduce(stream, 2, (size_t)gv, pa_, pb_, sc);
-                PCG_TRY(hipMemcpyAsync(&h, sc, sizeof(h), hipMemcpyDeviceToHost, stream));
-                PCG_TRY(hipStreamSynchronize(stream));
-                rr = sqrt(h.nr2) / nr0;
-                if (rr < convergence_threshold) { reason = 0; break; }      // :107-110
-                if (iter > max_iter) { reason = 2; break; }                  // :112-115
-                if (rr > divergence_threshold) { reason = 1; break; }        // :117-120
-                if (!(rr == rr)) { reason = 1; break; }                      // NaN: stop instead of spinning
-                hipLaunchKernelGGL(pcg_direction_kernel, dim3(gv), dim3(RB), 0, stream, n, sc, 0, z, d);                     // :126-128
-                iter++;
-            }
-        PCG_TRY(hipGetLastError());
-#undef PCG_TRY
-        cg_workspace_release(&ws);
     }
     if (exit_reason) *exit_reason = reason;
     if (iterations) *iterations = iter;

@@ -3,92 +3,125 @@
 // and offered by convergence_test) on the device, over the CSR matrix pa_csr_from_triplets builds.
 // Same recurrences, exit tests and exit order as the reference; the dot products are block-tree
 // reductions (deterministic run to run), not Eigen's sequential sums.
+//
+// Every kernel of the iteration is stated here, once, as a template over the structs of cg.hpp.  The plain matrix, the obstacle
+// problem's matrix behind its row map, the rows of one rank of a partitioned matrix, the Jacobi residual formed in place and the
+// patch preconditioner's stored one are instantiations of these bodies: the same statements in the same order, so that the
+// iterates of two solvers on the same system are the same bits by construction.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "cg.hpp"
+#include "device_tmp.hpp"
 
 namespace pa {
 
 // iA = 1 / diag(A)   (solver_cg.hpp:77-80)
-__global__ __launch_bounds__(RB) void cg_inv_diag_kernel(size_t n, const int64_t *rowptr, const int32_t *colind, const double *values,
-                                                         double *iA)
+template <class Rows>
+__global__ __launch_bounds__(RB) void cg_inv_diag_kernel(size_t n, Rows rows, const int64_t *rowptr, const int32_t *colind,
+                                                         const double *values, double *iA)
 {
     const size_t i = (size_t)blockIdx.x * RB + threadIdx.x;
     if (i >= n) return;
+    const int64_t R = rows.storage(i);
     double d = 0.0;
-    for (int64_t k = rowptr[i]; k < rowptr[i + 1]; ++k)
-        if ((size_t)colind[k] == i) d = values[k];
+    for (int64_t k = rowptr[R]; k < rowptr[R + 1]; ++k)
+        if (rows.diagonal(colind[k], i)) d = values[k];
     iA[i] = 1.0 / d;
 }
 
-// y = A d and the per-block partial of d . y
-__global__ __launch_bounds__(RB) void cg_spmv_kernel(size_t n, const int64_t *rowptr, const int32_t *colind, const double *values,
-                                                     const double *d, double *y, double *part_dy)
+// y = A d and the per-block partial of d . y: ROW_LANES consecutive lanes per row, lane l taking entries l, l + ROW_LANES, ... of the
+// row, a butterfly over the lanes of the row, block_sum over the rows of the block
+template <class Rows>
+__global__ __launch_bounds__(RB) void cg_spmv_kernel(size_t n, Rows rows, const int64_t *rowptr, const int32_t *colind,
+                                                     const double *values, const double *d, double *y, double *part_dy)
 {
     __shared__ double sh[RB / 64];
     const size_t row = ((size_t)blockIdx.x * RB + threadIdx.x) / ROW_LANES;
     const int sub = threadIdx.x % ROW_LANES;
     double s = 0.0;
-    if (row < n)
-        for (int64_t k = rowptr[row] + sub; k < rowptr[row + 1]; k += ROW_LANES) s += values[k] * d[colind[k]];
+    if (row < n) {
+        const int64_t R = rows.storage(row);
+        for (int64_t k = rowptr[R] + sub; k < rowptr[R + 1]; k += ROW_LANES) {
+            const int32_t c = colind[k];
+            if (rows.reads(c, n)) s += values[k] * rows.at(d, c);
+        }
+    }
 #pragma unroll
     for (int o = ROW_LANES / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, ROW_LANES);
     double dyp = 0.0;
-    if (row < n && sub == 0) { y[row] = s; dyp = d[row] * s; }
+    if (row < n && sub == 0) { y[row] = s; dyp = rows.own(d, row) * s; }
     const double t = block_sum(dyp, sh);
     if (threadIdx.x == 0) part_dy[blockIdx.x] = t;
 }
 
-// r = b - y (first residual, x = 0 means y = 0 is never formed: r = b), d = M^-1 r, partials of r.r and r.M^-1 r
-__global__ __launch_bounds__(RB) void cg_init_kernel(size_t n, const double *b, const double *iA, int precond, double *x, double *r,
-                                                     double *d, double *part_a, double *part_b)
+// r = b - y (first residual, x = 0 means y = 0 is never formed: r = b), partials of r.r; Jacobi: d = M^-1 r and partials of r.M^-1 r
+template <class Pre>
+__global__ __launch_bounds__(RB) void cg_init_kernel(size_t n, const double *b, Pre pre, double *x, double *r, double *d, double *part_a,
+                                                     double *part_b)
 {
     __shared__ double sh[RB / 64];
     const size_t i = (size_t)blockIdx.x * RB + threadIdx.x;
     double rr = 0.0, rz = 0.0;
     if (i < n) {
         const double ri = b[i];
-        const double zi = precond ? iA[i] * ri : ri;
-        x[i] = 0.0; r[i] = ri; d[i] = zi;
-        rr = ri * ri; rz = ri * zi;
+        x[i] = 0.0; r[i] = ri;
+        rr = ri * ri;
+        if constexpr (!Pre::stored) {
+            const double zi = pre.z(i, ri);
+            d[i] = zi;
+            rz = ri * zi;
+        }
     }
-    const double t0 = block_sum(rr, sh), t1 = block_sum(rz, sh);
-    if (threadIdx.x == 0) { part_a[blockIdx.x] = t0; part_b[blockIdx.x] = t1; }
+    const double t0 = block_sum(rr, sh);
+    if constexpr (!Pre::stored) {
+        const double t1 = block_sum(rz, sh);
+        if (threadIdx.x == 0) part_b[blockIdx.x] = t1;
+    }
+    if (threadIdx.x == 0) part_a[blockIdx.x] = t0;
 }
 
-// x += alpha d, r -= alpha y; partials of r.r and r.M^-1 r   (solver_cg.hpp:103-109, 126-127)
-__global__ __launch_bounds__(RB) void cg_update_kernel(size_t n, const CgScalars *sc, const double *iA, int precond, const double *d,
-                                                       const double *y, double *x, double *r, double *part_a, double *part_b)
+// x += alpha d, r -= alpha y; partials of r.r; Jacobi: and of r.M^-1 r   (solver_cg.hpp:103-109, 126-127)
+template <class Pre>
+__global__ __launch_bounds__(RB) void cg_update_kernel(size_t n, CgStep step, Pre pre, const double *d, const double *y, double *x,
+                                                       double *r, double *part_a, double *part_b)
 {
     __shared__ double sh[RB / 64];
     const size_t i = (size_t)blockIdx.x * RB + threadIdx.x;
-    const double alpha = sc->alpha;
+    const double alpha = step.get();
     double rr = 0.0, rz = 0.0;
     if (i < n) {
         x[i] += alpha * d[i];
         const double ri = r[i] - alpha * y[i];
         r[i] = ri;
-        rr = ri * ri; rz = ri * (precond ? iA[i] * ri : ri);
+        rr = ri * ri;
+        if constexpr (!Pre::stored) rz = ri * pre.z(i, ri);
     }
-    const double t0 = block_sum(rr, sh), t1 = block_sum(rz, sh);
-    if (threadIdx.x == 0) { part_a[blockIdx.x] = t0; part_b[blockIdx.x] = t1; }
+    const double t0 = block_sum(rr, sh);
+    if constexpr (!Pre::stored) {
+        const double t1 = block_sum(rz, sh);
+        if (threadIdx.x == 0) part_b[blockIdx.x] = t1;
+    }
+    if (threadIdx.x == 0) part_a[blockIdx.x] = t0;
 }
 
 // d = M^-1 r + beta d   (solver_cg.hpp:128)
-__global__ __launch_bounds__(RB) void cg_direction_kernel(size_t n, const CgScalars *sc, const double *iA, int precond, const double *r,
-                                                          double *d)
+template <class Pre>
+__global__ __launch_bounds__(RB) void cg_direction_kernel(size_t n, CgStep step, Pre pre, const double *r, double *d)
 {
     const size_t i = (size_t)blockIdx.x * RB + threadIdx.x;
     if (i >= n) return;
-    d[i] = (precond ? iA[i] * r[i] : r[i]) + sc->beta * d[i];
+    if constexpr (Pre::stored) d[i] = pre.first ? pre.z(i, 0.0) : pre.z(i, 0.0) + step.get() * d[i];
+    else d[i] = pre.z(i, r[i]) + step.get() * d[i];
 }
 
 // one block: sums up to two arrays of per-block partials, then the scalar algebra of the step
 //   mode 0 (after init):   rho = sum(b) [r.M^-1 r], nr2 = sum(a)
 //   mode 1 (after spmv):   dy = sum(a); alpha = rho / dy
 //   mode 2 (after update): nr2 = sum(a), rho_new = sum(b); beta = rho_new / rho; rho = rho_new
+//   mode 3 (the sums go over the ranks before anything is formed of them): the two sums of mode 2 -- nr2, rho_new -- and no algebra
+enum { CG_SUMS_ONLY = 3 };
 __global__ __launch_bounds__(RB) void cg_reduce_kernel(int mode, size_t nparts, const double *part_a, const double *part_b, CgScalars *sc)
 {
     __shared__ double sh[RB / 64];
@@ -101,23 +134,69 @@ __global__ __launch_bounds__(RB) void cg_reduce_kernel(int mode, size_t nparts, 
     if (threadIdx.x == 0) {
         if (mode == 0) { sc->nr2 = sa; sc->rho = sb; }
         else if (mode == 1) { sc->dy = sa; sc->alpha = sc->rho / sa; }
-        else { sc->nr2 = sa; sc->rho_new = sb; sc->beta = sb / sc->rho; sc->rho = sb; }
+        else {
+            sc->nr2 = sa; sc->rho_new = sb;
+            if (mode == 2) { sc->beta = sb / sc->rho; sc->rho = sb; }
+        }
     }
 }
 
-hipError_t cg_workspace_reserve(CgWorkspace *ws, size_t rows)
+namespace {
+
+template <class Rows>
+void launch_inv_diag(hipStream_t stream, size_t n, Rows rows, const int64_t *rowptr, const int32_t *colind, const double *values, double *iA)
+{
+    hipLaunchKernelGGL(cg_inv_diag_kernel<Rows>, dim3(cg_vector_grid(n)), dim3(RB), 0, stream, n, rows, rowptr, colind, values, iA);
+}
+
+template <class Rows>
+void launch_spmv(hipStream_t stream, size_t n, Rows rows, const int64_t *rowptr, const int32_t *colind, const double *values, const double *d,
+                 double *y, double *part_dy)
+{
+    hipLaunchKernelGGL(cg_spmv_kernel<Rows>, dim3(cg_row_grid(n)), dim3(RB), 0, stream, n, rows, rowptr, colind, values, d, y, part_dy);
+}
+
+void launch_reduce(hipStream_t stream, int mode, size_t nparts, const double *part_a, const double *part_b, CgScalars *sc)
+{
+    hipLaunchKernelGGL(cg_reduce_kernel, dim3(1), dim3(RB), 0, stream, mode, nparts, part_a, part_b, sc);
+}
+
+// the vector kernels of one solve: its grid, its vectors, and the preconditioned residual they are instantiated for
+struct VectorKernels {
+    hipStream_t stream;
+    size_t n;
+    unsigned gv;
+    double *x, *r, *d, *y, *part_a, *part_b;
+    template <class Pre> void init(const double *b, Pre pre) const
+    {
+        hipLaunchKernelGGL(cg_init_kernel<Pre>, dim3(gv), dim3(RB), 0, stream, n, b, pre, x, r, d, part_a, part_b);
+    }
+    template <class Pre> void update(CgStep alpha, Pre pre) const
+    {
+        hipLaunchKernelGGL(cg_update_kernel<Pre>, dim3(gv), dim3(RB), 0, stream, n, alpha, pre, (const double *)d, (const double *)y, x, r,
+                           part_a, part_b);
+    }
+    template <class Pre> void direction(CgStep beta, Pre pre) const
+    {
+        hipLaunchKernelGGL(cg_direction_kernel<Pre>, dim3(gv), dim3(RB), 0, stream, n, beta, pre, (const double *)r, d);
+    }
+};
+
+}  // namespace
+
+hipError_t cg_workspace_reserve(CgWorkspace *ws, size_t rows, size_t d_len)
 {
     cg_workspace_release(ws);
     const size_t nn = rows ? rows : 1;
-    const size_t gv = (nn + RB - 1) / RB, gs = (nn * ROW_LANES + RB - 1) / RB;
+    const size_t gv = cg_vector_grid(nn), gs = cg_row_grid(nn);
     const size_t nparts = gs > gv ? gs : gv;
     hipError_t e = hipMalloc((void **)&ws->r, nn * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&ws->d, nn * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&ws->d, (d_len > nn ? d_len : nn) * 8);
     if (e == hipSuccess) e = hipMalloc((void **)&ws->y, nn * 8);
     if (e == hipSuccess) e = hipMalloc((void **)&ws->iA, nn * 8);
     if (e == hipSuccess) e = hipMalloc((void **)&ws->part_a, nparts * 8);
     if (e == hipSuccess) e = hipMalloc((void **)&ws->part_b, nparts * 8);
-    if (e == hipSuccess) e = hipMalloc(&ws->scalars, sizeof(CgScalars));
+    if (e == hipSuccess) e = hipMalloc((void **)&ws->scalars, sizeof(CgScalars));
     if (e != hipSuccess) { cg_workspace_release(ws); return e; }
     ws->rows = nn;
     return hipSuccess;
@@ -130,95 +209,93 @@ void cg_workspace_release(CgWorkspace *ws)
     *ws = CgWorkspace();
 }
 
-// exit_reason: 0 converged, 1 diverged, 2 max_iter reached (cg_exit_reason, solver_cg.hpp:38-43)
-hipError_t conjugated_gradient_ops(hipStream_t stream, size_t n, const CgMatrixOps &ops, CgWorkspace *ws, const double *b, double *x,
-                                   double convergence_threshold, double divergence_threshold, size_t max_iter, int precond,
-                                   int *exit_reason, size_t *iterations, double *relative_residual)
+// The one-rank loop on the vectors of ws.  Per iteration: product, reduction 1, update, [pre->apply,] reduction 2, one read of the
+// scalars by the host, the exit tests, direction.  exit_reason: 0 converged, 1 diverged, 2 max_iter reached (cg_exit_reason,
+// solver_cg.hpp:38-43)
+static hipError_t cg_iterate(hipStream_t stream, size_t n, const CgCsr &m, const CgPreconditioner *pre, const CgWorkspace &ws, const double *b,
+                             double *x, double convergence_threshold, double divergence_threshold, size_t max_iter, int precond,
+                             int *exit_reason, size_t *iterations, double *relative_residual)
 {
-    hipError_t e = hipSuccess;
-    const size_t nn = n ? n : 1;
-    const unsigned gv = (unsigned)((nn + RB - 1) / RB);
-    const unsigned gs = (unsigned)((nn * ROW_LANES + RB - 1) / RB);
-    CgWorkspace own;
-    if (ws != nullptr && ws->rows < nn) return hipErrorInvalidValue;
-    auto cleanup = [&]() { cg_workspace_release(&own); };
-    if (ws == nullptr) {
-        e = cg_workspace_reserve(&own, nn);
-        if (e != hipSuccess) return e;
-        ws = &own;
-    }
-#define CG_TRY(call) do { e = (call); if (e != hipSuccess) { cleanup(); return e; } } while (0)
-    double *r = ws->r, *d = ws->d, *y = ws->y, *iA = ws->iA, *pa_ = ws->part_a, *pb_ = ws->part_b;
-    CgScalars *sc = (CgScalars *)ws->scalars;
+    const size_t gv = cg_vector_grid(n), gs = cg_row_grid(n);
+    const VectorKernels k{stream, n, (unsigned)gv, x, ws.r, ws.d, ws.y, ws.part_a, ws.part_b};
+    const CgJacobi jacobi{ws.iA, precond};
+    CgScalars *sc = ws.scalars;
+    const CgStep alpha{&sc->alpha, 0.0}, beta{&sc->beta, 0.0};
     CgScalars h{};
+    auto read_scalars = [&]() -> hipError_t {
+        const hipError_t e = hipMemcpyAsync(&h, sc, sizeof(h), hipMemcpyDeviceToHost, stream);
+        return e != hipSuccess ? e : hipStreamSynchronize(stream);
+    };
+    hipError_t e = hipSuccess;
     size_t iter = 0;
     int reason = 2;
     double rr = 0.0;
     if (n) {
-        ops.inv_diag(ops.user, stream, n, iA);
-        hipLaunchKernelGGL(cg_init_kernel, dim3(gv), dim3(RB), 0, stream, n, b, iA, precond, x, r, d, pa_, pb_);      // :82-84
-        hipLaunchKernelGGL(cg_reduce_kernel, dim3(1), dim3(RB), 0, stream, 0, (size_t)gv, pa_, pb_, sc);
-        CG_TRY(hipMemcpyAsync(&h, sc, sizeof(h), hipMemcpyDeviceToHost, stream));
-        CG_TRY(hipStreamSynchronize(stream));
+        if (pre) {
+            k.init(b, CgStoredZ{pre->z, 0});                                                                               // :73-84
+            pre->apply(pre->user, stream, ws.r, pre->z, ws.part_b);
+            k.direction(beta, CgStoredZ{pre->z, 1});
+        } else {
+            if (m.rowmap) launch_inv_diag(stream, n, CgRowsMapped{m.rowmap}, m.rowptr, m.colind, m.values, ws.iA);
+            else launch_inv_diag(stream, n, CgRowsPlain{}, m.rowptr, m.colind, m.values, ws.iA);
+            k.init(b, jacobi);                                                                                             // :82-84
+        }
+        launch_reduce(stream, 0, gv, ws.part_a, ws.part_b, sc);
+        if ((e = read_scalars()) != hipSuccess) return e;
         const double nr0 = sqrt(h.nr2);
         if (!(nr0 > 0.0)) { reason = 0; }                   // b = 0: x = 0 is the solution (the reference would divide by zero)
         else
             for (;;) {
-                ops.spmv(ops.user, stream, n, d, y, pa_);                                                                     // :99
-                hipLaunchKernelGGL(cg_reduce_kernel, dim3(1), dim3(RB), 0, stream, 1, (size_t)gs, pa_, (const double *)nullptr, sc);   // :101-102
-                hipLaunchKernelGGL(cg_update_kernel, dim3(gv), dim3(RB), 0, stream, n, sc, iA, precond, d, y, x, r, pa_, pb_);       // :103-105
-                hipLaunchKernelGGL(cg_reduce_kernel, dim3(1), dim3(RB), 0, stream, 2, (size_t)gv, pa_, pb_, sc);
-                CG_TRY(hipMemcpyAsync(&h, sc, sizeof(h), hipMemcpyDeviceToHost, stream));
-                CG_TRY(hipStreamSynchronize(stream));
+                if (m.rowmap) launch_spmv(stream, n, CgRowsMapped{m.rowmap}, m.rowptr, m.colind, m.values, ws.d, ws.y, ws.part_a);
+                else launch_spmv(stream, n, CgRowsPlain{}, m.rowptr, m.colind, m.values, ws.d, ws.y, ws.part_a);           // :99
+                launch_reduce(stream, 1, gs, ws.part_a, nullptr, sc);                                                      // :101-102
+                if (pre) {
+                    k.update(alpha, CgStoredZ{pre->z, 0});                                                                 // :103-105
+                    pre->apply(pre->user, stream, ws.r, pre->z, ws.part_b);
+                } else k.update(alpha, jacobi);
+                launch_reduce(stream, 2, gv, ws.part_a, ws.part_b, sc);
+                if ((e = read_scalars()) != hipSuccess) return e;
                 rr = sqrt(h.nr2) / nr0;
                 if (rr < convergence_threshold) { reason = 0; break; }      // :107-110
                 if (iter > max_iter) { reason = 2; break; }                  // :112-115
                 if (rr > divergence_threshold) { reason = 1; break; }        // :117-120
                 if (!(rr == rr)) { reason = 1; break; }                      // NaN: stop instead of spinning
-                hipLaunchKernelGGL(cg_direction_kernel, dim3(gv), dim3(RB), 0, stream, n, sc, iA, precond, r, d);           // :126-128
+                if (pre) k.direction(beta, CgStoredZ{pre->z, 0});                                                          // :126-128
+                else k.direction(beta, jacobi);
                 iter++;
             }
     } else reason = 0;
-    CG_TRY(hipGetLastError());
-#undef CG_TRY
-    cleanup();
+    if ((e = hipGetLastError()) != hipSuccess) return e;
     if (exit_reason) *exit_reason = reason;
     if (iterations) *iterations = iter;
     if (relative_residual) *relative_residual = rr;
     return hipSuccess;
 }
 
-void cg_launch_reduce(hipStream_t stream, int mode, size_t nparts, const double *part_a, const double *part_b, void *scalars)
+hipError_t conjugated_gradient_one_rank(hipStream_t stream, size_t n, const CgCsr &m, const CgPreconditioner *pre, CgWorkspace *ws,
+                                        const double *b, double *x, double convergence_threshold, double divergence_threshold,
+                                        size_t max_iter, int precond, int *exit_reason, size_t *iterations, double *relative_residual)
 {
-    hipLaunchKernelGGL(cg_reduce_kernel, dim3(1), dim3(RB), 0, stream, mode, nparts, part_a, part_b, (CgScalars *)scalars);
+    const size_t nn = n ? n : 1;
+    CgWorkspace own;
+    if (ws != nullptr && ws->rows < nn) return hipErrorInvalidValue;
+    if (ws == nullptr) {
+        const hipError_t e = cg_workspace_reserve(&own, nn, nn);
+        if (e != hipSuccess) return e;
+        ws = &own;
+    }
+    const hipError_t e = cg_iterate(stream, n, m, pre, *ws, b, x, convergence_threshold, divergence_threshold, max_iter, precond, exit_reason,
+                                    iterations, relative_residual);
+    cg_workspace_release(&own);
+    return e;
 }
-
-// the plain CSR matrix pa_csr_from_triplets builds
-namespace {
-using CsrMatrix = CgCsr;
-void csr_inv_diag(void *user, hipStream_t stream, size_t n, double *iA)
-{
-    const CsrMatrix *m = (const CsrMatrix *)user;
-    hipLaunchKernelGGL(cg_inv_diag_kernel, dim3((unsigned)((n + RB - 1) / RB)), dim3(RB), 0, stream, n, m->rowptr, m->colind, m->values, iA);
-}
-void csr_spmv(void *user, hipStream_t stream, size_t n, const double *d, double *y, double *part_dy)
-{
-    const CsrMatrix *m = (const CsrMatrix *)user;
-    hipLaunchKernelGGL(cg_spmv_kernel, dim3((unsigned)((n * ROW_LANES + RB - 1) / RB)), dim3(RB), 0, stream, n, m->rowptr, m->colind,
-                       m->values, d, y, part_dy);
-}
-}  // namespace
-
-CgMatrixOps cg_csr_ops(const CgCsr *m) { return CgMatrixOps{(void *)m, csr_inv_diag, csr_spmv}; }
 
 hipError_t conjugated_gradient(hipStream_t stream, size_t n, const int64_t *rowptr, const int32_t *colind, const double *values,
                                const double *b, double *x, double convergence_threshold, double divergence_threshold,
                                size_t max_iter, int precond, int *exit_reason, size_t *iterations, double *relative_residual)
 {
-    CsrMatrix m{rowptr, colind, values};
-    const CgMatrixOps ops{&m, csr_inv_diag, csr_spmv};
-    return conjugated_gradient_ops(stream, n, ops, nullptr, b, x, convergence_threshold, divergence_threshold, max_iter, precond,
-                                   exit_reason, iterations, relative_residual);
+    return conjugated_gradient_one_rank(stream, n, CgCsr{rowptr, colind, values, nullptr}, nullptr, nullptr, b, x, convergence_threshold,
+                                        divergence_threshold, max_iter, precond, exit_reason, iterations, relative_residual);
 }
 
 // ---- the same solver on a ROW-PARTITIONED system (several GPUs: the face-only condensed system is assembled by rows,
@@ -227,7 +304,9 @@ hipError_t conjugated_gradient(hipStream_t stream, size_t n, const int64_t *rowp
 // -- the columns this rank's rows read; the matrix is symmetric and banded by the mesh's row structure, so they belong to the
 // two neighbouring ranks -- whose two ends are refreshed from the neighbours once per iteration; the dot products are local
 // partial sums added over the ranks.  The transport is three callbacks (RCCL: pa_comm_cg_transport; host-staged gloo in the
-// tests: CgTransport, cg.hpp); without one the call is the one-rank solver above with its recurrences in the same order.
+// tests: CgTransport, cg.hpp).  The kernels are the one-rank loop's with the window view (CgRowsWindow) and the scalars of a
+// step by value; the loop is its own -- two host reads per iteration, because the sums go over the ranks before alpha and beta
+// are formed of them, and a collective exit -- and without a transport it forms what the one-rank loop forms, in the same order.
 
 // smallest and largest column index of the local rows (one block per 256 entries, atomics on two words)
 __global__ __launch_bounds__(RB) void cg_col_range_kernel(size_t nnz, const int32_t *colind, int *minmax)
@@ -236,71 +315,6 @@ __global__ __launch_bounds__(RB) void cg_col_range_kernel(size_t nnz, const int3
     if (k >= nnz) return;
     atomicMin(&minmax[0], colind[k]);
     atomicMax(&minmax[1], colind[k]);
-}
-
-__global__ __launch_bounds__(RB) void cg_inv_diag_rows_kernel(size_t n, int64_t row_begin, const int64_t *rowptr, const int32_t *colind,
-                                                              const double *values, double *iA)
-{
-    const size_t i = (size_t)blockIdx.x * RB + threadIdx.x;
-    if (i >= n) return;
-    double d = 0.0;
-    for (int64_t k = rowptr[i]; k < rowptr[i + 1]; ++k)
-        if ((int64_t)colind[k] == row_begin + (int64_t)i) d = values[k];
-    iA[i] = 1.0 / d;
-}
-
-// y = A_local dwin (columns shifted into the window) and the per-block partial of d_local . y
-__global__ __launch_bounds__(RB) void cg_spmv_rows_kernel(size_t n, int64_t col0, size_t own0, const int64_t *rowptr, const int32_t *colind,
-                                                          const double *values, const double *dwin, double *y, double *part_dy)
-{
-    __shared__ double sh[RB / 64];
-    const size_t row = ((size_t)blockIdx.x * RB + threadIdx.x) / ROW_LANES;
-    const int sub = threadIdx.x % ROW_LANES;
-    double s = 0.0;
-    if (row < n)
-        for (int64_t k = rowptr[row] + sub; k < rowptr[row + 1]; k += ROW_LANES) s += values[k] * dwin[(int64_t)colind[k] - col0];
-#pragma unroll
-    for (int o = ROW_LANES / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, ROW_LANES);
-    double dyp = 0.0;
-    if (row < n && sub == 0) { y[row] = s; dyp = dwin[own0 + row] * s; }
-    const double t = block_sum(dyp, sh);
-    if (threadIdx.x == 0) part_dy[blockIdx.x] = t;
-}
-
-// sums of up to two arrays of per-block partials -> out[0], out[1]
-__global__ __launch_bounds__(RB) void cg_sum_kernel(size_t nparts, const double *part_a, const double *part_b, double *out)
-{
-    __shared__ double sh[RB / 64];
-    double a = 0.0, b = 0.0;
-    for (size_t i = threadIdx.x; i < nparts; i += RB) {
-        a += part_a[i];
-        if (part_b) b += part_b[i];
-    }
-    const double sa = block_sum(a, sh), sb = block_sum(b, sh);
-    if (threadIdx.x == 0) { out[0] = sa; out[1] = sb; }
-}
-
-__global__ __launch_bounds__(RB) void cg_update_rows_kernel(size_t n, double alpha, const double *iA, int precond, const double *d,
-                                                            const double *y, double *x, double *r, double *part_a, double *part_b)
-{
-    __shared__ double sh[RB / 64];
-    const size_t i = (size_t)blockIdx.x * RB + threadIdx.x;
-    double rr = 0.0, rz = 0.0;
-    if (i < n) {
-        x[i] += alpha * d[i];
-        const double ri = r[i] - alpha * y[i];
-        r[i] = ri;
-        rr = ri * ri; rz = ri * (precond ? iA[i] * ri : ri);
-    }
-    const double t0 = block_sum(rr, sh), t1 = block_sum(rz, sh);
-    if (threadIdx.x == 0) { part_a[blockIdx.x] = t0; part_b[blockIdx.x] = t1; }
-}
-
-__global__ __launch_bounds__(RB) void cg_direction_rows_kernel(size_t n, double beta, const double *iA, int precond, const double *r, double *d)
-{
-    const size_t i = (size_t)blockIdx.x * RB + threadIdx.x;
-    if (i >= n) return;
-    d[i] = (precond ? iA[i] * r[i] : r[i]) + beta * d[i];
 }
 
 // status: 0 ok; 1 a transport callback failed on THIS rank; 2 this rank's rows read a column no neighbour range covers (or, without a
@@ -315,23 +329,18 @@ hipError_t conjugated_gradient_rows(hipStream_t stream, const CgTransport *tp, i
                                     int *exit_reason, size_t *iterations, double *relative_residual, int *transport_status)
 {
     const size_t n = (size_t)(row_end - row_begin);
-    double *r = nullptr, *dwin = nullptr, *y = nullptr, *iA = nullptr, *pa_ = nullptr, *pb_ = nullptr, *sums = nullptr;
-    int *mm = nullptr;
     const size_t nn = n ? n : 1;
-    const unsigned gv = (unsigned)((nn + RB - 1) / RB);
-    const unsigned gs = (unsigned)((nn * ROW_LANES + RB - 1) / RB);
-    const size_t nparts = gs > gv ? gs : gv;
-    auto cleanup = [&]() {
-        (void)hipFree(r); (void)hipFree(dwin); (void)hipFree(y); (void)hipFree(iA); (void)hipFree(pa_); (void)hipFree(pb_);
-        (void)hipFree(sums); (void)hipFree(mm);
-    };
+    const size_t gv = cg_vector_grid(nn), gs = cg_row_grid(nn);
+    CgWorkspace ws;
+    DeviceTmp tmp(stream);
+    int *mm = nullptr;
     if (transport_status) *transport_status = 0;
     int fail = 0;                          // this rank's status (see above); 0 while everything went well
     hipError_t herr = hipSuccess;
     auto hip_ok = [&](hipError_t e) -> bool { if (e != hipSuccess && !fail) { fail = 4; herr = e; } return e == hipSuccess; };
     auto leave = [&](int status) -> hipError_t {
         if (transport_status) *transport_status = status;
-        cleanup();
+        cg_workspace_release(&ws);
         return status == 4 ? herr : hipSuccess;
     };
     // all ranks agree on whether anybody failed: the flag summed over the ranks (one rank: the flag itself)
@@ -351,7 +360,7 @@ hipError_t conjugated_gradient_rows(hipStream_t stream, const CgTransport *tp, i
                 nnz = ends[1] - ends[0];
         }
         int h[2] = {0x7fffffff, -1};
-        if (!fail && hip_ok(hipMalloc((void **)&mm, 8)) && hip_ok(hipMemcpyAsync(mm, h, 8, hipMemcpyHostToDevice, stream))) {
+        if (!fail && (tmp.alloc(&mm, 2) || hip_ok(tmp.error())) && hip_ok(hipMemcpyAsync(mm, h, 8, hipMemcpyHostToDevice, stream))) {
             if (nnz > 0) hipLaunchKernelGGL(cg_col_range_kernel, dim3((unsigned)((nnz + RB - 1) / RB)), dim3(RB), 0, stream, (size_t)nnz, colind, mm);
             if (hip_ok(hipMemcpyAsync(h, mm, 8, hipMemcpyDeviceToHost, stream)) && hip_ok(hipStreamSynchronize(stream)) && nnz > 0) {
                 need_lo = h[0] < row_begin ? row_begin - h[0] : 0;
@@ -366,23 +375,22 @@ hipError_t conjugated_gradient_rows(hipStream_t stream, const CgTransport *tp, i
     } else if (need_lo || need_hi) fail = 2;
     if (!fail && (give_lo > (int64_t)n || give_hi > (int64_t)n)) fail = 2;
     const size_t nwin = n + (size_t)need_lo + (size_t)need_hi;
-    if (!fail) {
-        (void)(hip_ok(hipMalloc((void **)&r, nn * 8)) && hip_ok(hipMalloc((void **)&dwin, (nwin ? nwin : 1) * 8)) && hip_ok(hipMalloc((void **)&y, nn * 8)) &&
-               hip_ok(hipMalloc((void **)&iA, nn * 8)) && hip_ok(hipMalloc((void **)&pa_, nparts * 8)) && hip_ok(hipMalloc((void **)&pb_, nparts * 8)) &&
-               hip_ok(hipMalloc((void **)&sums, 16)) && hip_ok(hipMemsetAsync(dwin, 0, (nwin ? nwin : 1) * 8, stream)));
-    }
+    if (!fail) (void)(hip_ok(cg_workspace_reserve(&ws, nn, nwin)) && hip_ok(hipMemsetAsync(ws.d, 0, (nwin ? nwin : 1) * 8, stream)));
     {
         const int st = agree();            // nobody starts iterating unless everybody can
         if (st) return leave(st);
     }
-    double *d = dwin + need_lo;            // the owned part of the window
+    double *dwin = ws.d, *d = dwin + need_lo;            // the window, and its owned part
+    const VectorKernels k{stream, n, (unsigned)gv, x, ws.r, d, ws.y, ws.part_a, ws.part_b};
+    const CgJacobi jacobi{ws.iA, precond};
+    const CgRowsWindow rows{row_begin, row_begin - need_lo, (size_t)need_lo};
     double hs[3];
     // local sums -> host -> ranks, the failure flag behind them.  Returns 0, or the status all ranks leave with.
-    auto reduce2 = [&](size_t np, const double *pa2, const double *pb2, int nvals) -> int {
+    auto reduce2 = [&](size_t np, const double *pb2, int nvals) -> int {
         hs[0] = hs[1] = 0.0;
         if (!fail) {
-            hipLaunchKernelGGL(cg_sum_kernel, dim3(1), dim3(RB), 0, stream, np, pa2, pb2, sums);
-            (void)(hip_ok(hipMemcpyAsync(hs, sums, 16, hipMemcpyDeviceToHost, stream)) && hip_ok(hipStreamSynchronize(stream)));
+            launch_reduce(stream, CG_SUMS_ONLY, np, ws.part_a, pb2, ws.scalars);
+            (void)(hip_ok(hipMemcpyAsync(hs, &ws.scalars->nr2, 16, hipMemcpyDeviceToHost, stream)) && hip_ok(hipStreamSynchronize(stream)));
         }
         hs[nvals] = fail ? 1.0 : 0.0;
         if (tp && tp->allreduce_sum(tp->user, hs, nvals + 1) != 0) return fail ? fail : 1;
@@ -398,10 +406,9 @@ hipError_t conjugated_gradient_rows(hipStream_t stream, const CgTransport *tp, i
     int reason = 2;
     double rr = 0.0;
     {
-        if (n) hipLaunchKernelGGL(cg_inv_diag_rows_kernel, dim3(gv), dim3(RB), 0, stream, n, row_begin, rowptr, colind, values, iA);
-        // r = b, d = M^-1 r (x = 0), partials of r.r and r.M^-1 r       solver_cg.hpp:73-84
-        hipLaunchKernelGGL(cg_init_kernel, dim3(gv), dim3(RB), 0, stream, n, b, iA, precond, x, r, d, pa_, pb_);
-        int st = reduce2(gv, pa_, pb_, 2);
+        if (n) launch_inv_diag(stream, n, rows, rowptr, colind, values, ws.iA);
+        k.init(b, jacobi);                 // r = b, d = M^-1 r (x = 0), partials of r.r and r.M^-1 r       solver_cg.hpp:73-84
+        int st = reduce2(gv, ws.part_b, 2);
         if (st) return leave(st);
         const double nr0 = sqrt(hs[0]);
         double rho = hs[1];
@@ -409,14 +416,12 @@ hipError_t conjugated_gradient_rows(hipStream_t stream, const CgTransport *tp, i
         else
             for (;;) {
                 refresh();
-                if (!fail)
-                    hipLaunchKernelGGL(cg_spmv_rows_kernel, dim3(gs), dim3(RB), 0, stream, n, row_begin - need_lo, (size_t)need_lo, rowptr, colind,
-                                       values, dwin, y, pa_);                                                        // :99
-                st = reduce2(gs, pa_, (const double *)nullptr, 1);
+                if (!fail) launch_spmv(stream, n, rows, rowptr, colind, values, dwin, ws.y, ws.part_a);              // :99
+                st = reduce2(gs, nullptr, 1);
                 if (st) return leave(st);
                 const double alpha = rho / hs[0];                                                                    // :101-102
-                hipLaunchKernelGGL(cg_update_rows_kernel, dim3(gv), dim3(RB), 0, stream, n, alpha, iA, precond, d, y, x, r, pa_, pb_);   // :103-105
-                st = reduce2(gv, pa_, pb_, 2);
+                k.update(CgStep{nullptr, alpha}, jacobi);                                                            // :103-105
+                st = reduce2(gv, ws.part_b, 2);
                 if (st) return leave(st);
                 rr = sqrt(hs[0]) / nr0;
                 if (rr < convergence_threshold) { reason = 0; break; }      // :107-110
@@ -425,7 +430,7 @@ hipError_t conjugated_gradient_rows(hipStream_t stream, const CgTransport *tp, i
                 if (!(rr == rr)) { reason = 1; break; }
                 const double beta = hs[1] / rho;
                 rho = hs[1];
-                hipLaunchKernelGGL(cg_direction_rows_kernel, dim3(gv), dim3(RB), 0, stream, n, beta, iA, precond, r, d);   // :126-128
+                k.direction(CgStep{nullptr, beta}, jacobi);                                                          // :126-128
                 iter++;
             }
     }
@@ -434,11 +439,10 @@ hipError_t conjugated_gradient_rows(hipStream_t stream, const CgTransport *tp, i
         const int st = agree();            // a rank whose last launches failed says so before anybody reports success
         if (st) return leave(st);
     }
-    cleanup();
     if (exit_reason) *exit_reason = reason;
     if (iterations) *iterations = iter;
     if (relative_residual) *relative_residual = rr;
-    return hipSuccess;
+    return leave(0);
 }
 
 }  // namespace pa

@@ -135,8 +135,8 @@ def test_contract_of_the_entry_point(asm):
 @pytest.mark.parametrize("case", [T.Case(n, precond, arrow) for n in (257, 4097, 65537) for arrow in (False, True) for precond in (True, False)],
                          ids=T.case_id)
 def test_rows_solver_of_one_rank(asm, case):
-    """pa_conjugated_gradient_rows without a transport (its own cg_*_rows_kernels and cg_sum_kernel): every iterate at the twin's gate,
-    and the bits of pa_conjugated_gradient -- at 257 rows, at 4097 (second trip over the SpMV partials) and 65537 (over the vector's)"""
+    """pa_conjugated_gradient_rows without a transport (the kernels with the window view CgRowsWindow and by-value scalars,
+    cg_reduce_kernel in mode 3): every iterate at the twin's gate, and the bits of pa_conjugated_gradient -- at 257 rows, at 4097 (second trip over the SpMV partials) and 65537 (over the vector's)"""
     sy = T.system(case)
     dv = _upload(asm, sy)
     for m in range(1, len(T.truth(case).rr) + 1):
@@ -152,7 +152,7 @@ def test_rows_solver_of_one_rank(asm, case):
 def test_rows_solver_of_three_ranks(precond):
     """4500 rows of the band over three thread-ranks (three contexts), parts (0, 17, 300, 4500): the first rank is exactly as tall as
     the band, so all of it travels to its neighbour and its whole window beyond arrives from there; the last rank's 4200 rows make
-    263 SpMV partials, a second trip of cg_sum_kernel.  The sums are grouped by rank, so these are not the one-rank bits: the judge
+    263 SpMV partials, a second trip of cg_reduce_kernel.  The sums are grouped by rank, so these are not the one-rank bits: the judge
     is the twin (truth in longdouble), every iterate at its gate, every exit as truth's history gives it, on every rank."""
     import torch
     if not torch.cuda.is_available():
