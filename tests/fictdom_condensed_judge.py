@@ -12,7 +12,7 @@ elimination."""
 import numpy as np
 
 DPS = 50
-RECORD_GATE = 1e-13          # of the record's largest entry: the gate test_cut_records_against_mpmath holds ifcond_cut_kernel to
+RECORD_GATE = 1e-13          # of the record's largest entry: the gate test_cut_records_against_mpmath holds ifd_records_kernel to
 RECOVER_GATE = 1e-13         # of the cell's largest |u_T|
 
 

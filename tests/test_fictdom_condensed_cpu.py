@@ -39,14 +39,30 @@ def test_header_binding_and_library_agree_on_the_new_exports(name):
 
 
 def test_kernel_file_is_built_and_holds_the_two_kernels():
+    """the unit is built, and the cut cells' elimination and recovery are stated once: in the header both units include"""
     from proton_amd import _build
-    src = open(os.path.join(ROOT, "proton_amd", "csrc", "fictdom_condensed.hip")).read()
-    assert "fdcond_cut_kernel" in src and "fdcond_recover_kernel" in src and '#include "ifd_dense.hpp"' in src
+    csrc = os.path.join(ROOT, "proton_amd", "csrc")
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc))}
     assert '"fictdom_condensed"' in open(_build.__file__).read()
-    # the dense text is shared, not copied: one definition, in the header both files include
-    for f in ("fictdom_condensed.hip", "interface_condensed.hip"):
-        s = open(os.path.join(ROOT, "proton_amd", "csrc", f)).read()
+    units = ("fictdom_condensed.hip", "interface_condensed.hip")
+    # each problem keeps a recovery kernel of its own for its addressing
+    assert "void fdcond_recover_kernel(" in text["fictdom_condensed.hip"] and "void ifcond_recover_kernel(" in text["interface_condensed.hip"]
+    for f in units:
+        s = text[f]
         assert "int ifd_cholesky(" not in s and "struct IfdAr<true>" not in s and '#include "ifd_dense.hpp"' in s
+        # each unit launches the shared records kernel and calls the shared recovery; it defines neither
+        assert "ifd_records_kernel<" in s and "ifd_recover_cell<" in s
+        assert "void ifd_records_kernel(" not in s and "*ifd_recover_cell(" not in s
+    # the factorization, the forward substitution over the NC columns, the Schur / g product loop and the two triangular sweeps:
+    # one distinctive token of each, once under csrc/, and that in the header
+    for token in ("int ifd_cholesky(", "void ifd_records_kernel(", "*ifd_recover_cell(",
+                  "for (int c = lane; c < NC; c += 64)",
+                  "Ar::mul(W[i * N + k], W[j * N + k])", "Ar::mul(W[i * N + k], W[NF * N + k])",
+                  "Ar::mul(A[lane * N + j], b[j])", "Ar::mul(A[j * N + lane], b[j])"):
+        assert [f for f in text if token in text[f]] == ["ifd_dense.hpp"] and text["ifd_dense.hpp"].count(token) == 1, token
+    # no more than six kernels in the two units and their header: records, recovery of either problem, info remap, masked
+    # right-hand side, copy
+    assert sum(len(re.findall(r"__global__", text[f])) for f in units + ("ifd_dense.hpp",)) <= 6
 
 
 def cut_matrices(oracle, N, k):

@@ -49,18 +49,23 @@ def sizes(k):
     return cbs, fbs, nf, nf * (nf + 1) // 2
 
 
-def synthetic_cut(asm, k, seed):
-    """D (B B^T + I) D with D a geometric scale over three decades, mirrored from its lower triangle -> (lc [ncut, M, M], rhs)"""
-    import torch
-    cbs, fbs, nf, ntri = sizes(k)
-    M = cbs + nf
-    rng = np.random.default_rng(seed)
-    lcs = np.zeros((asm.ncut, M, M))
-    for c in range(asm.ncut):
+def synthetic_spd(rng, n, M):
+    """n matrices D (B B^T + I) D with D a geometric scale over three decades, mirrored from the lower triangle -> [n, M, M]"""
+    lcs = np.zeros((n, M, M))
+    for c in range(n):
         B = rng.standard_normal((M, M))
         d = 10.0 ** (-3.0 * rng.permutation(M) / (M - 1))
         X = np.tril(d[:, None] * (B @ B.T + np.eye(M)) * d[None, :])
         lcs[c] = X + np.tril(X, -1).T
+    return lcs
+
+
+def synthetic_cut(asm, k, seed):
+    """synthetic_spd in the cut cells' shape and a random right-hand side -> (lc [ncut, M, M], rhs)"""
+    import torch
+    cbs, fbs, nf, ntri = sizes(k)
+    rng = np.random.default_rng(seed)
+    lcs = synthetic_spd(rng, asm.ncut, cbs + nf)
     rhs = rng.standard_normal((asm.ncut, cbs))
     return torch.from_numpy(lcs).to(asm.device), torch.from_numpy(rhs).to(asm.device)
 
