@@ -773,6 +773,25 @@ int pa_interface_condensed_csr_fill(pa_context *ctx, int face_deg, const double 
                                     double *d_values, double *d_rhs);
 int pa_interface_condensed_recover(pa_context *ctx, int face_deg, const double *d_lc, const double *d_rhs, const double *d_lc_cut,
                                    const double *d_rhs_cut, const double *d_g, const double *d_xF, double *d_full);
+/* The patch tables of that face-only system for pa_patch_precond_* / pa_conjugated_gradient_patch (solver_cg.hpp:63-144 with
+ * patches where the reference has 1 / diag(A); the solve they serve is cuthho_square.cpp:1737-1743), in interface_assembler's
+ * numbering, in which a cut face owns two blocks: rows are rows of pa_interface_condensed_csr_pattern, `kind` is that of
+ * pa_condensed_patches, the table format that of pa_patch_precond_*.
+ *   PA_PATCH_FACE: one patch per non-Dirichlet face by ascending face id: all rows of its blocks, fbs for an uncut face, 2 fbs
+ *     for a cut face (negative block, then positive block); at most 8 rows.  The patches partition the rows in order.  (A cut
+ *     face on the Dirichlet boundary -- a level set that leaves the domain, which interface_assembler refuses -- is counted by
+ *     pa_cut_preprocess's numbering and owns nothing: its empty row group lies in no patch of either kind.)
+ *   PA_PATCH_CELL: by ascending cell id.  An uncut cell with a non-Dirichlet face gives one patch: the blocks of its
+ *     non-Dirichlet faces in the cell's face order bottom, right, top, left.  A cut cell gives up to two, negative side first:
+ *     the patch of a side holds, in that order, of a cut face the side's block, of an uncut face its one block only if the face
+ *     lies on that side.  Dirichlet faces are skipped, a side without rows gives no patch; at most 4 fbs <= PA_PATCH_MAX_ROWS
+ *     rows.  Every block of an interior face lies in exactly two cell patches.
+ * The query gives the sizes of d_patch_ptr (*npatches + 1) and d_patch_rows (*entries).  Refused, before anything is written:
+ * what pa_interface_csr_* refuses, in its order (face_deg 0..3, whole-mesh cut contexts, system_size < 2^31); an unknown kind or
+ * a NULL output (PA_ERR_INVALID_ARG); a table of 2^31 entries or more.  Pending side-stream work (pa_context_set_cut_overlap)
+ * is joined first.  Both wait for the stream. */
+int pa_interface_condensed_patches_query(pa_context *ctx, int face_deg, int kind, size_t *npatches, size_t *entries);
+int pa_interface_condensed_patches(pa_context *ctx, int face_deg, int kind, int64_t *d_patch_ptr, int32_t *d_patch_rows);
 
 /* The face-only system of interface_assembler assembled and solved BY ROW SLABS (cuthho_square.cpp:1142-1178 the numbering,
  * :1203-1354 the assembly, :1664-1743 the loop and the solve; the reference has one process).  The context is one of

@@ -738,6 +738,33 @@ class BatchAssembler:
                                              _ptr(ops.get("rhs_cut")), _ptr(g), xF.data_ptr(), full.data_ptr())
         return full[:info.system_size]
 
+    def interface_condensed_patches(self, fd, kind):
+        """the patch table of the face-only system of interface_condensed_csr_pattern: kind "face" (one patch per non-Dirichlet
+        face: all rows of its one or two blocks) or "cell" (one per uncut cell and per side of a cut cell)
+        -> (patch_ptr int64 [npatches + 1], patch_rows int32)"""
+        kind = {"face": capi.PATCH_FACE, "cell": capi.PATCH_CELL}.get(kind, kind)
+        npatches, entries = self.ctx.interface_condensed_patches_query(fd, kind)
+        ptr = torch.empty(npatches + 1, dtype=torch.int64, device=self.device)
+        rows = torch.empty(max(entries, 1), dtype=torch.int32, device=self.device)
+        self.ctx.interface_condensed_patches(fd, kind, ptr.data_ptr(), rows.data_ptr())
+        return ptr, rows[:entries]
+
+    def interface_condensed_solve(self, fd, ops, g=None, tol=1e-9, div=100.0, max_iter=None, precond=True, patches=None):
+        """cuthho_square.cpp:1664-1743 on the face-only system from interface_local_ops' dict: the records, the pattern, the fill,
+        conjugated_gradient (precond: Jacobi) or, patches "face" / "cell", conjugated_gradient_patch on that table of
+        interface_condensed_patches, and the recovery -> (full solution vector, iterations, exit reason)"""
+        rec = self.interface_condensed_ops(fd, ops)
+        rowptr, colind = self.interface_condensed_csr_pattern(fd)
+        values, b = self.interface_condensed_csr_fill(fd, rec, g)
+        if max_iter is None:
+            max_iter = 20 * b.numel()
+        if patches is None:
+            xF, reason, iters, _ = self.conjugated_gradient(rowptr, colind, values, b, tol=tol, div=div, max_iter=max_iter, precond=precond)
+        else:
+            xF, reason, iters, _ = self.conjugated_gradient_patch(rowptr, colind, values, b, self.interface_condensed_patches(fd, patches),
+                                                                  tol=tol, div=div, max_iter=max_iter)
+        return self.interface_condensed_recover(fd, ops, xF, g), iters, reason
+
     # ---- the same by row slabs: a context of cut_preprocess(rows=...), or the whole mesh as one slab ----
     def interface_rows_info(self, fd):
         """pa_interface_rows_query: the slab's owned rows, column window, cell blocks and halo sizes"""

@@ -50,6 +50,7 @@ EXPORTS = [
     "pa_fictdom_condensed_ops_batch", "pa_fictdom_condensed_recover",
     "pa_patch_precond_query", "pa_patch_precond_factor", "pa_patch_precond_apply", "pa_conjugated_gradient_patch",
     "pa_condensed_patches_query", "pa_condensed_patches",
+    "pa_interface_condensed_patches_query", "pa_interface_condensed_patches",
 ]
 
 
@@ -267,6 +268,8 @@ def lib():
     L.pa_interface_condensed_csr_pattern.argtypes = [vp, C.c_int, dp, dp]
     L.pa_interface_condensed_csr_fill.argtypes = [vp, C.c_int] + [dp] * 5
     L.pa_interface_condensed_recover.argtypes = [vp, C.c_int] + [dp] * 7
+    L.pa_interface_condensed_patches_query.argtypes = [vp, C.c_int, C.c_int, C.POINTER(sz), C.POINTER(sz)]
+    L.pa_interface_condensed_patches.argtypes = [vp, C.c_int, C.c_int, dp, dp]
     L.pa_interface_rows_partition_info.argtypes = [sz, sz, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(LevelSet), C.c_int, sz, sz,
                                                    C.c_int, C.POINTER(InterfaceRowsInfo)]
     L.pa_interface_rows_query.argtypes = [vp, C.c_int, C.POINTER(InterfaceRowsInfo)]
@@ -687,6 +690,15 @@ class Context:
     def interface_condensed_recover(self, face_deg, lc, rhs, lc_cut, rhs_cut, g, xF, full):
         self._ck(self._L.pa_interface_condensed_recover(self.h, face_deg, lc, rhs, lc_cut, rhs_cut, g, xF, full),
                  "pa_interface_condensed_recover")
+
+    def interface_condensed_patches_query(self, face_deg, kind):
+        npatches, entries = C.c_size_t(0), C.c_size_t(0)
+        self._ck(self._L.pa_interface_condensed_patches_query(self.h, face_deg, kind, C.byref(npatches), C.byref(entries)),
+                 "pa_interface_condensed_patches_query")
+        return npatches.value, entries.value
+
+    def interface_condensed_patches(self, face_deg, kind, patch_ptr, patch_rows):
+        self._ck(self._L.pa_interface_condensed_patches(self.h, face_deg, kind, patch_ptr, patch_rows), "pa_interface_condensed_patches")
 
     def interface_rows_query(self, face_deg):
         out = InterfaceRowsInfo()

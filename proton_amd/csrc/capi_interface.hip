@@ -338,6 +338,40 @@ int pa_interface_condensed_recover(pa_context *ctx, int face_deg, const double *
     return PA_OK;
 }
 
+// the patch tables of the face-only system: the refusals of pa_interface_csr_* in its order, then the kind and the outputs (with
+// `write`), then the side stream joined; counted on the device, written only if the entries fit int32
+static int if_patches(pa_context *ctx, int face_deg, int kind, bool write, size_t *npatches, size_t *entries, int64_t *d_patch_ptr,
+                      int32_t *d_patch_rows)
+{
+    const int st = if_refusals(ctx, face_deg, true);
+    if (st != PA_OK) return st;
+    if (kind != PA_PATCH_FACE && kind != PA_PATCH_CELL) return PA_ERR_INVALID_ARG;
+    if (write ? (!d_patch_ptr || (ctx->cut.if_num_other_faces && !d_patch_rows)) : (!npatches || !entries)) return PA_ERR_INVALID_ARG;
+    PA_HIP(ctx, join_side_stream(ctx));      // cut-cell work still out on the side stream
+    uint64_t np = 0, ne = 0;
+    PA_HIP(ctx, pa::ifcond_patches(ctx->stream, ifcsr_mesh(ctx), face_deg, kind == PA_PATCH_FACE ? pa::IF_PATCH_FACE : pa::IF_PATCH_CELL, &np,
+                                   &ne, write ? d_patch_ptr : nullptr, d_patch_rows));
+    if (ne >= ((uint64_t)1 << 31)) {                      // int32 slots of pa_patch_precond_*
+        ctx->last_error = "pa_interface_condensed_patches: the table has 2^31 entries or more";
+        return PA_ERR_INVALID_ARG;
+    }
+    if (npatches) *npatches = (size_t)np;
+    if (entries) *entries = (size_t)ne;
+    return PA_OK;
+}
+
+int pa_interface_condensed_patches_query(pa_context *ctx, int face_deg, int kind, size_t *npatches, size_t *entries)
+{
+    if (!ctx) return PA_ERR_INVALID_ARG;
+    return if_patches(ctx, face_deg, kind, false, npatches, entries, nullptr, nullptr);
+}
+
+int pa_interface_condensed_patches(pa_context *ctx, int face_deg, int kind, int64_t *d_patch_ptr, int32_t *d_patch_rows)
+{
+    if (!ctx) return PA_ERR_INVALID_ARG;
+    return if_patches(ctx, face_deg, kind, true, nullptr, nullptr, d_patch_ptr, d_patch_rows);
+}
+
 // ---- the face-only system by row slabs (pa_interface_rows_*): a context of pa_cut_preprocess_rows, or of pa_cut_preprocess as
 // the one-slab case.  The numbering of the slab comes from the whole-mesh tags every rank holds (interface_rows.hpp). ----
 static void ifrows_info_fill(const pa::IfRowsHost &h, int face_deg, uint64_t nnz, pa_interface_rows_info *out)

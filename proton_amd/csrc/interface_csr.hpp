@@ -158,4 +158,15 @@ hipError_t ifcond_info_remap(hipStream_t stream, size_t n, int32_t *info);
 hipError_t ifcond_recover(hipStream_t stream, const IfCsrMesh &m, int face_deg, int max_blocks, const IfCondArgs &a, const double *lc,
                           const double *rhs, const double *lc_cut, const double *rhs_cut, const double *xF, double *full);
 
+// ---- the patch tables of the face-only system for pa_patch_precond_* (patch_precond.hip) ----------------------------------
+// Rows are values of if_face_index.  IF_PATCH_FACE: one patch per non-Dirichlet face, all rows of its blocks (a cut face: the
+// negative block, then the positive).  IF_PATCH_CELL: one patch per uncut cell, and per side of a cut cell (negative first): the
+// blocks if_face_index gives that side's local slots, in the face order bottom, right, top, left -- an uncut face of a cut cell
+// only on the side it lies on.  Dirichlet faces are skipped; a cell or side without rows gives no patch.
+constexpr int IF_PATCH_FACE = 0, IF_PATCH_CELL = 1;     // PA_PATCH_FACE, PA_PATCH_CELL
+// counts the table (*npatches, *entries) and, with ptr given and *entries < 2^31, writes it (ptr *npatches + 1, rows *entries);
+// waits for the stream
+hipError_t ifcond_patches(hipStream_t stream, const IfCsrMesh &m, int face_deg, int kind, uint64_t *npatches, uint64_t *entries,
+                          int64_t *ptr, int32_t *rows);
+
 }  // namespace pa

@@ -1,6 +1,7 @@
 // patch_precond.hip -- an additive Schwarz preconditioner over patches of rows for the device conjugate gradient
 // (solver_cg.hpp:63-144 with  z = sum_p R_p^T (R_p A R_p^T)^-1 R_p r  where the reference multiplies by 1 / diag(A); the solve of
-// cuthho_square.cpp:915-919 on the face-only system), and the patch tables of that system: one patch per face, or per cell.
+// cuthho_square.cpp:915-919 on the face-only system), and the patch tables of that system: one patch per face, or per cell; for the
+// interface problem's system (the solve of cuthho_square.cpp:1737-1743) one per face with all its blocks, or per cell side.
 //
 // A patch holds 1..16 rows.  P = 4, 8 or 16 consecutive lanes share a patch (the smallest P that holds the table's largest patch),
 // lane l owning row l: a 16-row patch fills a quarter of a wavefront, four patches a wavefront, and everything the lanes of a patch
@@ -21,6 +22,7 @@
 
 #include "cg.hpp"
 #include "device_tmp.hpp"
+#include "interface_csr.hpp"
 #include "patch_precond.hpp"
 #include "scan.hpp"
 
@@ -446,6 +448,91 @@ void cell_patches(hipStream_t stream, uint32_t ncells, uint32_t npatches, const 
 {
     hipLaunchKernelGGL(cell_patches_kernel, dim3((ncells + RB) / RB), dim3(RB), 0, stream, ncells, npatches, cell_faces, face_compress, cprefix,
                        index, fbs, ptr, rows);
+}
+
+// ---- the patch tables of the interface problem's face-only system (pa_interface_condensed_patches: interface_assembler's numbering, in
+// which a cut face owns two blocks; the tables of IfCsrMesh alone, counted and placed by the scans of scan.hpp) --------------------------
+// An item is what may give a patch: a face (IF_PATCH_FACE), or side s of cell X as item 2 X + s (IF_PATCH_CELL; an uncut cell is
+// its item 2 X alone).  -> the item's face blocks in the patch's order (none: no patch)
+__device__ __forceinline__ int ifp_blocks(const IfCsrMesh &m, int kind, size_t item, int32_t *blk)
+{
+    int n = 0;
+    if (kind == IF_PATCH_FACE) {
+        const int32_t b = m.face_table[item];
+        if (b < 0) return 0;
+        blk[n++] = b;
+        if (m.face_loc[item] == IF_LOC_CUT) blk[n++] = b + 1;
+        return n;
+    }
+    const size_t X = item >> 1;
+    const int s = (int)(item & 1);
+    const bool cut = m.cell_loc[X] == IF_LOC_CUT;
+    if (!cut && s == 1) return 0;
+    for (int lf = 0; lf < 4; ++lf) {                     // bottom, right, top, left
+        const uint32_t f = m.cell_faces[4 * X + lf];
+        const int32_t b = m.face_table[f];
+        if (b < 0) continue;
+        const int8_t fl = m.face_loc[f];
+        if (cut && fl != IF_LOC_CUT && fl != s) continue;                                   // an uncut face: on its own side only
+        blk[n++] = b + ((cut && s == 1 && fl == IF_LOC_CUT) ? 1 : 0);                       // dup of if_global_index
+    }
+    return n;
+}
+
+// per block of items: its patches (bp) and its face blocks (bb)
+__global__ __launch_bounds__(SCAN_BLOCK) void ifp_count_kernel(IfCsrMesh m, int kind, size_t nitems, uint32_t *bp, uint32_t *bb)
+{
+    __shared__ uint32_t sh[SCAN_BLOCK / 64];
+    const size_t item = (size_t)blockIdx.x * SCAN_BLOCK + threadIdx.x;
+    int32_t blk[4];
+    const uint32_t nb = item < nitems ? (uint32_t)ifp_blocks(m, kind, item, blk) : 0u;
+    uint32_t tp, tb;
+    block_exclusive_scan(nb ? 1u : 0u, sh, tp);
+    block_exclusive_scan(nb, sh, tb);
+    if (threadIdx.x == 0) { bp[blockIdx.x] = tp; bb[blockIdx.x] = tb; }
+}
+
+// bp, bb scanned (their totals at [nblk]): every item with blocks writes its patch
+__global__ __launch_bounds__(SCAN_BLOCK) void ifp_fill_kernel(IfCsrMesh m, int kind, size_t nitems, int fbs, const uint32_t *bp,
+                                                              const uint32_t *bb, uint32_t nblk, int64_t *ptr, int32_t *rows)
+{
+    __shared__ uint32_t sh[SCAN_BLOCK / 64];
+    const size_t item = (size_t)blockIdx.x * SCAN_BLOCK + threadIdx.x;
+    int32_t blk[4];
+    const uint32_t nb = item < nitems ? (uint32_t)ifp_blocks(m, kind, item, blk) : 0u;
+    uint32_t tp, tb;
+    const uint32_t p = bp[blockIdx.x] + block_exclusive_scan(nb ? 1u : 0u, sh, tp);
+    const uint32_t b0 = bb[blockIdx.x] + block_exclusive_scan(nb, sh, tb);
+    if (item == 0) ptr[bp[nblk]] = (int64_t)bb[nblk] * fbs;
+    if (nb == 0) return;
+    int64_t at = (int64_t)b0 * fbs;
+    ptr[p] = at;
+    for (uint32_t i = 0; i < nb; ++i)
+        for (int k = 0; k < fbs; ++k) rows[at++] = blk[i] * fbs + k;
+}
+
+hipError_t ifcond_patches(hipStream_t stream, const IfCsrMesh &m, int face_deg, int kind, uint64_t *npatches, uint64_t *entries,
+                          int64_t *ptr, int32_t *rows)
+{
+    const int fbs = if_dims(face_deg).fbs;
+    const size_t nitems = kind == IF_PATCH_FACE ? (size_t)m.nfaces : 2 * (size_t)m.ncells;
+    const uint32_t nblk = (uint32_t)(nitems ? (nitems + SCAN_BLOCK - 1) / SCAN_BLOCK : 1);
+    DeviceTmp tmp(stream);
+    uint32_t *bp = nullptr, *bb = nullptr;
+    if (!tmp.alloc(&bp, (size_t)nblk + 1) || !tmp.alloc(&bb, (size_t)nblk + 1)) return tmp.error();
+    hipLaunchKernelGGL(ifp_count_kernel, dim3(nblk), dim3(SCAN_BLOCK), 0, stream, m, kind, nitems, bp, bb);
+    hipLaunchKernelGGL(active_block_scan_kernel, dim3(1), dim3(SCAN_BLOCK), 0, stream, bp, nblk);
+    hipLaunchKernelGGL(active_block_scan_kernel, dim3(1), dim3(SCAN_BLOCK), 0, stream, bb, nblk);
+    uint32_t tot[2] = {0, 0};
+    if (!tmp.ok(hipGetLastError()) || !tmp.ok(hipMemcpyAsync(&tot[0], bp + nblk, sizeof(uint32_t), hipMemcpyDeviceToHost, stream)) ||
+        !tmp.ok(hipMemcpyAsync(&tot[1], bb + nblk, sizeof(uint32_t), hipMemcpyDeviceToHost, stream)) || !tmp.ok(hipStreamSynchronize(stream)))
+        return tmp.error();
+    *npatches = tot[0];
+    *entries = (uint64_t)tot[1] * fbs;
+    if (ptr == nullptr || *entries >= ((uint64_t)1 << 31)) return hipSuccess;
+    hipLaunchKernelGGL(ifp_fill_kernel, dim3(nblk), dim3(SCAN_BLOCK), 0, stream, m, kind, nitems, fbs, bp, bb, nblk, ptr, rows);
+    if (tmp.ok(hipGetLastError())) tmp.ok(hipStreamSynchronize(stream));       // the block offsets live until the kernel has read them
+    return tmp.error();
 }
 
 }  // namespace pa

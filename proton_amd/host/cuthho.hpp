@@ -475,11 +475,12 @@ class interface_assembler {
 
     // The same loop (:1664-1716) and its solve (:1737-1743) with the cell unknowns eliminated on the device: the operators as
     // assemble_all, the cells' static condensation (cut cells in double-double, pa_interface_condensed_ops_batch), the face-only
-    // system directly in CSR (pa_interface_condensed_csr_*), pa_conjugated_gradient on it and the cell unknowns recovered
+    // system directly in CSR (pa_interface_condensed_csr_*), pa_conjugated_gradient on it (patches = PA_PATCH_FACE / PA_PATCH_CELL:
+    // pa_conjugated_gradient_patch on the table of pa_interface_condensed_patches) and the cell unknowns recovered
     // (pa_interface_condensed_recover).  Returns the full solution vector in the reference's numbering -- what
     // conjugated_gradient(LHS, RHS, sol) leaves in `sol` -- for take_local_data; LHS / RHS are left untouched.
     std::vector<T> solve_condensed(const Mesh &msh, const params<T> &parms, int rhs_fn, int dirichlet_fn, const cg_params<T> &cgp,
-                                   size_t *iterations = nullptr, cg_exit_reason *exit_reason = nullptr)
+                                   size_t *iterations = nullptr, cg_exit_reason *exit_reason = nullptr, int patches = -1)
     {
         if (!msh.preprocessed) throw std::logic_error("cutHHO mesh not preprocessed");
         for (size_t c = 0; c < msh.cells.size(); ++c) {                                  // :1304-1305, as assemble_cut
@@ -518,9 +519,21 @@ class interface_assembler {
         int32_t reason = 0;
         size_t iters = 0;
         double rr = 0.0;
-        dev.check(pa_conjugated_gradient(dev.ctx(), nF, d_rowptr.get(), d_colind.get(), d_values.get(), d_b.get(), d_xF.get(),
-                                         cgp.convergence_threshold, cgp.divergence_threshold, cgp.max_iter, cgp.apply_preconditioner ? 1 : 0,
-                                         &reason, &iters, &rr), "pa_conjugated_gradient");
+        if (patches < 0)
+            dev.check(pa_conjugated_gradient(dev.ctx(), nF, d_rowptr.get(), d_colind.get(), d_values.get(), d_b.get(), d_xF.get(),
+                                             cgp.convergence_threshold, cgp.divergence_threshold, cgp.max_iter, cgp.apply_preconditioner ? 1 : 0,
+                                             &reason, &iters, &rr), "pa_conjugated_gradient");
+        else {
+            // patches = PA_PATCH_FACE / PA_PATCH_CELL: the patch preconditioner in place of the point Jacobi
+            size_t npatches = 0, entries = 0;
+            dev.check(pa_interface_condensed_patches_query(dev.ctx(), fd, patches, &npatches, &entries), "pa_interface_condensed_patches_query");
+            proton_amd::device_buffer<int64_t> d_pptr(npatches + 1);
+            proton_amd::device_buffer<int32_t> d_prows(entries + 1);
+            dev.check(pa_interface_condensed_patches(dev.ctx(), fd, patches, d_pptr.get(), d_prows.get()), "pa_interface_condensed_patches");
+            dev.check(pa_conjugated_gradient_patch(dev.ctx(), nF, d_rowptr.get(), d_colind.get(), d_values.get(), d_b.get(), d_xF.get(), npatches,
+                                                   d_pptr.get(), d_prows.get(), cgp.convergence_threshold, cgp.divergence_threshold,
+                                                   cgp.max_iter, &reason, &iters, &rr), "pa_conjugated_gradient_patch");
+        }
         if (cgp.verbose) std::cout << " -> Iteration " << iters << ", rr = " << rr << std::endl;
         if (iterations) *iterations = iters;
         if (exit_reason)
