@@ -542,6 +542,72 @@ enum { PA_PATCH_FACE = 0, PA_PATCH_CELL = 1 };
 int pa_condensed_patches_query(pa_context *ctx, pa_degree_info di, int kind, size_t *npatches, size_t *entries);
 int pa_condensed_patches(pa_context *ctx, pa_degree_info di, int kind, int64_t *d_patch_ptr, int32_t *d_patch_rows);
 
+/* ---- a Galerkin coarse level next to the patches --------------------------------------------------------
+ * The patch sum has no global information: its iteration count grows with 1 / h.  These add one coarse level, solved exactly:
+ *     z = (accumulate ? z : 0) + P (P^T A P)^-1 P^T r
+ * The coarse space is a caller-owned table P (nrows x ncoarse) in CSR: d_p_ptr (nrows + 1, int64, starting at 0), d_p_cols
+ * (int32) and d_p_vals (double).  A row holds 0 to PA_COARSE_MAX_ROW_ENTRIES entries, its columns ascend without repeats and lie
+ * within [0, ncoarse), its values are finite; ncoarse runs from 1 to PA_COARSE_MAX_NODES.  A table that breaks one of these is
+ * refused with PA_ERR_INVALID_ARG and text in pa_last_error(), checked on the device before anything is indexed with it, and no
+ * output buffer is touched (d_scratch is no output).  Callers own the device memory. */
+#define PA_COARSE_MAX_ROW_ENTRIES 4
+#define PA_COARSE_MAX_NODES 4096
+typedef struct {
+    uint64_t entries;            /* d_p_ptr[nrows]                                                                     */
+    uint64_t pt_bytes;           /* bytes of d_pt: P^T in CSR (row pointer, fine rows ascending within a row, values)   */
+    uint64_t factor_doubles;     /* doubles of d_factor: ncoarse (ncoarse + 1) / 2, the packed lower triangle of L^-1    */
+    uint64_t scratch_bytes;      /* bytes of d_scratch (the coarse vectors of an apply, the work space of the factor)    */
+} pa_coarse_precond_info;
+/* solver_cg.hpp:63-144, cuthho_square.cpp:915-919: what a table needs; reads d_p_ptr only (ncoarse within 1..4096 and rows of
+ * 0..4 entries, else PA_ERR_INVALID_ARG).  Waits for the stream. */
+int pa_coarse_precond_query(pa_context *ctx, size_t nrows, size_t ncoarse, const int64_t *d_p_ptr, pa_coarse_precond_info *out);
+/* The set-up of solver_cg.hpp:63-144 (its lines 77-80) for the coarse level (cuthho_square.cpp:915-919): validates the table,
+ * builds P^T into d_pt, forms A_c = P^T A P -- W = A P with at most 16 columns per row (more: PA_ERR_INVALID_ARG), then every
+ * coarse row's lower triangle summed in a fixed order by the lane that owns the column, and mirrored: d_coarse_matrix (ncoarse^2,
+ * may be NULL) is exactly symmetric --, takes its Cholesky factor in plain double and stores the packed lower triangle of L^-1
+ * into d_factor.  The first non-positive pivot j gives *pivot = j + 1 (host, may be NULL; 0 otherwise) and PA_ERR_NOT_SPD.
+ * Waits for the stream. */
+int pa_coarse_precond_factor(pa_context *ctx, size_t nrows, const int64_t *d_rowptr, const int32_t *d_colind, const double *d_values,
+                             size_t ncoarse, const int64_t *d_p_ptr, const int32_t *d_p_cols, const double *d_p_vals, void *d_pt,
+                             double *d_factor, void *d_scratch, double *d_coarse_matrix, int32_t *pivot);
+/* The preconditioner's product of solver_cg.hpp:63-144 (its lines 84 and 126) for the coarse level (cuthho_square.cpp:915-919):
+ * d_z = (accumulate ? d_z : 0) + P L^-T L^-1 P^T d_r with the table, d_pt, d_factor and d_scratch of a pa_coarse_precond_factor
+ * that returned PA_OK.  Restriction: a fixed lane-strided order per coarse row, then a fixed reduction tree; two packed
+ * triangular products; a gather of at most 4 terms per row.  No floating-point atomics, the same bits from call to call. */
+int pa_coarse_precond_apply(pa_context *ctx, size_t nrows, size_t ncoarse, const int64_t *d_p_ptr, const int32_t *d_p_cols,
+                            const double *d_p_vals, const void *d_pt, const double *d_factor, void *d_scratch, int accumulate,
+                            const double *d_r, double *d_z);
+/* conjugated_gradient (solver_cg.hpp:63-144; the solve of cuthho_square.cpp:915-919) with z = (patch sum) + (coarse term): the
+ * arguments and the three results of pa_conjugated_gradient_patch plus the coarse table; the same recurrences, exit tests and
+ * exit order.  The factors live for the call.  Refusals leave d_x untouched: of the patch table first, then of the coarse table
+ * (PA_ERR_INVALID_ARG), then PA_ERR_NOT_SPD of either level before the first iteration. */
+int pa_conjugated_gradient_patch_coarse(pa_context *ctx, size_t nrows, const int64_t *d_rowptr, const int32_t *d_colind,
+                                        const double *d_values, const double *d_b, double *d_x,
+                                        size_t npatches, const int64_t *d_patch_ptr, const int32_t *d_patch_rows,
+                                        size_t ncoarse, const int64_t *d_p_ptr, const int32_t *d_p_cols, const double *d_p_vals,
+                                        double convergence_threshold, double divergence_threshold, size_t max_iter,
+                                        int32_t *exit_reason, size_t *iterations, double *relative_residual);
+/* The coarse table of the face-only system of pa_condensed_csr_pattern (the Poisson and the fictitious-domain systems; the
+ * solve is cuthho_square.cpp:915-919 / solver_cg.hpp:63-144), built on the device: bilinear hats on every H-th mesh line.
+ *   Coarse lines, per direction with N cells: the vertex indices 0, H, 2 H, .. below N, and N (H >= 1; the last interval is
+ *   shorter if H does not divide N).  The 1-D hat of line l_j at vertex index i: 1 at l_j, (double)(i - l_(j-1)) / (double)(l_j -
+ *   l_(j-1)) on the left interval, (double)(l_(j+1) - i) / (double)(l_(j+1) - l_j) on the right one, 0 elsewhere; the 2-D hat is
+ *   phi = wx * wy, one rounding.  Hats live in index space: the table does not change with pa_mesh_set_points.
+ *   Coarse nodes: the crossings of interior lines (the boundary is Dirichlet), row-major, jy outer, jx inner.
+ *   Entries (face basis bases.hpp:253-279: monomials in ep, -1 at the face's first point a, +1 at its second point b): for
+ *   compressed face q and every node with phi(a) != 0 or phi(b) != 0, row q fbs gets 0.5 * (phi(a) + phi(b)), row q fbs + 1
+ *   (fbs >= 2) gets 0.5 * (phi(b) - phi(a)) when that is not zero; the rows of higher modes are empty.
+ *   PA_COARSE_ONE: as above.  PA_COARSE_BY_SIDE (needs pa_cut_preprocess, else PA_ERR_NO_MESH): a face wholly on the side
+ *   opposite to `where` is in part 1, every other face in part 0; a node's hat becomes up to two columns, each restricted to one
+ *   part's faces; all part-0 columns come first, then the part-1 columns, each in node order; empty columns are dropped.
+ * Whole-mesh structured contexts; a slab is refused as pa_condensed_patches refuses one.  No interior node, or more than
+ * PA_COARSE_MAX_NODES columns: PA_ERR_INVALID_ARG with H and the count in pa_last_error().  The query gives ncoarse and the
+ * size of d_p_cols / d_p_vals (*entries); d_p_ptr takes system rows + 1. */
+enum { PA_COARSE_ONE = 0, PA_COARSE_BY_SIDE = 1 };
+int pa_condensed_coarse_query(pa_context *ctx, pa_degree_info di, int H, int parts, int where, size_t *ncoarse, size_t *entries);
+int pa_condensed_coarse(pa_context *ctx, pa_degree_info di, int H, int parts, int where, int64_t *d_p_ptr, int32_t *d_p_cols,
+                        double *d_p_vals);
+
 /* ---- cutHHO (fictitious domain, `cuthho_square -f`) -----------------------------------------
  * circle_level_set / line_level_set, apps/cuthho/cuthho_square.cpp:56-124 */
 typedef struct { int32_t kind; double radius, alpha, beta, cut_y; } pa_level_set;   /* kind 0 circle, 1 line */

@@ -310,16 +310,77 @@ class BatchAssembler:
                                                                x.data_ptr(), ptr.numel() - 1, ptr.data_ptr(), rows.data_ptr(), tol, div, max_iter)
         return x, reason, iters, rr
 
-    def condensed_solve(self, cd, fd, cond, g=None, tol=1e-9, div=100.0, max_iter=None, precond=True, patches=None):
+    # ---- the Galerkin coarse level (coarse_precond.hip) ----------------------------------
+    def condensed_coarse(self, cd, fd, H, parts="one", where=capi.LOC_NEGATIVE):
+        """the coarse table of the face-only system of condensed_csr_pattern: bilinear hats on every H-th mesh line, parts "one" or
+        "side" (every hat split at the interface; needs the cut preprocessing) -> (p_ptr int64 [rows + 1], p_cols int32, p_vals
+        float64, ncoarse)"""
+        di, _ = capi.degree_info(cd, fd)
+        parts = {"one": capi.COARSE_ONE, "side": capi.COARSE_BY_SIDE}.get(parts, parts)
+        ncoarse, entries = self.ctx.condensed_coarse_query(di, H, parts, where)
+        nrows = self.ctx.assembler_query(di).num_other_faces * (fd + 1)
+        ptr = torch.empty(nrows + 1, dtype=torch.int64, device=self.device)
+        cols = torch.empty(max(entries, 1), dtype=torch.int32, device=self.device)
+        vals = torch.empty(max(entries, 1), dtype=torch.float64, device=self.device)
+        self.ctx.condensed_coarse(di, H, parts, where, ptr.data_ptr(), cols.data_ptr(), vals.data_ptr())
+        return ptr, cols[:entries], vals[:entries], ncoarse
+
+    def coarse_precond_factor(self, rowptr, colind, values, coarse, want_matrix=False):
+        """pa_coarse_precond_query + pa_coarse_precond_factor on the table `coarse` = (p_ptr, p_cols, p_vals, ncoarse) -> dict(pt,
+        factor, scratch, pivot, sizes, coarse, n [, matrix]): what coarse_precond_apply takes.  pivot > 0: the coarse matrix has its
+        first non-positive pivot at pivot - 1."""
+        ptr, cols, vals, ncoarse = coarse
+        n = rowptr.numel() - 1
+        sz = self.ctx.coarse_precond_query(n, ncoarse, ptr.data_ptr())
+        pt = torch.zeros(max(sz.pt_bytes, 1), dtype=torch.uint8, device=self.device)       # (its parts are padded to 256 bytes)
+        factor = torch.empty(max(sz.factor_doubles, 1), dtype=torch.float64, device=self.device)
+        scratch = torch.empty(max(sz.scratch_bytes, 1), dtype=torch.uint8, device=self.device)
+        matrix = torch.empty((ncoarse, ncoarse), dtype=torch.float64, device=self.device) if want_matrix else None
+        pivot = self.ctx.coarse_precond_factor(n, rowptr.data_ptr(), colind.data_ptr(), values.data_ptr(), ncoarse, ptr.data_ptr(),
+                                               cols.data_ptr(), vals.data_ptr(), pt.data_ptr(), factor.data_ptr(), scratch.data_ptr(),
+                                               _ptr(matrix))
+        out = {"pt": pt, "factor": factor, "scratch": scratch, "pivot": pivot, "sizes": sz, "coarse": coarse, "n": n}
+        if want_matrix:
+            out["matrix"] = matrix
+        return out
+
+    def coarse_precond_apply(self, pre, r, z=None, accumulate=False):
+        """z = (accumulate ? z : 0) + P (P^T A P)^-1 P^T r with what coarse_precond_factor returned"""
+        ptr, cols, vals, ncoarse = pre["coarse"]
+        if z is None:
+            z = torch.zeros_like(r) if accumulate else torch.empty_like(r)
+        self.ctx.coarse_precond_apply(pre["n"], ncoarse, ptr.data_ptr(), cols.data_ptr(), vals.data_ptr(), pre["pt"].data_ptr(),
+                                      pre["factor"].data_ptr(), pre["scratch"].data_ptr(), accumulate, r.data_ptr(), z.data_ptr())
+        return z
+
+    def conjugated_gradient_patch_coarse(self, rowptr, colind, values, b, patches, coarse, tol=1e-9, div=100.0, max_iter=1000, x=None):
+        """solver_cg.hpp:63-144 with z = (patch sum) + (coarse term) -> (x, exit_reason, iterations, relative residual)"""
+        ptr, rows = patches
+        cptr, ccols, cvals, ncoarse = coarse
+        if x is None:
+            x = torch.empty_like(b)
+        reason, iters, rr = self.ctx.conjugated_gradient_patch_coarse(
+            b.numel(), rowptr.data_ptr(), colind.data_ptr(), values.data_ptr(), b.data_ptr(), x.data_ptr(), ptr.numel() - 1, ptr.data_ptr(),
+            rows.data_ptr(), ncoarse, cptr.data_ptr(), ccols.data_ptr(), cvals.data_ptr(), tol, div, max_iter)
+        return x, reason, iters, rr
+
+    def condensed_solve(self, cd, fd, cond, g=None, tol=1e-9, div=100.0, max_iter=None, precond=True, patches=None, coarse=None):
         """the face-only system of the records `cond` (condensed_ops) assembled (condensed_csr_pattern / condensed_csr_fill) and
-        solved: patches None = conjugated_gradient (precond: Jacobi), "face" / "cell" = conjugated_gradient_patch on that table
+        solved: patches None = conjugated_gradient (precond: Jacobi), "face" / "cell" = conjugated_gradient_patch on that table;
+        coarse = H (needs patches): conjugated_gradient_patch_coarse with the table condensed_coarse(H, "one") as well
         -> (xF, exit_reason, iterations, relative residual).  Whole-mesh contexts."""
+        if coarse is not None and patches is None:
+            raise ValueError("coarse needs patches")
         rowptr, colind = self.condensed_csr_pattern(cd, fd)
         values, b = self.condensed_csr_fill(cd, fd, cond, g)
         if max_iter is None:
             max_iter = 4 * b.numel()
         if patches is None:
             return self.conjugated_gradient(rowptr, colind, values, b, tol=tol, div=div, max_iter=max_iter, precond=precond)
+        if coarse is not None:
+            return self.conjugated_gradient_patch_coarse(rowptr, colind, values, b, self.condensed_patches(cd, fd, patches),
+                                                         self.condensed_coarse(cd, fd, int(coarse), "one"), tol=tol, div=div,
+                                                         max_iter=max_iter)
         return self.conjugated_gradient_patch(rowptr, colind, values, b, self.condensed_patches(cd, fd, patches), tol=tol, div=div,
                                               max_iter=max_iter)
 
@@ -587,13 +648,16 @@ class BatchAssembler:
         return full
 
     def fictdom_condensed_solve(self, fd, where=capi.LOC_NEGATIVE, rhs_fn=capi.FN_SIN_SIN_RHS, bcs_fn=capi.FN_SIN_SIN_SOL, tol=1e-13,
-                                g=None, max_iter=None, precond=True, overlap=False, patches=None):
+                                g=None, max_iter=None, precond=True, overlap=False, patches=None, coarse=None):
         """cuthho_square.cpp:881-919 and :959-962 on the face-only system: the operators (pa_cut_uncut_rhs_batch,
         pa_cut_local_ops_batch; overlap: on the context's side stream), the records, condensed_csr_pattern / condensed_csr_fill,
         conjugated_gradient and the recovery -> (full solution vector, iterations, exit reason).  g: the boundary data
         (default: dirichlet_data of bcs_fn).  patches "face" / "cell": conjugated_gradient_patch on that table of condensed_patches
-        in place of conjugated_gradient.  Whole-mesh contexts."""
+        in place of conjugated_gradient; coarse = H (needs patches): conjugated_gradient_patch_coarse with the table
+        condensed_coarse(H, "side") as well.  Whole-mesh contexts."""
         cd = fd + 1
+        if coarse is not None and patches is None:
+            raise ValueError("coarse needs patches")
         if g is None:
             g = self.dirichlet_data(fd, bcs_fn)
         cut = None
@@ -615,6 +679,10 @@ class BatchAssembler:
             max_iter = 4 * b.numel()
         if patches is None:
             xF, reason, iters, _ = self.conjugated_gradient(rowptr, colind, values, b, tol=tol, max_iter=max_iter, precond=precond)
+        elif coarse is not None:
+            xF, reason, iters, _ = self.conjugated_gradient_patch_coarse(rowptr, colind, values, b, self.condensed_patches(cd, fd, patches),
+                                                                         self.condensed_coarse(cd, fd, int(coarse), "side", where), tol=tol,
+                                                                         max_iter=max_iter)
         else:
             xF, reason, iters, _ = self.conjugated_gradient_patch(rowptr, colind, values, b, self.condensed_patches(cd, fd, patches), tol=tol,
                                                                   max_iter=max_iter)

@@ -51,6 +51,8 @@ EXPORTS = [
     "pa_patch_precond_query", "pa_patch_precond_factor", "pa_patch_precond_apply", "pa_conjugated_gradient_patch",
     "pa_condensed_patches_query", "pa_condensed_patches",
     "pa_interface_condensed_patches_query", "pa_interface_condensed_patches",
+    "pa_coarse_precond_query", "pa_coarse_precond_factor", "pa_coarse_precond_apply", "pa_conjugated_gradient_patch_coarse",
+    "pa_condensed_coarse_query", "pa_condensed_coarse",
 ]
 
 
@@ -140,6 +142,14 @@ PATCH_FACE, PATCH_CELL = 0, 1
 PATCH_MAX_ROWS = 16
 
 
+class CoarsePrecondInfo(C.Structure):
+    _fields_ = [("entries", C.c_uint64), ("pt_bytes", C.c_uint64), ("factor_doubles", C.c_uint64), ("scratch_bytes", C.c_uint64)]
+
+
+COARSE_ONE, COARSE_BY_SIDE = 0, 1
+COARSE_MAX_ROW_ENTRIES, COARSE_MAX_NODES = 4, 4096
+
+
 class LevelSet(C.Structure):
     _fields_ = [("kind", C.c_int32), ("radius", C.c_double), ("alpha", C.c_double), ("beta", C.c_double),
                 ("cut_y", C.c_double)]
@@ -218,6 +228,13 @@ def lib():
                                                C.POINTER(C.c_int32), C.POINTER(sz), C.POINTER(C.c_double)]
     L.pa_condensed_patches_query.argtypes = [vp, DegreeInfo, C.c_int, C.POINTER(sz), C.POINTER(sz)]
     L.pa_condensed_patches.argtypes = [vp, DegreeInfo, C.c_int, dp, dp]
+    L.pa_coarse_precond_query.argtypes = [vp, sz, sz, dp, C.POINTER(CoarsePrecondInfo)]
+    L.pa_coarse_precond_factor.argtypes = [vp, sz, dp, dp, dp, sz, dp, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_int32)]
+    L.pa_coarse_precond_apply.argtypes = [vp, sz, sz, dp, dp, dp, dp, dp, dp, C.c_int, dp, dp]
+    L.pa_conjugated_gradient_patch_coarse.argtypes = [vp, sz, dp, dp, dp, dp, dp, sz, dp, dp, sz, dp, dp, dp, C.c_double, C.c_double, sz,
+                                                      C.POINTER(C.c_int32), C.POINTER(sz), C.POINTER(C.c_double)]
+    L.pa_condensed_coarse_query.argtypes = [vp, DegreeInfo, C.c_int, C.c_int, C.c_int, C.POINTER(sz), C.POINTER(sz)]
+    L.pa_condensed_coarse.argtypes = [vp, DegreeInfo, C.c_int, C.c_int, C.c_int, dp, dp, dp]
     L.pa_conjugated_gradient_rows.argtypes = [vp, C.POINTER(CgTransport), C.c_int64, C.c_int64, dp, dp, dp, dp, dp, C.c_double, C.c_double, sz,
                                               C.c_int, C.POINTER(C.c_int32), C.POINTER(sz), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
     L.pa_comm_cg_transport.argtypes = [vp, C.POINTER(CgTransport)]
@@ -550,6 +567,41 @@ class Context:
 
     def condensed_patches(self, di, kind, patch_ptr, patch_rows):
         self._ck(self._L.pa_condensed_patches(self.h, di, kind, patch_ptr, patch_rows), "pa_condensed_patches")
+
+    def coarse_precond_query(self, nrows, ncoarse, p_ptr):
+        out = CoarsePrecondInfo()
+        self._ck(self._L.pa_coarse_precond_query(self.h, nrows, ncoarse, p_ptr, C.byref(out)), "pa_coarse_precond_query")
+        return out
+
+    def coarse_precond_factor(self, nrows, rowptr, colind, values, ncoarse, p_ptr, p_cols, p_vals, pt, factor, scratch, coarse_matrix=None):
+        """-> 0, or j + 1 for the first non-positive pivot j of the coarse matrix; other refusals raise"""
+        pivot = C.c_int32(0)
+        st = self._L.pa_coarse_precond_factor(self.h, nrows, rowptr, colind, values, ncoarse, p_ptr, p_cols, p_vals, pt, factor, scratch,
+                                              coarse_matrix, C.byref(pivot))
+        if st != 6:                                   # PA_ERR_NOT_SPD: the caller reads the pivot
+            self._ck(st, "pa_coarse_precond_factor")
+        return pivot.value
+
+    def coarse_precond_apply(self, nrows, ncoarse, p_ptr, p_cols, p_vals, pt, factor, scratch, accumulate, r, z):
+        self._ck(self._L.pa_coarse_precond_apply(self.h, nrows, ncoarse, p_ptr, p_cols, p_vals, pt, factor, scratch, int(accumulate), r, z),
+                 "pa_coarse_precond_apply")
+
+    def conjugated_gradient_patch_coarse(self, nrows, rowptr, colind, values, b, x, npatches, patch_ptr, patch_rows, ncoarse, p_ptr, p_cols,
+                                         p_vals, tol=1e-9, div=100.0, max_iter=1000):
+        reason, iters, rr = C.c_int32(0), C.c_size_t(0), C.c_double(0.0)
+        self._ck(self._L.pa_conjugated_gradient_patch_coarse(self.h, nrows, rowptr, colind, values, b, x, npatches, patch_ptr, patch_rows,
+                                                             ncoarse, p_ptr, p_cols, p_vals, tol, div, max_iter, C.byref(reason),
+                                                             C.byref(iters), C.byref(rr)), "pa_conjugated_gradient_patch_coarse")
+        return reason.value, iters.value, rr.value
+
+    def condensed_coarse_query(self, di, H, parts, where):
+        ncoarse, entries = C.c_size_t(0), C.c_size_t(0)
+        self._ck(self._L.pa_condensed_coarse_query(self.h, di, H, parts, where, C.byref(ncoarse), C.byref(entries)),
+                 "pa_condensed_coarse_query")
+        return ncoarse.value, entries.value
+
+    def condensed_coarse(self, di, H, parts, where, p_ptr, p_cols, p_vals):
+        self._ck(self._L.pa_condensed_coarse(self.h, di, H, parts, where, p_ptr, p_cols, p_vals), "pa_condensed_coarse")
 
     def copy_to_host(self, host_dst, d_src, nbytes):
         self._ck(self._L.pa_copy_to_host(self.h, host_dst, d_src, nbytes), "pa_copy_to_host")

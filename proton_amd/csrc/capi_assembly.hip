@@ -1,10 +1,11 @@
 // capi_assembly.hip -- the C ABI of the global systems of an uncut mesh: the assembler's triplets and local data, the energy form,
-// the condensed (face-only) system, the assembler's own system directly in CSR, triplets to CSR, the conjugate gradient, and the patch preconditioner with its tables.
+// the condensed (face-only) system, the assembler's own system directly in CSR, triplets to CSR, the conjugate gradient, the patch preconditioner with its tables, and the Galerkin coarse level with its table.
 #include <hip/hip_runtime.h>
 
 #include <string>
 
 #include "cg.hpp"
+#include "coarse_precond.hpp"
 #include "context.hpp"
 #include "csr.hpp"
 #include "device_tmp.hpp"
@@ -555,5 +556,138 @@ int pa_condensed_patches(pa_context *ctx, pa_degree_info di, int kind, int64_t *
     pa::cell_patches(ctx->stream, v.ncells, count, v.cell_faces, v.face_compress, v.cprefix, index, fbs, d_patch_ptr, d_patch_rows);
     PA_HIP(ctx, hipGetLastError());
     PA_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the index lives until the kernel has read it
+    return PA_OK;
+}
+
+// ---- the Galerkin coarse level and the conjugate gradient with it: coarse_precond.hip --------------------------------------------
+static int coarse_refused(pa_context *ctx, const char *who, int refusal)
+{
+    ctx->last_error = std::string(who) + ": " + pa::coarse_refusal_text(refusal);
+    return PA_ERR_INVALID_ARG;
+}
+
+int pa_coarse_precond_query(pa_context *ctx, size_t nrows, size_t ncoarse, const int64_t *d_p_ptr, pa_coarse_precond_info *out)
+{
+    if (!ctx || !d_p_ptr || !out) return PA_ERR_INVALID_ARG;
+    PA_HIP(ctx, hipSetDevice(ctx->device));
+    pa::CoarseSizes sz;
+    int refusal = 0;
+    PA_HIP(ctx, pa::coarse_query(ctx->stream, nrows, ncoarse, d_p_ptr, &sz, &refusal));
+    if (refusal) return coarse_refused(ctx, "pa_coarse_precond_query", refusal);
+    out->entries = sz.entries; out->pt_bytes = sz.pt_bytes; out->factor_doubles = sz.factor_doubles; out->scratch_bytes = sz.scratch_bytes;
+    return PA_OK;
+}
+
+int pa_coarse_precond_factor(pa_context *ctx, size_t nrows, const int64_t *d_rowptr, const int32_t *d_colind, const double *d_values,
+                             size_t ncoarse, const int64_t *d_p_ptr, const int32_t *d_p_cols, const double *d_p_vals, void *d_pt,
+                             double *d_factor, void *d_scratch, double *d_coarse_matrix, int32_t *pivot)
+{
+    if (!ctx || !d_rowptr || !d_p_ptr || !d_pt || !d_factor || !d_scratch) return PA_ERR_INVALID_ARG;
+    if (nrows && (!d_colind || !d_values || !d_p_cols || !d_p_vals)) return PA_ERR_INVALID_ARG;
+    PA_HIP(ctx, hipSetDevice(ctx->device));
+    pa::CoarseSizes sz;
+    int refusal = 0;
+    PA_HIP(ctx, pa::coarse_query(ctx->stream, nrows, ncoarse, d_p_ptr, &sz, &refusal));
+    if (refusal) return coarse_refused(ctx, "pa_coarse_precond_factor", refusal);
+    const pa::CoarseTable t{nrows, ncoarse, d_p_ptr, d_p_cols, d_p_vals};
+    PA_HIP(ctx, pa::coarse_validate(ctx->stream, t, sz, d_scratch, &refusal));
+    if (refusal) return coarse_refused(ctx, "pa_coarse_precond_factor", refusal);
+    int32_t piv = 0;
+    PA_HIP(ctx, pa::coarse_factor(ctx->stream, d_rowptr, d_colind, d_values, t, sz, d_pt, d_factor, d_scratch, d_coarse_matrix, &piv, &refusal));
+    if (refusal) return coarse_refused(ctx, "pa_coarse_precond_factor", refusal);
+    if (pivot) *pivot = piv;
+    if (piv) { ctx->last_error = "pa_coarse_precond_factor: the coarse matrix is not positive definite (pivot " + std::to_string(piv - 1) + ")"; return PA_ERR_NOT_SPD; }
+    return PA_OK;
+}
+
+int pa_coarse_precond_apply(pa_context *ctx, size_t nrows, size_t ncoarse, const int64_t *d_p_ptr, const int32_t *d_p_cols,
+                            const double *d_p_vals, const void *d_pt, const double *d_factor, void *d_scratch, int accumulate,
+                            const double *d_r, double *d_z)
+{
+    if (!ctx || !d_p_ptr || !d_pt || !d_factor || !d_scratch) return PA_ERR_INVALID_ARG;
+    if (nrows && (!d_p_cols || !d_p_vals || !d_r || !d_z)) return PA_ERR_INVALID_ARG;
+    PA_HIP(ctx, hipSetDevice(ctx->device));
+    pa::CoarseSizes sz;
+    int refusal = 0;
+    PA_HIP(ctx, pa::coarse_query(ctx->stream, nrows, ncoarse, d_p_ptr, &sz, &refusal));
+    if (refusal) return coarse_refused(ctx, "pa_coarse_precond_apply", refusal);
+    const pa::CoarseTable t{nrows, ncoarse, d_p_ptr, d_p_cols, d_p_vals};
+    pa::coarse_apply(ctx->stream, t, sz, d_pt, d_factor, d_scratch, accumulate, d_r, d_z, nullptr);
+    PA_HIP(ctx, hipGetLastError());
+    return PA_OK;
+}
+
+int pa_conjugated_gradient_patch_coarse(pa_context *ctx, size_t nrows, const int64_t *d_rowptr, const int32_t *d_colind,
+                                        const double *d_values, const double *d_b, double *d_x, size_t npatches,
+                                        const int64_t *d_patch_ptr, const int32_t *d_patch_rows, size_t ncoarse, const int64_t *d_p_ptr,
+                                        const int32_t *d_p_cols, const double *d_p_vals, double convergence_threshold,
+                                        double divergence_threshold, size_t max_iter, int32_t *exit_reason, size_t *iterations,
+                                        double *relative_residual)
+{
+    if (!ctx || !d_rowptr || (nrows && (!d_colind || !d_values || !d_b || !d_x || !d_patch_ptr || !d_patch_rows || !d_p_ptr || !d_p_cols ||
+                                        !d_p_vals)))
+        return PA_ERR_INVALID_ARG;
+    PA_HIP(ctx, hipSetDevice(ctx->device));
+    int reason = 0, status = 0, refusal = 0;
+    int32_t pivot = 0;
+    PA_HIP(ctx, pa::conjugated_gradient_patch_coarse(ctx->stream, nrows, d_rowptr, d_colind, d_values, d_b, d_x, npatches, d_patch_ptr,
+                                                     d_patch_rows, ncoarse, d_p_ptr, d_p_cols, d_p_vals, convergence_threshold,
+                                                     divergence_threshold, max_iter, &reason, iterations, relative_residual, &status,
+                                                     &refusal, &pivot));
+    if (status == 1) return patch_refused(ctx, "pa_conjugated_gradient_patch_coarse", refusal);
+    if (status == 3) return coarse_refused(ctx, "pa_conjugated_gradient_patch_coarse", refusal);
+    if (status == 2) { ctx->last_error = "pa_conjugated_gradient_patch_coarse: a patch matrix is not positive definite (pa_patch_precond_factor says which)"; return PA_ERR_NOT_SPD; }
+    if (status == 4) { ctx->last_error = "pa_conjugated_gradient_patch_coarse: the coarse matrix is not positive definite (pivot " + std::to_string(pivot - 1) + ")"; return PA_ERR_NOT_SPD; }
+    if (exit_reason) *exit_reason = reason;
+    return PA_OK;
+}
+
+// the refusals of the two pa_condensed_coarse entries and the mesh they read
+static int coarse_mesh(pa_context *ctx, pa_degree_info di, int H, int parts, int where, pa::CoarseMesh *m)
+{
+    if (!degree_ok(di) || H < 1 || (parts != PA_COARSE_ONE && parts != PA_COARSE_BY_SIDE)) return PA_ERR_INVALID_ARG;
+    if (parts == PA_COARSE_BY_SIDE && where != PA_LOC_NEGATIVE && where != PA_LOC_POSITIVE) return PA_ERR_INVALID_ARG;
+    PA_HIP(ctx, hipSetDevice(ctx->device));
+    const int st = asm_prepare(ctx);                     // whole-mesh contexts only, as pa_condensed_patches
+    if (st != PA_OK) return st;
+    if (!ctx->faces.structured) { ctx->last_error = "pa_condensed_coarse: the mesh of pa_mesh_generate / pa_cut_preprocess only"; return PA_ERR_INVALID_ARG; }
+    if (parts == PA_COARSE_BY_SIDE && (!ctx->cut.host || !ctx->cut.face_loc.get())) return PA_ERR_NO_MESH;
+    PA_HIP(ctx, join_side_stream(ctx));
+    m->sm = ctx->faces.sm; m->nfaces = (uint32_t)ctx->faces.nfaces_local;
+    m->face_pts = ctx->faces.face_pts.get(); m->face_compress = ctx->faces.face_compress.get();
+    m->face_loc = parts == PA_COARSE_BY_SIDE ? ctx->cut.face_loc.get() : nullptr; m->where = where;
+    return PA_OK;
+}
+
+static int coarse_count_refused(pa_context *ctx, const char *who, int H, uint64_t ncoarse)
+{
+    ctx->last_error = std::string(who) + ": H = " + std::to_string(H) + " gives " + std::to_string(ncoarse) +
+                      " coarse columns; 1 to " + std::to_string(PA_COARSE_MAX_NODES) + " are served";
+    return PA_ERR_INVALID_ARG;
+}
+
+int pa_condensed_coarse_query(pa_context *ctx, pa_degree_info di, int H, int parts, int where, size_t *ncoarse, size_t *entries)
+{
+    if (!ctx || !ncoarse || !entries) return PA_ERR_INVALID_ARG;
+    pa::CoarseMesh m;
+    const int st = coarse_mesh(ctx, di, H, parts, where, &m);
+    if (st != PA_OK) return st;
+    uint64_t nc = 0, ne = 0;
+    PA_HIP(ctx, pa::condensed_coarse(ctx->stream, m, di.face_deg + 1, H, &nc, &ne, nullptr, nullptr, nullptr));
+    if (nc < 1 || nc > (uint64_t)PA_COARSE_MAX_NODES) return coarse_count_refused(ctx, "pa_condensed_coarse_query", H, nc);
+    *ncoarse = (size_t)nc;
+    *entries = (size_t)ne;
+    return PA_OK;
+}
+
+int pa_condensed_coarse(pa_context *ctx, pa_degree_info di, int H, int parts, int where, int64_t *d_p_ptr, int32_t *d_p_cols, double *d_p_vals)
+{
+    if (!ctx || !d_p_ptr || !d_p_cols || !d_p_vals) return PA_ERR_INVALID_ARG;
+    pa::CoarseMesh m;
+    const int st = coarse_mesh(ctx, di, H, parts, where, &m);
+    if (st != PA_OK) return st;
+    uint64_t nc = 0, ne = 0;
+    PA_HIP(ctx, pa::condensed_coarse(ctx->stream, m, di.face_deg + 1, H, &nc, &ne, d_p_ptr, d_p_cols, d_p_vals));
+    if (nc < 1 || nc > (uint64_t)PA_COARSE_MAX_NODES) return coarse_count_refused(ctx, "pa_condensed_coarse", H, nc);
     return PA_OK;
 }

@@ -1,0 +1,76 @@
+// coarse_precond.hpp -- host entry points of coarse_precond.hip: a Galerkin coarse level for the device conjugate gradient
+//   z = (accumulate ? z : 0) + P (P^T A P)^-1 P^T r
+// added to the patch sum of patch_precond.hpp in the conjugate gradient of solver_cg.hpp:63-144 (the solve of
+// cuthho_square.cpp:915-919), and the coarse table of the face-only system: bilinear hats on every H-th mesh line.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "structured_mesh.hpp"
+
+namespace pa {
+
+constexpr int COARSE_MAX_ROW_ENTRIES = 4;  // PA_COARSE_MAX_ROW_ENTRIES
+constexpr int COARSE_MAX_NODES = 4096;     // PA_COARSE_MAX_NODES
+constexpr int COARSE_W_SLOTS = 16;         // (column, value) slots of a row of A P
+
+// the coarse table P (n x ncoarse) in CSR: row i holds cols[ptr[i]] .. cols[ptr[i + 1] - 1], ascending, with vals
+struct CoarseTable {
+    size_t n, ncoarse;
+    const int64_t *ptr;                    // n + 1
+    const int32_t *cols;
+    const double *vals;
+};
+
+// what one table needs.  pt: P^T in CSR as one buffer (row pointer, fine rows, values); the factor is the packed lower triangle of
+// L^-1 (row i at i (i + 1) / 2); the scratch holds the coarse vectors of an apply in front and the build's work space behind
+struct CoarseSizes {
+    uint64_t entries;                      // ptr[n]
+    uint64_t pt_bytes, factor_doubles, scratch_bytes;
+};
+
+// why a table was refused (0 = it was not); where a table breaks several rules the largest code is reported
+enum { COARSE_OK = 0, COARSE_BAD_SIZE = 1, COARSE_BAD_VALUE = 2, COARSE_BAD_ORDER = 3, COARSE_BAD_INDEX = 4, COARSE_BAD_NODES = 5,
+       COARSE_TOO_LARGE = 6, COARSE_W_OVERFLOW = 7 };
+const char *coarse_refusal_text(int refusal);
+
+// sizes of the table; checks ncoarse and ptr alone (ptr[0] = 0, every row of 0..4 entries).  Waits for the stream.
+hipError_t coarse_query(hipStream_t stream, size_t n, size_t ncoarse, const int64_t *ptr, CoarseSizes *out, int *refusal);
+// the columns and values of a table whose ptr has passed coarse_query: in range, ascending, finite.  Writes scratch only.  Waits.
+hipError_t coarse_validate(hipStream_t stream, const CoarseTable &t, const CoarseSizes &sz, void *scratch, int *refusal);
+// P^T, A_c = P^T A P (to coarse_matrix as well if not null), its Cholesky factor and the packed L^-1 of a validated table;
+// *pivot = 0 or j + 1 for the first non-positive pivot j; *refusal: a row of A P beyond COARSE_W_SLOTS columns.  Waits.
+hipError_t coarse_factor(hipStream_t stream, const int64_t *rowptr, const int32_t *colind, const double *values, const CoarseTable &t,
+                         const CoarseSizes &sz, void *pt, double *factor, void *scratch, double *coarse_matrix, int32_t *pivot,
+                         int *refusal);
+// z = (accumulate ? z : 0) + P L^-T L^-1 P^T r; part_rz (may be null): the partial sums of r . z per block of RB rows
+void coarse_apply(hipStream_t stream, const CoarseTable &t, const CoarseSizes &sz, const void *pt, const double *factor, void *scratch,
+                  int accumulate, const double *r, double *z, double *part_rz);
+
+// status: 0 solved (see exit_reason), 1 patch table refused, 2 a patch is not positive definite, 3 coarse table refused
+// (*refusal: its code), 4 the coarse matrix is not positive definite (*pivot); x is written only with 0
+hipError_t conjugated_gradient_patch_coarse(hipStream_t stream, size_t n, const int64_t *rowptr, const int32_t *colind,
+                                            const double *values, const double *b, double *x, size_t npatches, const int64_t *patch_ptr,
+                                            const int32_t *patch_rows, size_t ncoarse, const int64_t *p_ptr, const int32_t *p_cols,
+                                            const double *p_vals, double convergence_threshold, double divergence_threshold,
+                                            size_t max_iter, int *exit_reason, size_t *iterations, double *relative_residual, int *status,
+                                            int *refusal, int32_t *pivot);
+
+// ---- the coarse table of the face-only system of pa_condensed_csr_pattern (whole-mesh structured contexts) ----
+// The mesh and what a face is: its two points (face_pts, point p = vertex (p % (Nx + 1), p / (Nx + 1))), its compressed id (-1
+// Dirichlet) and, by side, its location (face_loc) against `where`.  ptr = null: the sizes only.  Waits for the stream.
+struct CoarseMesh {
+    StructuredMesh sm;
+    uint32_t nfaces;
+    const uint32_t *face_pts;
+    const int32_t *face_compress;
+    const int8_t *face_loc;                // null: one part
+    int where;
+};
+hipError_t condensed_coarse(hipStream_t stream, const CoarseMesh &m, int fbs, int H, uint64_t *ncoarse, uint64_t *entries, int64_t *ptr,
+                            int32_t *cols, double *vals);
+
+}  // namespace pa

@@ -1095,15 +1095,17 @@ class assembler {
     // unknowns eliminated on the device: the operators as assemble_all_fictdom, every cell's packed condensed record
     // (pa_fictdom_condensed_ops_batch: cut cells in double-double), the face-only system directly in CSR (pa_condensed_csr_*),
     // pa_conjugated_gradient on it (patches = PA_PATCH_FACE / PA_PATCH_CELL: pa_conjugated_gradient_patch on the table of
-    // pa_condensed_patches) and the cell unknowns recovered (pa_fictdom_condensed_recover).  Returns the full solution
+    // pa_condensed_patches; with coarse = H > 0 as well: pa_conjugated_gradient_patch_coarse with the table of pa_condensed_coarse,
+    // every hat split by side of the interface) and the cell unknowns recovered (pa_fictdom_condensed_recover).  Returns the full solution
     // vector in the reference's numbering -- what solver.solve(RHS) leaves in `sol` -- for take_local_data; LHS / RHS are left
     // untouched.
     template <typename LevelSet, typename Location>
     std::vector<T> solve_condensed_fictdom(const Mesh &msh, const LevelSet & /*level_set_function*/, Location where, int rhs_fn, int dirichlet_fn,
                                            const cg_params<T> &cgp, size_t *iterations = nullptr, cg_exit_reason *exit_reason = nullptr,
-                                           int patches = -1)
+                                           int patches = -1, int coarse = 0)
     {
         if (!msh.preprocessed) throw std::logic_error("cutHHO mesh not preprocessed");
+        if (coarse > 0 && patches < 0) throw std::invalid_argument("solve_condensed_fictdom: coarse needs patches");
         auto &dev = proton_amd::device::instance();
         pa_sizes sz;
         dev.check(pa_sizes_for(di.c_abi(), PA_QUAD_FAN, &sz), "pa_sizes_for");
@@ -1143,6 +1145,21 @@ class assembler {
             proton_amd::device_buffer<int64_t> d_pptr(npatches + 1);
             proton_amd::device_buffer<int32_t> d_prows(entries + 1);
             dev.check(pa_condensed_patches(dev.ctx(), di.c_abi(), patches, d_pptr.get(), d_prows.get()), "pa_condensed_patches");
+            if (coarse > 0) {
+                // ... and the Galerkin coarse level: bilinear hats on every coarse-th mesh line, split by side of the interface
+                size_t ncoarse = 0, centries = 0;
+                dev.check(pa_condensed_coarse_query(dev.ctx(), di.c_abi(), coarse, PA_COARSE_BY_SIDE, (int)where, &ncoarse, &centries),
+                          "pa_condensed_coarse_query");
+                proton_amd::device_buffer<int64_t> d_cptr(nF + 1);
+                proton_amd::device_buffer<int32_t> d_ccols(centries + 1);
+                proton_amd::device_buffer<double> d_cvals(centries + 1);
+                dev.check(pa_condensed_coarse(dev.ctx(), di.c_abi(), coarse, PA_COARSE_BY_SIDE, (int)where, d_cptr.get(), d_ccols.get(),
+                                              d_cvals.get()), "pa_condensed_coarse");
+                dev.check(pa_conjugated_gradient_patch_coarse(dev.ctx(), nF, d_rowptr.get(), d_colind.get(), d_values.get(), d_b.get(), d_xF.get(),
+                                                              npatches, d_pptr.get(), d_prows.get(), ncoarse, d_cptr.get(), d_ccols.get(),
+                                                              d_cvals.get(), cgp.convergence_threshold, cgp.divergence_threshold, cgp.max_iter,
+                                                              &reason, &iters, &rr), "pa_conjugated_gradient_patch_coarse");
+            } else
             dev.check(pa_conjugated_gradient_patch(dev.ctx(), nF, d_rowptr.get(), d_colind.get(), d_values.get(), d_b.get(), d_xF.get(), npatches,
                                                    d_pptr.get(), d_prows.get(), cgp.convergence_threshold, cgp.divergence_threshold,
                                                    cgp.max_iter, &reason, &iters, &rr), "pa_conjugated_gradient_patch");
