@@ -858,6 +858,28 @@ int pa_interface_condensed_recover(pa_context *ctx, int face_deg, const double *
  * is joined first.  Both wait for the stream. */
 int pa_interface_condensed_patches_query(pa_context *ctx, int face_deg, int kind, size_t *npatches, size_t *entries);
 int pa_interface_condensed_patches(pa_context *ctx, int face_deg, int kind, int64_t *d_patch_ptr, int32_t *d_patch_rows);
+/* The coarse table of that face-only system for pa_coarse_precond_* / pa_conjugated_gradient_patch_coarse (solver_cg.hpp:63-144
+ * with z = patch sum + P (P^T A P)^-1 P^T r where the reference has 1 / diag(A); the solve it serves is
+ * cuthho_square.cpp:1737-1743), in interface_assembler's numbering, built on the device.  Rows are rows of
+ * pa_interface_condensed_csr_pattern: unknown k of block b at b fbs + k; an uncut non-Dirichlet face owns one block, a cut face
+ * two (negative side, then positive side).  The hats are pa_condensed_coarse's -- the same coarse lines, 1-D and 2-D hats and
+ * node order, the same arithmetic -- and so are the entries of a block: from the end points a, b of its face, row b fbs gets
+ * 0.5 * (phi(a) + phi(b)) for every node with phi(a) != 0 or phi(b) != 0, row b fbs + 1 (fbs >= 2) gets 0.5 * (phi(b) - phi(a))
+ * where that is not zero, higher modes are empty.  The face basis of a cut face is the whole face's (cuthho_square.cpp:371, 471,
+ * 594): both of its blocks get the same values.
+ *   PA_COARSE_ONE: the column is the node.  PA_COARSE_BY_SIDE: the block of an uncut face is in the part of the face's side
+ *   (0 negative, 1 positive), a cut face's first block in part 0 and its second in part 1; part-0 columns come first, then the
+ *   part-1 columns, each in node order; columns no block touches are dropped -- the table pa_condensed_coarse(..,
+ *   PA_COARSE_BY_SIDE, PA_LOC_NEGATIVE) would build if every block were a face of its own.
+ * A cut face on the Dirichlet boundary is counted by the numbering and owns nothing: its row group stays empty (equal pointers).
+ * The query gives ncoarse and the size of d_p_cols / d_p_vals (*entries); d_p_ptr takes system_size + 1.  Refused, before
+ * anything is written: what pa_interface_csr_* refuses, in its order (face_deg 0..3, whole-mesh cut contexts, system_size <
+ * 2^31); H < 1, an unknown `parts` or a NULL output (PA_ERR_INVALID_ARG); no interior node, or more than PA_COARSE_MAX_NODES
+ * columns (PA_ERR_INVALID_ARG with H and the count in pa_last_error()).  Pending side-stream work
+ * (pa_context_set_cut_overlap) is joined first.  Both wait for the stream. */
+int pa_interface_condensed_coarse_query(pa_context *ctx, int face_deg, int H, int parts, size_t *ncoarse, size_t *entries);
+int pa_interface_condensed_coarse(pa_context *ctx, int face_deg, int H, int parts, int64_t *d_p_ptr, int32_t *d_p_cols,
+                                  double *d_p_vals);
 
 /* The face-only system of interface_assembler assembled and solved BY ROW SLABS (cuthho_square.cpp:1142-1178 the numbering,
  * :1203-1354 the assembly, :1664-1743 the loop and the solve; the reference has one process).  The context is one of

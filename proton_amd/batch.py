@@ -817,10 +817,27 @@ class BatchAssembler:
         self.ctx.interface_condensed_patches(fd, kind, ptr.data_ptr(), rows.data_ptr())
         return ptr, rows[:entries]
 
-    def interface_condensed_solve(self, fd, ops, g=None, tol=1e-9, div=100.0, max_iter=None, precond=True, patches=None):
+    def interface_condensed_coarse(self, fd, H, parts="side"):
+        """the coarse table of the face-only system of interface_condensed_csr_pattern: condensed_coarse's hats on every H-th mesh
+        line, both blocks of a cut face with the face's values; parts "one", or "side" (an uncut face's block in the part of its
+        side, a cut face's blocks one in each) -> (p_ptr int64 [rows + 1], p_cols int32, p_vals float64, ncoarse)"""
+        parts = {"one": capi.COARSE_ONE, "side": capi.COARSE_BY_SIDE}.get(parts, parts)
+        ncoarse, entries = self.ctx.interface_condensed_coarse_query(fd, H, parts)
+        nrows = self.ctx.interface_condensed_query(fd).system_size
+        ptr = torch.empty(nrows + 1, dtype=torch.int64, device=self.device)
+        cols = torch.empty(max(entries, 1), dtype=torch.int32, device=self.device)
+        vals = torch.empty(max(entries, 1), dtype=torch.float64, device=self.device)
+        self.ctx.interface_condensed_coarse(fd, H, parts, ptr.data_ptr(), cols.data_ptr(), vals.data_ptr())
+        return ptr, cols[:entries], vals[:entries], ncoarse
+
+    def interface_condensed_solve(self, fd, ops, g=None, tol=1e-9, div=100.0, max_iter=None, precond=True, patches=None, coarse=None,
+                                  coarse_parts="side"):
         """cuthho_square.cpp:1664-1743 on the face-only system from interface_local_ops' dict: the records, the pattern, the fill,
         conjugated_gradient (precond: Jacobi) or, patches "face" / "cell", conjugated_gradient_patch on that table of
-        interface_condensed_patches, and the recovery -> (full solution vector, iterations, exit reason)"""
+        interface_condensed_patches, and the recovery; coarse = H (needs patches): conjugated_gradient_patch_coarse with the table
+        interface_condensed_coarse(H, coarse_parts) as well -> (full solution vector, iterations, exit reason)"""
+        if coarse is not None and patches is None:
+            raise ValueError("coarse needs patches")
         rec = self.interface_condensed_ops(fd, ops)
         rowptr, colind = self.interface_condensed_csr_pattern(fd)
         values, b = self.interface_condensed_csr_fill(fd, rec, g)
@@ -828,6 +845,10 @@ class BatchAssembler:
             max_iter = 20 * b.numel()
         if patches is None:
             xF, reason, iters, _ = self.conjugated_gradient(rowptr, colind, values, b, tol=tol, div=div, max_iter=max_iter, precond=precond)
+        elif coarse is not None:
+            xF, reason, iters, _ = self.conjugated_gradient_patch_coarse(rowptr, colind, values, b, self.interface_condensed_patches(fd, patches),
+                                                                         self.interface_condensed_coarse(fd, int(coarse), coarse_parts),
+                                                                         tol=tol, div=div, max_iter=max_iter)
         else:
             xF, reason, iters, _ = self.conjugated_gradient_patch(rowptr, colind, values, b, self.interface_condensed_patches(fd, patches),
                                                                   tol=tol, div=div, max_iter=max_iter)

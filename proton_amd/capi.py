@@ -53,6 +53,7 @@ EXPORTS = [
     "pa_interface_condensed_patches_query", "pa_interface_condensed_patches",
     "pa_coarse_precond_query", "pa_coarse_precond_factor", "pa_coarse_precond_apply", "pa_conjugated_gradient_patch_coarse",
     "pa_condensed_coarse_query", "pa_condensed_coarse",
+    "pa_interface_condensed_coarse_query", "pa_interface_condensed_coarse",
 ]
 
 
@@ -287,6 +288,8 @@ def lib():
     L.pa_interface_condensed_recover.argtypes = [vp, C.c_int] + [dp] * 7
     L.pa_interface_condensed_patches_query.argtypes = [vp, C.c_int, C.c_int, C.POINTER(sz), C.POINTER(sz)]
     L.pa_interface_condensed_patches.argtypes = [vp, C.c_int, C.c_int, dp, dp]
+    L.pa_interface_condensed_coarse_query.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(sz), C.POINTER(sz)]
+    L.pa_interface_condensed_coarse.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, dp, dp]
     L.pa_interface_rows_partition_info.argtypes = [sz, sz, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(LevelSet), C.c_int, sz, sz,
                                                    C.c_int, C.POINTER(InterfaceRowsInfo)]
     L.pa_interface_rows_query.argtypes = [vp, C.c_int, C.POINTER(InterfaceRowsInfo)]
@@ -751,6 +754,15 @@ class Context:
 
     def interface_condensed_patches(self, face_deg, kind, patch_ptr, patch_rows):
         self._ck(self._L.pa_interface_condensed_patches(self.h, face_deg, kind, patch_ptr, patch_rows), "pa_interface_condensed_patches")
+
+    def interface_condensed_coarse_query(self, face_deg, H, parts):
+        ncoarse, entries = C.c_size_t(0), C.c_size_t(0)
+        self._ck(self._L.pa_interface_condensed_coarse_query(self.h, face_deg, H, parts, C.byref(ncoarse), C.byref(entries)),
+                 "pa_interface_condensed_coarse_query")
+        return ncoarse.value, entries.value
+
+    def interface_condensed_coarse(self, face_deg, H, parts, p_ptr, p_cols, p_vals):
+        self._ck(self._L.pa_interface_condensed_coarse(self.h, face_deg, H, parts, p_ptr, p_cols, p_vals), "pa_interface_condensed_coarse")
 
     def interface_rows_query(self, face_deg):
         out = InterfaceRowsInfo()

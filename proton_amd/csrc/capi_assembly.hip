@@ -659,7 +659,7 @@ static int coarse_mesh(pa_context *ctx, pa_degree_info di, int H, int parts, int
     return PA_OK;
 }
 
-static int coarse_count_refused(pa_context *ctx, const char *who, int H, uint64_t ncoarse)
+int coarse_count_refused(pa_context *ctx, const char *who, int H, uint64_t ncoarse)
 {
     ctx->last_error = std::string(who) + ": H = " + std::to_string(H) + " gives " + std::to_string(ncoarse) +
                       " coarse columns; 1 to " + std::to_string(PA_COARSE_MAX_NODES) + " are served";

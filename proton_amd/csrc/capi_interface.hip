@@ -1,10 +1,12 @@
 // capi_interface.hip -- the C ABI of the two-sided interface problem: the cut cells' operators of both sides, the
-// interface_assembler's system as triplets and in CSR, condensed to the face unknowns, and by row slabs.
+// interface_assembler's system as triplets and in CSR, condensed to the face unknowns with its patch and coarse tables, and by
+// row slabs.
 #include <hip/hip_runtime.h>
 
 #include <string>
 #include <vector>
 
+#include "coarse_precond.hpp"
 #include "context.hpp"
 #include "cut_interface_device.hpp"
 
@@ -370,6 +372,38 @@ int pa_interface_condensed_patches(pa_context *ctx, int face_deg, int kind, int6
 {
     if (!ctx) return PA_ERR_INVALID_ARG;
     return if_patches(ctx, face_deg, kind, true, nullptr, nullptr, d_patch_ptr, d_patch_rows);
+}
+
+// the coarse table of the face-only system: the refusals of pa_interface_csr_* in its order, then H, the parts and the outputs
+// (with `write`), then the side stream joined; sized on the device, written only if the columns are within 1..PA_COARSE_MAX_NODES
+static int if_coarse(pa_context *ctx, const char *who, int face_deg, int H, int parts, bool write, size_t *ncoarse, size_t *entries,
+                     int64_t *d_p_ptr, int32_t *d_p_cols, double *d_p_vals)
+{
+    const int st = if_refusals(ctx, face_deg, true);
+    if (st != PA_OK) return st;
+    if (H < 1 || (parts != PA_COARSE_ONE && parts != PA_COARSE_BY_SIDE)) return PA_ERR_INVALID_ARG;
+    if (write ? (!d_p_ptr || !d_p_cols || !d_p_vals) : (!ncoarse || !entries)) return PA_ERR_INVALID_ARG;
+    if (!ctx->faces.structured || !ctx->faces.face_pts.get()) return PA_ERR_NO_MESH;       // (pa_cut_preprocess leaves both)
+    PA_HIP(ctx, join_side_stream(ctx));      // cut-cell work still out on the side stream
+    const pa::IfCoarseMesh m{ifcsr_mesh(ctx), ctx->faces.sm, ctx->faces.face_pts.get(), parts == PA_COARSE_BY_SIDE ? 1 : 0};
+    uint64_t nc = 0, ne = 0;
+    PA_HIP(ctx, pa::interface_condensed_coarse(ctx->stream, m, face_deg + 1, H, &nc, &ne, write ? d_p_ptr : nullptr, d_p_cols, d_p_vals));
+    if (nc < 1 || nc > (uint64_t)PA_COARSE_MAX_NODES) return coarse_count_refused(ctx, who, H, nc);
+    if (ncoarse) *ncoarse = (size_t)nc;
+    if (entries) *entries = (size_t)ne;
+    return PA_OK;
+}
+
+int pa_interface_condensed_coarse_query(pa_context *ctx, int face_deg, int H, int parts, size_t *ncoarse, size_t *entries)
+{
+    if (!ctx) return PA_ERR_INVALID_ARG;
+    return if_coarse(ctx, "pa_interface_condensed_coarse_query", face_deg, H, parts, false, ncoarse, entries, nullptr, nullptr, nullptr);
+}
+
+int pa_interface_condensed_coarse(pa_context *ctx, int face_deg, int H, int parts, int64_t *d_p_ptr, int32_t *d_p_cols, double *d_p_vals)
+{
+    if (!ctx) return PA_ERR_INVALID_ARG;
+    return if_coarse(ctx, "pa_interface_condensed_coarse", face_deg, H, parts, true, nullptr, nullptr, d_p_ptr, d_p_cols, d_p_vals);
 }
 
 // ---- the face-only system by row slabs (pa_interface_rows_*): a context of pa_cut_preprocess_rows, or of pa_cut_preprocess as

@@ -17,6 +17,9 @@
 //           block partials of r . z).  No dependent chain of length ncoarse, no floating-point atomics: the same bits on every call.
 //   solve:  conjugated_gradient_patch_coarse validates and factors both levels and hands patch_apply + coarse_apply to the one-rank
 //           loop of solver.hip.  No iteration of its own here.
+//   table:  the hats and the kernels that count, place and write them are stated once, for the numbering of pa_condensed_csr_pattern
+//           (a non-Dirichlet face owns one block) and for interface_assembler's (a cut face owns two: the solve of
+//           cuthho_square.cpp:1737-1743); a mesh type says what a face gives (face_blocks).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -556,22 +559,16 @@ __device__ __forceinline__ double cl_hat(int j, int i, int N, int H)
     return 0.0;
 }
 
-struct FaceHats { int n; int32_t node[4]; double v0[4], v1[4]; int part; int32_t q; };
+struct FaceHats { int n; int32_t node[4]; double v0[4], v1[4]; };
 
-// the interior nodes whose hat does not vanish at both ends of face f, in node order, with the values of the face's two lowest modes
-__device__ __forceinline__ FaceHats face_hats(const CoarseMesh &m, int H, uint32_t f)
+// the interior nodes whose hat does not vanish at both of the points pa, pb (a face's ends), in node order, with the values of the
+// face's two lowest modes
+__device__ __forceinline__ FaceHats point_hats(const StructuredMesh &sm, int H, uint32_t pa, uint32_t pb)
 {
     FaceHats o;
-    o.n = 0; o.part = 0;
-    o.q = m.face_compress[f];
-    if (o.q < 0) return o;
-    const int Nx = (int)m.sm.Nx, Ny = (int)m.sm.Ny, npr = Nx + 1;
-    const uint32_t pa = m.face_pts[2 * f], pb = m.face_pts[2 * f + 1];
+    o.n = 0;
+    const int Nx = (int)sm.Nx, Ny = (int)sm.Ny, npr = Nx + 1;
     const int ax = (int)(pa % npr), ay = (int)(pa / npr), bx = (int)(pb % npr), by = (int)(pb / npr);
-    if (m.face_loc != nullptr) {
-        const int loc = m.face_loc[f];
-        o.part = (loc != 2 && loc != m.where) ? 1 : 0;                 // 2: PA_LOC_ON_INTERFACE
-    }
     const int nlx = cl_lines(Nx, H), nly = cl_lines(Ny, H), nix = nlx - 2;
     const int x0 = (ax < bx ? ax : bx) / H, x1 = (ax < bx ? bx : ax) / H + 1;
     const int y0 = (ay < by ? ay : by) / H, y1 = (ay < by ? by : ay) / H + 1;
@@ -589,77 +586,142 @@ __device__ __forceinline__ FaceHats face_hats(const CoarseMesh &m, int H, uint32
     return o;
 }
 
-__device__ __forceinline__ uint32_t face_entries(const FaceHats &h, int fbs)
+// what face f gives: its hats, and the nb blocks that take them, each with its part; unowned: the block a face counted by the
+// numbering leaves without an owner (-1: none), whose pointers are still due
+struct FaceBlocks { FaceHats h; int nb; int32_t q[2]; int part[2]; int32_t unowned; };
+
+// the numbering of pa_condensed_csr_pattern: the one block of a non-Dirichlet face
+__device__ __forceinline__ FaceBlocks face_blocks(const CoarseMesh &m, int H, uint32_t f)
 {
-    uint32_t e = (uint32_t)h.n;
-    if (fbs >= 2)
-        for (int k = 0; k < h.n; ++k) e += h.v1[k] != 0.0 ? 1u : 0u;
-    return e;
+    FaceBlocks o;
+    o.h.n = 0; o.nb = 0; o.unowned = -1;
+    const int32_t q = m.face_compress[f];
+    if (q < 0) return o;
+    o.nb = 1; o.q[0] = q; o.part[0] = 0;
+    if (m.face_loc != nullptr) {
+        const int loc = m.face_loc[f];
+        o.part[0] = (loc != 2 && loc != m.where) ? 1 : 0;              // 2: PA_LOC_ON_INTERFACE
+    }
+    o.h = point_hats(m.sm, H, m.face_pts[2 * f], m.face_pts[2 * f + 1]);
+    return o;
 }
 
-}  // namespace
+// interface_assembler's numbering: the two blocks of a cut face take the same values (the face basis of a cut face is the whole
+// face's, cuthho_square.cpp:371, 471, 594).  A cut face on the Dirichlet boundary is counted and owns nothing: its block follows
+// the blocks of the nearest owning face below it and the unowned blocks between the two.
+__device__ __forceinline__ FaceBlocks face_blocks(const IfCoarseMesh &m, int H, uint32_t f)
+{
+    FaceBlocks o;
+    o.h.n = 0; o.nb = 0; o.unowned = -1;
+    const int32_t b = m.im.face_table[f];
+    const bool cut = m.im.face_loc[f] == IF_LOC_CUT;
+    if (b < 0) {
+        if (!cut) return o;
+        int32_t at = 0;
+        for (uint32_t g = f; g-- > 0;) {
+            const int32_t bg = m.im.face_table[g];
+            const bool cg = m.im.face_loc[g] == IF_LOC_CUT;
+            if (bg >= 0) { at += bg + (cg ? 2 : 1); break; }
+            at += cg ? 1 : 0;
+        }
+        o.unowned = at;
+        return o;
+    }
+    o.nb = cut ? 2 : 1;
+    o.q[0] = b; o.q[1] = b + 1;
+    o.part[0] = (m.by_side && !cut && m.im.face_loc[f] == 1) ? 1 : 0;  // 1: PA_LOC_POSITIVE
+    o.part[1] = m.by_side ? 1 : 0;
+    o.h = point_hats(m.sm, H, m.face_pts[2 * f], m.face_pts[2 * f + 1]);
+    return o;
+}
 
-// by side: used[part nnodes + node] = some face of the part meets the node's hat (every writer stores the same byte)
-__global__ __launch_bounds__(RB) void coarse_used_kernel(CoarseMesh m, int H, uint32_t nnodes, uint8_t *used)
+__device__ __forceinline__ uint32_t face_entries(const FaceBlocks &b, int fbs)
+{
+    uint32_t e = (uint32_t)b.h.n;
+    if (fbs >= 2)
+        for (int k = 0; k < b.h.n; ++k) e += b.h.v1[k] != 0.0 ? 1u : 0u;
+    return e * (uint32_t)b.nb;
+}
+
+inline uint32_t coarse_faces(const CoarseMesh &m) { return m.nfaces; }
+inline uint32_t coarse_faces(const IfCoarseMesh &m) { return m.im.nfaces; }
+inline uint64_t coarse_blocks(const CoarseMesh &m) { return sm_num_other_faces(m.sm); }
+inline uint64_t coarse_blocks(const IfCoarseMesh &m) { return m.im.num_other_faces; }
+inline bool coarse_by_side(const CoarseMesh &m) { return m.face_loc != nullptr; }
+inline bool coarse_by_side(const IfCoarseMesh &m) { return m.by_side != 0; }
+
+// by side: used[part nnodes + node] = some block of the part meets the node's hat (every writer stores the same byte)
+template <class Mesh>
+__global__ __launch_bounds__(RB) void coarse_used_kernel(Mesh m, uint32_t nfaces, int H, uint32_t nnodes, uint8_t *used)
 {
     const uint32_t f = blockIdx.x * RB + threadIdx.x;
-    if (f >= m.nfaces) return;
-    const FaceHats h = face_hats(m, H, f);
-    for (int k = 0; k < h.n; ++k) used[(size_t)h.part * nnodes + h.node[k]] = 1;
+    if (f >= nfaces) return;
+    const FaceBlocks b = face_blocks(m, H, f);
+    for (int s = 0; s < b.nb; ++s)
+        for (int k = 0; k < b.h.n; ++k) used[(size_t)b.part[s] * nnodes + b.h.node[k]] = 1;
 }
 
 // per block of faces: its entries
-__global__ __launch_bounds__(SCAN_BLOCK) void coarse_count_kernel(CoarseMesh m, int H, int fbs, uint32_t *blk)
+template <class Mesh>
+__global__ __launch_bounds__(SCAN_BLOCK) void coarse_count_kernel(Mesh m, uint32_t nfaces, int H, int fbs, uint32_t *blk)
 {
     __shared__ uint32_t sh[SCAN_BLOCK / 64];
     const uint32_t f = blockIdx.x * SCAN_BLOCK + threadIdx.x;
     uint32_t e = 0;
-    if (f < m.nfaces) e = face_entries(face_hats(m, H, f), fbs);
+    if (f < nfaces) e = face_entries(face_blocks(m, H, f), fbs);
     uint32_t total;
     block_exclusive_scan(e, sh, total);
     if (threadIdx.x == 0) blk[blockIdx.x] = total;
 }
 
-// blk scanned (the total at [nblk]): every non-Dirichlet face writes the pointers of its fbs rows and the entries of the first two;
-// column: the node's (index = null) or index[part nnodes + node]
-__global__ __launch_bounds__(SCAN_BLOCK) void coarse_fill_kernel(CoarseMesh m, int H, int fbs, uint32_t nnodes, const int32_t *index,
-                                                                 const uint32_t *blk, uint32_t nblk, uint64_t nrows, int64_t *ptr,
-                                                                 int32_t *cols, double *vals)
+// blk scanned (the total at [nblk]): every face writes, for each of its blocks, the pointers of the fbs rows and the entries of the
+// first two, and the pointers of a block it leaves unowned; column: the node's (index = null) or index[part nnodes + node]
+template <class Mesh>
+__global__ __launch_bounds__(SCAN_BLOCK) void coarse_fill_kernel(Mesh m, uint32_t nfaces, int H, int fbs, uint32_t nnodes,
+                                                                 const int32_t *index, const uint32_t *blk, uint32_t nblk, uint64_t nrows,
+                                                                 int64_t *ptr, int32_t *cols, double *vals)
 {
     __shared__ uint32_t sh[SCAN_BLOCK / 64];
     const uint32_t f = blockIdx.x * SCAN_BLOCK + threadIdx.x;
-    FaceHats h;
-    h.n = 0; h.q = -1; h.part = 0;
-    if (f < m.nfaces) h = face_hats(m, H, f);
-    const uint32_t e = face_entries(h, fbs);
+    FaceBlocks b;
+    b.h.n = 0; b.nb = 0; b.unowned = -1;
+    if (f < nfaces) b = face_blocks(m, H, f);
+    const uint32_t e = face_entries(b, fbs);
     uint32_t total;
     int64_t at = (int64_t)blk[blockIdx.x] + block_exclusive_scan(e, sh, total);
     if (f == 0) ptr[nrows] = (int64_t)blk[nblk];
-    if (h.q < 0) return;
-    const int64_t row0 = (int64_t)h.q * fbs;
-    ptr[row0] = at;
-    for (int k = 0; k < h.n; ++k) {
-        cols[at] = index != nullptr ? index[(size_t)h.part * nnodes + h.node[k]] : h.node[k];
-        vals[at] = h.v0[k];
-        ++at;
+    if (b.unowned >= 0)
+        for (int k = 0; k < fbs; ++k) ptr[(int64_t)b.unowned * fbs + k] = at;
+    for (int s = 0; s < b.nb; ++s) {
+        const int64_t row0 = (int64_t)b.q[s] * fbs;
+        const int32_t *col = index != nullptr ? index + (size_t)b.part[s] * nnodes : nullptr;
+        ptr[row0] = at;
+        for (int k = 0; k < b.h.n; ++k) {
+            cols[at] = col != nullptr ? col[b.h.node[k]] : b.h.node[k];
+            vals[at] = b.h.v0[k];
+            ++at;
+        }
+        if (fbs >= 2) {
+            ptr[row0 + 1] = at;
+            for (int k = 0; k < b.h.n; ++k)
+                if (b.h.v1[k] != 0.0) {
+                    cols[at] = col != nullptr ? col[b.h.node[k]] : b.h.node[k];
+                    vals[at] = b.h.v1[k];
+                    ++at;
+                }
+        }
+        for (int k = 2; k < fbs; ++k) ptr[row0 + k] = at;
     }
-    if (fbs >= 2) {
-        ptr[row0 + 1] = at;
-        for (int k = 0; k < h.n; ++k)
-            if (h.v1[k] != 0.0) {
-                cols[at] = index != nullptr ? index[(size_t)h.part * nnodes + h.node[k]] : h.node[k];
-                vals[at] = h.v1[k];
-                ++at;
-            }
-    }
-    for (int k = 2; k < fbs; ++k) ptr[row0 + k] = at;
 }
 
-hipError_t condensed_coarse(hipStream_t stream, const CoarseMesh &m, int fbs, int H, uint64_t *ncoarse, uint64_t *entries, int64_t *ptr,
-                            int32_t *cols, double *vals)
+// the table of either numbering: the columns (by side: the used ones, scanned), the entries (counted, scanned), the fill
+template <class Mesh>
+hipError_t coarse_table(hipStream_t stream, const Mesh &m, int fbs, int H, uint64_t *ncoarse, uint64_t *entries, int64_t *ptr,
+                        int32_t *cols, double *vals)
 {
     *ncoarse = 0;
     *entries = 0;
+    const uint32_t nfaces = coarse_faces(m);
     const uint64_t nix = (m.sm.Nx + (uint64_t)H - 1) / H, niy = (m.sm.Ny + (uint64_t)H - 1) / H;
     if (nix < 2 || niy < 2) return hipSuccess;                          // no interior line in some direction
     const uint64_t nn64 = (nix - 1) * (niy - 1);
@@ -667,7 +729,7 @@ hipError_t condensed_coarse(hipStream_t stream, const CoarseMesh &m, int fbs, in
     const uint32_t nnodes = (uint32_t)nn64;
     DeviceTmp tmp(stream);
     int32_t *index = nullptr;
-    if (m.face_loc == nullptr) {
+    if (!coarse_by_side(m)) {
         *ncoarse = nnodes;
     } else {
         const uint32_t items = 2 * nnodes, nb = (items + SCAN_TILE - 1) / SCAN_TILE;
@@ -677,7 +739,7 @@ hipError_t condensed_coarse(hipStream_t stream, const CoarseMesh &m, int fbs, in
         if (!tmp.alloc(&used, items) || !tmp.alloc(&counts, (size_t)nb + 1) || !tmp.alloc(&unused, items) || !tmp.alloc(&index, items))
             return tmp.error();
         if (!tmp.ok(hipMemsetAsync(used, 0, items, stream))) return tmp.error();
-        hipLaunchKernelGGL(coarse_used_kernel, dim3((m.nfaces + RB - 1) / RB), dim3(RB), 0, stream, m, H, nnodes, used);
+        hipLaunchKernelGGL((coarse_used_kernel<Mesh>), dim3((nfaces + RB - 1) / RB), dim3(RB), 0, stream, m, nfaces, H, nnodes, used);
         hipLaunchKernelGGL(active_count_kernel, dim3(nb), dim3(SCAN_BLOCK), 0, stream, used, items, counts);
         hipLaunchKernelGGL(active_block_scan_kernel, dim3(1), dim3(SCAN_BLOCK), 0, stream, counts, nb);
         hipLaunchKernelGGL(active_tables_kernel, dim3(nb), dim3(SCAN_BLOCK), 0, stream, used, items, counts, unused, index);
@@ -687,10 +749,10 @@ hipError_t condensed_coarse(hipStream_t stream, const CoarseMesh &m, int fbs, in
             return tmp.error();
         *ncoarse = total;
     }
-    const uint32_t nblk = (m.nfaces + SCAN_BLOCK - 1) / SCAN_BLOCK;
+    const uint32_t nblk = (nfaces + SCAN_BLOCK - 1) / SCAN_BLOCK;
     uint32_t *blk = nullptr;
     if (!tmp.alloc(&blk, (size_t)nblk + 1)) return tmp.error();
-    hipLaunchKernelGGL(coarse_count_kernel, dim3(nblk), dim3(SCAN_BLOCK), 0, stream, m, H, fbs, blk);
+    hipLaunchKernelGGL((coarse_count_kernel<Mesh>), dim3(nblk), dim3(SCAN_BLOCK), 0, stream, m, nfaces, H, fbs, blk);
     hipLaunchKernelGGL(active_block_scan_kernel, dim3(1), dim3(SCAN_BLOCK), 0, stream, blk, nblk);
     uint32_t total = 0;
     if (!tmp.ok(hipGetLastError()) || !tmp.ok(hipMemcpyAsync(&total, blk + nblk, sizeof(uint32_t), hipMemcpyDeviceToHost, stream)) ||
@@ -698,10 +760,25 @@ hipError_t condensed_coarse(hipStream_t stream, const CoarseMesh &m, int fbs, in
         return tmp.error();
     *entries = total;
     if (ptr == nullptr || *ncoarse < 1 || *ncoarse > (uint64_t)COARSE_MAX_NODES) return hipSuccess;
-    const uint64_t nrows = (uint64_t)sm_num_other_faces(m.sm) * fbs;
-    hipLaunchKernelGGL(coarse_fill_kernel, dim3(nblk), dim3(SCAN_BLOCK), 0, stream, m, H, fbs, nnodes, index, blk, nblk, nrows, ptr, cols, vals);
+    const uint64_t nrows = coarse_blocks(m) * fbs;
+    hipLaunchKernelGGL((coarse_fill_kernel<Mesh>), dim3(nblk), dim3(SCAN_BLOCK), 0, stream, m, nfaces, H, fbs, nnodes, index, blk, nblk, nrows, ptr,
+                       cols, vals);
     if (tmp.ok(hipGetLastError())) tmp.ok(hipStreamSynchronize(stream));       // the temporaries live until the kernel has read them
     return tmp.error();
+}
+
+}  // namespace
+
+hipError_t condensed_coarse(hipStream_t stream, const CoarseMesh &m, int fbs, int H, uint64_t *ncoarse, uint64_t *entries, int64_t *ptr,
+                            int32_t *cols, double *vals)
+{
+    return coarse_table(stream, m, fbs, H, ncoarse, entries, ptr, cols, vals);
+}
+
+hipError_t interface_condensed_coarse(hipStream_t stream, const IfCoarseMesh &m, int fbs, int H, uint64_t *ncoarse, uint64_t *entries,
+                                      int64_t *ptr, int32_t *cols, double *vals)
+{
+    return coarse_table(stream, m, fbs, H, ncoarse, entries, ptr, cols, vals);
 }
 
 }  // namespace pa

@@ -9,6 +9,7 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "interface_csr.hpp"
 #include "structured_mesh.hpp"
 
 namespace pa {
@@ -72,5 +73,18 @@ struct CoarseMesh {
 };
 hipError_t condensed_coarse(hipStream_t stream, const CoarseMesh &m, int fbs, int H, uint64_t *ncoarse, uint64_t *entries, int64_t *ptr,
                             int32_t *cols, double *vals);
+
+// ---- the same hats on the face-only system of pa_interface_condensed_csr_pattern (interface_assembler's numbering: im) ----
+// An uncut non-Dirichlet face owns block face_table[f], a cut one that block (negative side) and the next (positive side); both
+// take the values of the face's end points.  by_side: an uncut face's block is in the part of its side, a cut face's blocks in
+// parts 0 and 1.  A cut face on the Dirichlet boundary owns nothing: the pointers of its unowned block are written, equal.
+struct IfCoarseMesh {
+    IfCsrMesh im;
+    StructuredMesh sm;
+    const uint32_t *face_pts;
+    int by_side;
+};
+hipError_t interface_condensed_coarse(hipStream_t stream, const IfCoarseMesh &m, int fbs, int H, uint64_t *ncoarse, uint64_t *entries,
+                                      int64_t *ptr, int32_t *cols, double *vals);
 
 }  // namespace pa

@@ -476,13 +476,16 @@ class interface_assembler {
     // The same loop (:1664-1716) and its solve (:1737-1743) with the cell unknowns eliminated on the device: the operators as
     // assemble_all, the cells' static condensation (cut cells in double-double, pa_interface_condensed_ops_batch), the face-only
     // system directly in CSR (pa_interface_condensed_csr_*), pa_conjugated_gradient on it (patches = PA_PATCH_FACE / PA_PATCH_CELL:
-    // pa_conjugated_gradient_patch on the table of pa_interface_condensed_patches) and the cell unknowns recovered
-    // (pa_interface_condensed_recover).  Returns the full solution vector in the reference's numbering -- what
+    // pa_conjugated_gradient_patch on the table of pa_interface_condensed_patches; with coarse = H > 0 as well:
+    // pa_conjugated_gradient_patch_coarse with the table of pa_interface_condensed_coarse, coarse_parts = PA_COARSE_BY_SIDE or
+    // PA_COARSE_ONE) and the cell unknowns recovered (pa_interface_condensed_recover).  Returns the full solution vector in the reference's numbering -- what
     // conjugated_gradient(LHS, RHS, sol) leaves in `sol` -- for take_local_data; LHS / RHS are left untouched.
     std::vector<T> solve_condensed(const Mesh &msh, const params<T> &parms, int rhs_fn, int dirichlet_fn, const cg_params<T> &cgp,
-                                   size_t *iterations = nullptr, cg_exit_reason *exit_reason = nullptr, int patches = -1)
+                                   size_t *iterations = nullptr, cg_exit_reason *exit_reason = nullptr, int patches = -1, int coarse = 0,
+                                   int coarse_parts = PA_COARSE_BY_SIDE)
     {
         if (!msh.preprocessed) throw std::logic_error("cutHHO mesh not preprocessed");
+        if (coarse > 0 && patches < 0) throw std::invalid_argument("interface_assembler::solve_condensed: coarse needs patches");
         for (size_t c = 0; c < msh.cells.size(); ++c) {                                  // :1304-1305, as assemble_cut
             if (msh.cell_tags[c] != element_location::ON_INTERFACE) continue;
             for (auto f : proton_amd::face_offsets(msh, msh.cells[c]))
@@ -530,6 +533,21 @@ class interface_assembler {
             proton_amd::device_buffer<int64_t> d_pptr(npatches + 1);
             proton_amd::device_buffer<int32_t> d_prows(entries + 1);
             dev.check(pa_interface_condensed_patches(dev.ctx(), fd, patches, d_pptr.get(), d_prows.get()), "pa_interface_condensed_patches");
+            if (coarse > 0) {
+                // ... and the Galerkin coarse level: bilinear hats on every coarse-th mesh line, whole or split by side of the interface
+                size_t ncoarse = 0, centries = 0;
+                dev.check(pa_interface_condensed_coarse_query(dev.ctx(), fd, coarse, coarse_parts, &ncoarse, &centries),
+                          "pa_interface_condensed_coarse_query");
+                proton_amd::device_buffer<int64_t> d_cptr(nF + 1);
+                proton_amd::device_buffer<int32_t> d_ccols(centries + 1);
+                proton_amd::device_buffer<double> d_cvals(centries + 1);
+                dev.check(pa_interface_condensed_coarse(dev.ctx(), fd, coarse, coarse_parts, d_cptr.get(), d_ccols.get(), d_cvals.get()),
+                          "pa_interface_condensed_coarse");
+                dev.check(pa_conjugated_gradient_patch_coarse(dev.ctx(), nF, d_rowptr.get(), d_colind.get(), d_values.get(), d_b.get(), d_xF.get(),
+                                                              npatches, d_pptr.get(), d_prows.get(), ncoarse, d_cptr.get(), d_ccols.get(),
+                                                              d_cvals.get(), cgp.convergence_threshold, cgp.divergence_threshold, cgp.max_iter,
+                                                              &reason, &iters, &rr), "pa_conjugated_gradient_patch_coarse");
+            } else
             dev.check(pa_conjugated_gradient_patch(dev.ctx(), nF, d_rowptr.get(), d_colind.get(), d_values.get(), d_b.get(), d_xF.get(), npatches,
                                                    d_pptr.get(), d_prows.get(), cgp.convergence_threshold, cgp.divergence_threshold,
                                                    cgp.max_iter, &reason, &iters, &rr), "pa_conjugated_gradient_patch");
