@@ -1003,6 +1003,48 @@ int pa_copy_to_device(pa_context *ctx, void *d_dst, const void *host_src, size_t
 /* the RCCL transport of a communicator (user = the communicator) */
 int pa_comm_cg_transport(pa_comm *comm, pa_cg_transport *out);
 
+/* ---- the patches and the coarse level on the ROW-PARTITIONED system ------------------------------------------
+ * pa_conjugated_gradient_rows (solver_cg.hpp:45-144; the solve of cuthho_square.cpp:915-919 where it was assembled) with the
+ * preconditioner of pa_conjugated_gradient_patch_coarse, z = (patch sum) + (coarse term), in place of the point Jacobi: the
+ * arguments of pa_conjugated_gradient_rows without apply_preconditioner, plus two caller-owned device tables of THIS rank.
+ *   Patches: npatches, d_patch_ptr, d_patch_rows as pa_patch_precond_*, the rows GLOBAL indices, every one within [row_begin,
+ *   row_end), every owned row in at least one patch.  A patch's block then lies inside the rank's rows and their own columns:
+ *   the patch level needs no communication.
+ *   Coarse: ncoarse (the same on every rank; 0 = patches only, the three pointers may be NULL), and the rank's own rows of P:
+ *   d_p_ptr (row_end - row_begin + 1, from 0), d_p_cols (global coarse columns), d_p_vals, as pa_coarse_precond_*.
+ * Set-up: the rows of P for the two ends of the window travel through `halo` (8 doubles a row: four (column as double, value)
+ * pairs padded with column -1, so 8 x give sent and 8 x need received), W = A_r P_window, the rank's addend P_r^T W in the
+ * one-rank product's fixed order, the lower triangle of A_c through allreduce_sum (in pieces of at most 2^20 + 1 values) and
+ * mirrored -- exactly symmetric, the same bits on every rank --, and every rank factors it.
+ * Iteration: the recurrences, exit tests and exit order of pa_conjugated_gradient_patch_coarse with three sums over the ranks:
+ * d . y; the coarse restriction P_r^T r (ncoarse + 1 values); (r . r, r . z).  No floating-point atomics: two calls with the
+ * same inputs give the same bits.  With transport = NULL, row_begin = 0 and whole tables the call is
+ * pa_conjugated_gradient_patch_coarse bit for bit, with ncoarse = 0 pa_conjugated_gradient_patch.
+ * *transport_status as pa_conjugated_gradient_rows, and 5: a table of this rank was refused (PA_ERR_INVALID_ARG, text in
+ * pa_last_error), 6: a patch of this rank or the coarse matrix is not positive definite (PA_ERR_NOT_SPD; a pivot of A_c is the
+ * same on every rank, all report 6).  The other ranks leave with 3 and PA_ERR_COMM, all before the first iteration.  d_x is
+ * written only when the call returns PA_OK. */
+int pa_conjugated_gradient_rows_patch_coarse(pa_context *ctx, const pa_cg_transport *transport, int64_t row_begin, int64_t row_end,
+                                             const int64_t *d_rowptr, const int32_t *d_colind, const double *d_values, const double *d_b,
+                                             double *d_x, size_t npatches, const int64_t *d_patch_ptr, const int32_t *d_patch_rows,
+                                             size_t ncoarse, const int64_t *d_p_ptr, const int32_t *d_p_cols, const double *d_p_vals,
+                                             double convergence_threshold, double divergence_threshold, size_t max_iter,
+                                             int32_t *exit_reason, size_t *iterations, double *relative_residual, int32_t *transport_status);
+/* The tables of a slab for that call (assembler::assemble hho.hpp:344-406 numbers the faces; a context of pa_mesh_generate(..,
+ * row_begin, row_end), the whole mesh being the slab of all rows), built on the device from the mesh's closed forms.
+ *   Patches, rows as GLOBAL indices.  PA_PATCH_FACE: one patch per owned non-Dirichlet face.  PA_PATCH_CELL: one patch per cell of
+ *   the slab with an owned non-Dirichlet face, the rows of those faces in the order bottom, right, top, left; a cell of the top
+ *   row of a slab that is not the last loses its top face, which the slab above owns.  The face tables of the slabs, concatenated,
+ *   are pa_condensed_patches' of the whole mesh; the cell tables are its table with every row outside the patch's slab deleted.
+ *   Coarse (basic_mesh.hpp:230-298 gives the vertex indices the hats live on), PA_COARSE_ONE only: rows [row_begin, row_end) of
+ *   pa_condensed_coarse's whole-mesh table bit for bit, the same ncoarse and column ids, d_p_ptr rebased to 0.
+ * Not served: PA_COARSE_BY_SIDE (PA_ERR_INVALID_ARG), the slabs of the interface problem, the single-process C++ headers; the
+ * solver above takes any caller's table.  Other refusals as pa_condensed_patches / pa_condensed_coarse. */
+int pa_condensed_rows_patches_query(pa_context *ctx, pa_degree_info di, int kind, size_t *npatches, size_t *entries);
+int pa_condensed_rows_patches(pa_context *ctx, pa_degree_info di, int kind, int64_t *d_patch_ptr, int32_t *d_patch_rows);
+int pa_condensed_rows_coarse_query(pa_context *ctx, pa_degree_info di, int H, int parts, size_t *ncoarse, size_t *entries);
+int pa_condensed_rows_coarse(pa_context *ctx, pa_degree_info di, int H, int parts, int64_t *d_p_ptr, int32_t *d_p_cols, double *d_p_vals);
+
 /* occupancy / launch facts of the dominant kernel for the roofline bookkeeping */
 typedef struct {
     int32_t lanes_per_cell, cells_per_block, block_threads, lds_bytes_per_block;

@@ -364,6 +364,43 @@ class BatchAssembler:
             rows.data_ptr(), ncoarse, cptr.data_ptr(), ccols.data_ptr(), cvals.data_ptr(), tol, div, max_iter)
         return x, reason, iters, rr
 
+    # ---- both levels on the row-partitioned system (rows_precond.hip): the tables of this context's slab ----
+    def condensed_rows_patches(self, cd, fd, kind):
+        """condensed_patches for the rows this context's slab owns (generate_mesh(.., rows=..); a whole mesh is the slab of all
+        rows), the rows as global indices; a cell patch keeps the slab's own rows only -> (patch_ptr, patch_rows)"""
+        di, _ = capi.degree_info(cd, fd)
+        kind = {"face": capi.PATCH_FACE, "cell": capi.PATCH_CELL}.get(kind, kind)
+        npatches, entries = self.ctx.condensed_rows_patches_query(di, kind)
+        ptr = torch.empty(npatches + 1, dtype=torch.int64, device=self.device)
+        rows = torch.empty(max(entries, 1), dtype=torch.int32, device=self.device)
+        self.ctx.condensed_rows_patches(di, kind, ptr.data_ptr(), rows.data_ptr())
+        return ptr, rows[:entries]
+
+    def condensed_rows_coarse(self, cd, fd, H):
+        """rows [row_begin, row_end) of condensed_coarse(cd, fd, H, "one") of the whole mesh for this context's slab: the same
+        columns, p_ptr from 0 -> (p_ptr, p_cols, p_vals, ncoarse)"""
+        di, _ = capi.degree_info(cd, fd)
+        ncoarse, entries = self.ctx.condensed_rows_coarse_query(di, H, capi.COARSE_ONE)
+        info = self.condensed_info(cd, fd)
+        ptr = torch.empty(info.row_end - info.row_begin + 1, dtype=torch.int64, device=self.device)
+        cols = torch.empty(max(entries, 1), dtype=torch.int32, device=self.device)
+        vals = torch.empty(max(entries, 1), dtype=torch.float64, device=self.device)
+        self.ctx.condensed_rows_coarse(di, H, capi.COARSE_ONE, ptr.data_ptr(), cols.data_ptr(), vals.data_ptr())
+        return ptr, cols[:entries], vals[:entries], ncoarse
+
+    def conjugated_gradient_rows_patch_coarse(self, transport, row_begin, row_end, rowptr, colind, values, b, patches, coarse=None, tol=1e-9,
+                                              div=100.0, max_iter=1000, x=None):
+        """pa_conjugated_gradient_rows_patch_coarse on this rank's rows with its tables (condensed_rows_patches,
+        condensed_rows_coarse or None) -> (x, exit_reason, iterations, relative residual)"""
+        ptr, rows = patches
+        cptr, ccols, cvals, ncoarse = coarse if coarse is not None else (None, None, None, 0)
+        if x is None:
+            x = torch.zeros_like(b)
+        reason, iters, rr = self.ctx.conjugated_gradient_rows_patch_coarse(
+            transport, row_begin, row_end, rowptr.data_ptr(), colind.data_ptr(), values.data_ptr(), b.data_ptr(), x.data_ptr(),
+            ptr.numel() - 1, ptr.data_ptr(), rows.data_ptr(), ncoarse, _ptr(cptr), _ptr(ccols), _ptr(cvals), tol, div, max_iter)
+        return x, reason, iters, rr
+
     def condensed_solve(self, cd, fd, cond, g=None, tol=1e-9, div=100.0, max_iter=None, precond=True, patches=None, coarse=None):
         """the face-only system of the records `cond` (condensed_ops) assembled (condensed_csr_pattern / condensed_csr_fill) and
         solved: patches None = conjugated_gradient (precond: Jacobi), "face" / "cell" = conjugated_gradient_patch on that table;

@@ -53,6 +53,8 @@ EXPORTS = [
     "pa_interface_condensed_patches_query", "pa_interface_condensed_patches",
     "pa_coarse_precond_query", "pa_coarse_precond_factor", "pa_coarse_precond_apply", "pa_conjugated_gradient_patch_coarse",
     "pa_condensed_coarse_query", "pa_condensed_coarse",
+    "pa_conjugated_gradient_rows_patch_coarse", "pa_condensed_rows_patches_query", "pa_condensed_rows_patches",
+    "pa_condensed_rows_coarse_query", "pa_condensed_rows_coarse",
     "pa_interface_condensed_coarse_query", "pa_interface_condensed_coarse",
 ]
 
@@ -236,6 +238,13 @@ def lib():
                                                       C.POINTER(C.c_int32), C.POINTER(sz), C.POINTER(C.c_double)]
     L.pa_condensed_coarse_query.argtypes = [vp, DegreeInfo, C.c_int, C.c_int, C.c_int, C.POINTER(sz), C.POINTER(sz)]
     L.pa_condensed_coarse.argtypes = [vp, DegreeInfo, C.c_int, C.c_int, C.c_int, dp, dp, dp]
+    L.pa_conjugated_gradient_rows_patch_coarse.argtypes = [vp, C.POINTER(CgTransport), C.c_int64, C.c_int64, dp, dp, dp, dp, dp, sz, dp, dp, sz,
+                                                           dp, dp, dp, C.c_double, C.c_double, sz, C.POINTER(C.c_int32), C.POINTER(sz),
+                                                           C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+    L.pa_condensed_rows_patches_query.argtypes = [vp, DegreeInfo, C.c_int, C.POINTER(sz), C.POINTER(sz)]
+    L.pa_condensed_rows_patches.argtypes = [vp, DegreeInfo, C.c_int, dp, dp]
+    L.pa_condensed_rows_coarse_query.argtypes = [vp, DegreeInfo, C.c_int, C.c_int, C.POINTER(sz), C.POINTER(sz)]
+    L.pa_condensed_rows_coarse.argtypes = [vp, DegreeInfo, C.c_int, C.c_int, dp, dp, dp]
     L.pa_conjugated_gradient_rows.argtypes = [vp, C.POINTER(CgTransport), C.c_int64, C.c_int64, dp, dp, dp, dp, dp, C.c_double, C.c_double, sz,
                                               C.c_int, C.POINTER(C.c_int32), C.POINTER(sz), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
     L.pa_comm_cg_transport.argtypes = [vp, C.POINTER(CgTransport)]
@@ -621,6 +630,36 @@ class Context:
                                                      int(precond), C.byref(reason), C.byref(iters), C.byref(rr), C.byref(tstat)),
                  "pa_conjugated_gradient_rows (transport status %d)" % tstat.value)
         return reason.value, iters.value, rr.value
+
+    def conjugated_gradient_rows_patch_coarse(self, transport, row_begin, row_end, rowptr, colind, values, b, x, npatches, patch_ptr, patch_rows,
+                                              ncoarse=0, p_ptr=None, p_cols=None, p_vals=None, tol=1e-9, div=100.0, max_iter=1000):
+        """pa_conjugated_gradient_rows_patch_coarse; transport: a CgTransport (or None = one rank); the tables are this rank's (global
+        patch rows; ncoarse = 0: patches only).  Returns (reason, iterations, rr); x is written only then."""
+        reason, iters, rr, tstat = C.c_int32(0), C.c_size_t(0), C.c_double(0.0), C.c_int32(0)
+        tp = C.byref(transport) if transport is not None else None
+        self._ck(self._L.pa_conjugated_gradient_rows_patch_coarse(self.h, tp, row_begin, row_end, rowptr, colind, values, b, x, npatches,
+                                                                  patch_ptr, patch_rows, ncoarse, p_ptr, p_cols, p_vals, tol, div, max_iter,
+                                                                  C.byref(reason), C.byref(iters), C.byref(rr), C.byref(tstat)),
+                 "pa_conjugated_gradient_rows_patch_coarse (transport status %d)" % tstat.value)
+        return reason.value, iters.value, rr.value
+
+    def condensed_rows_patches_query(self, di, kind):
+        npatches, entries = C.c_size_t(0), C.c_size_t(0)
+        self._ck(self._L.pa_condensed_rows_patches_query(self.h, di, kind, C.byref(npatches), C.byref(entries)),
+                 "pa_condensed_rows_patches_query")
+        return npatches.value, entries.value
+
+    def condensed_rows_patches(self, di, kind, patch_ptr, patch_rows):
+        self._ck(self._L.pa_condensed_rows_patches(self.h, di, kind, patch_ptr, patch_rows), "pa_condensed_rows_patches")
+
+    def condensed_rows_coarse_query(self, di, H, parts):
+        ncoarse, entries = C.c_size_t(0), C.c_size_t(0)
+        self._ck(self._L.pa_condensed_rows_coarse_query(self.h, di, H, parts, C.byref(ncoarse), C.byref(entries)),
+                 "pa_condensed_rows_coarse_query")
+        return ncoarse.value, entries.value
+
+    def condensed_rows_coarse(self, di, H, parts, p_ptr, p_cols, p_vals):
+        self._ck(self._L.pa_condensed_rows_coarse(self.h, di, H, parts, p_ptr, p_cols, p_vals), "pa_condensed_rows_coarse")
 
     def take_local_data(self, di, first, n, solution, g, out):
         self._ck(self._L.pa_take_local_data_batch(self.h, di, first, n, solution, g, out), "pa_take_local_data_batch")

@@ -1,5 +1,6 @@
 // capi_assembly.hip -- the C ABI of the global systems of an uncut mesh: the assembler's triplets and local data, the energy form,
-// the condensed (face-only) system, the assembler's own system directly in CSR, triplets to CSR, the conjugate gradient, the patch preconditioner with its tables, and the Galerkin coarse level with its table.
+// the condensed (face-only) system, the assembler's own system directly in CSR, triplets to CSR, the conjugate gradient, the patch preconditioner with its tables, the Galerkin coarse level with its table, and
+// both on the row-partitioned system with the tables of a slab.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -11,6 +12,7 @@
 #include "device_tmp.hpp"
 #include "hho_assembly.hpp"
 #include "patch_precond.hpp"
+#include "rows_precond.hpp"
 #include "scan.hpp"
 
 int pa_triplets_batch(pa_context *ctx, pa_degree_info di, size_t first, size_t n, const double *d_lc,
@@ -544,7 +546,7 @@ int pa_condensed_patches(pa_context *ctx, pa_degree_info di, int kind, int64_t *
     if ((uint64_t)fbs * v.cell_faces_total >= ((uint64_t)1 << 31)) return PA_ERR_INVALID_ARG;      // int32 slots
     if (v.nown && !d_patch_rows) return PA_ERR_INVALID_ARG;
     if (kind == PA_PATCH_FACE) {
-        pa::face_patches(ctx->stream, v.nown, fbs, d_patch_ptr, d_patch_rows);
+        pa::face_patches(ctx->stream, v.nown, fbs, 0, d_patch_ptr, d_patch_rows);
         PA_HIP(ctx, hipGetLastError());
         return PA_OK;
     }
@@ -640,6 +642,116 @@ int pa_conjugated_gradient_patch_coarse(pa_context *ctx, size_t nrows, const int
     if (status == 4) { ctx->last_error = "pa_conjugated_gradient_patch_coarse: the coarse matrix is not positive definite (pivot " + std::to_string(pivot - 1) + ")"; return PA_ERR_NOT_SPD; }
     if (exit_reason) *exit_reason = reason;
     return PA_OK;
+}
+
+// ---- both levels on the row-partitioned system, and the tables of a slab: rows_precond.hip ---------------------------------------
+int pa_conjugated_gradient_rows_patch_coarse(pa_context *ctx, const pa_cg_transport *transport, int64_t row_begin, int64_t row_end,
+                                             const int64_t *d_rowptr, const int32_t *d_colind, const double *d_values, const double *d_b,
+                                             double *d_x, size_t npatches, const int64_t *d_patch_ptr, const int32_t *d_patch_rows,
+                                             size_t ncoarse, const int64_t *d_p_ptr, const int32_t *d_p_cols, const double *d_p_vals,
+                                             double convergence_threshold, double divergence_threshold, size_t max_iter,
+                                             int32_t *exit_reason, size_t *iterations, double *relative_residual, int32_t *transport_status)
+{
+    if (!ctx || !d_rowptr || row_end < row_begin || row_end >= ((int64_t)1 << 31)) return PA_ERR_INVALID_ARG;
+    if (row_end > row_begin && (!d_colind || !d_values || !d_b || !d_x || !d_patch_ptr || !d_patch_rows)) return PA_ERR_INVALID_ARG;
+    if (ncoarse && (!d_p_ptr || !d_p_cols || !d_p_vals)) return PA_ERR_INVALID_ARG;
+    if (transport && (!transport->allreduce_sum || !transport->halo || !transport->neighbour_counts)) return PA_ERR_INVALID_ARG;
+    PA_HIP(ctx, hipSetDevice(ctx->device));
+    pa::CgTransport tp{};
+    if (transport) { tp.user = transport->user; tp.allreduce_sum = transport->allreduce_sum; tp.halo = transport->halo; tp.neighbour_counts = transport->neighbour_counts; }
+    int reason = 0, tstat = 0;
+    pa::RowsPrecondReport rep;
+    const hipError_t he = pa::conjugated_gradient_rows_patch_coarse(ctx->stream, transport ? &tp : nullptr, row_begin, row_end, d_rowptr, d_colind,
+                                                                    d_values, d_b, d_x, npatches, d_patch_ptr, d_patch_rows, ncoarse, d_p_ptr,
+                                                                    d_p_cols, d_p_vals, convergence_threshold, divergence_threshold, max_iter,
+                                                                    &reason, iterations, relative_residual, &tstat, &rep);
+    if (exit_reason) *exit_reason = reason;
+    if (transport_status) *transport_status = tstat;
+    const char *who = "pa_conjugated_gradient_rows_patch_coarse";
+    if (he != hipSuccess) { ctx->last_error = std::string(who) + ": " + hipGetErrorString(he); return PA_ERR_HIP; }
+    if (tstat == 3) ctx->last_error = std::string(who) + ": another rank failed; every rank left the solve at the same reduction";
+    if (tstat == 5) return rep.level == 1 ? patch_refused(ctx, who, rep.refusal) : coarse_refused(ctx, who, rep.refusal);
+    if (tstat == 6) {
+        ctx->last_error = std::string(who) + (rep.level == 1 ? ": a patch matrix of this rank is not positive definite"
+                                                             : ": the coarse matrix is not positive definite (pivot " + std::to_string(rep.pivot - 1) + ")");
+        return PA_ERR_NOT_SPD;
+    }
+    return (tstat == 1 || tstat == 3) ? PA_ERR_COMM : (tstat == 2 ? PA_ERR_INVALID_ARG : PA_OK);
+}
+
+// a slab of the generator mesh and the compressed faces [p0, p1) it owns (cond_prepare); a whole mesh is the slab of all rows
+static int slab_of(pa_context *ctx, pa_degree_info di, const char *who, pa::StructuredMesh *sm, int32_t *p0, int32_t *p1)
+{
+    if (!degree_ok(di)) return PA_ERR_INVALID_ARG;
+    PA_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->faces.cell_faces.get()) return PA_ERR_NO_MESH;
+    if (!ctx->faces.structured) { ctx->last_error = std::string(who) + ": the mesh of pa_mesh_generate only"; return PA_ERR_INVALID_ARG; }
+    const int st = cond_prepare(ctx);
+    if (st != PA_OK) return st;
+    if ((uint64_t)(di.face_deg + 1) * ctx->faces.num_other_faces >= ((uint64_t)1 << 31)) return PA_ERR_INVALID_ARG;      // int32 rows
+    *sm = ctx->faces.sm; *p0 = ctx->cond.p0; *p1 = ctx->cond.p0 + (int32_t)ctx->cond.nown;
+    return PA_OK;
+}
+
+static int rows_patches(pa_context *ctx, pa_degree_info di, int kind, const char *who, size_t *npatches, size_t *entries, int64_t *d_patch_ptr,
+                        int32_t *d_patch_rows)
+{
+    if (kind != PA_PATCH_FACE && kind != PA_PATCH_CELL) return PA_ERR_INVALID_ARG;
+    pa::StructuredMesh sm;
+    int32_t p0 = 0, p1 = 0;
+    const int st = slab_of(ctx, di, who, &sm, &p0, &p1);
+    if (st != PA_OK) return st;
+    const int fbs = di.face_deg + 1;
+    uint64_t np = (uint64_t)(p1 - p0), ne = np * fbs;
+    if (kind == PA_PATCH_FACE) {
+        if (d_patch_ptr) {
+            pa::face_patches(ctx->stream, (uint32_t)np, fbs, p0 * fbs, d_patch_ptr, d_patch_rows);
+            PA_HIP(ctx, hipGetLastError());
+        }
+    } else PA_HIP(ctx, pa::slab_cell_patches(ctx->stream, sm, p0, p1, fbs, &np, &ne, d_patch_ptr, d_patch_rows));
+    if (npatches) *npatches = (size_t)np;
+    if (entries) *entries = (size_t)ne;
+    return PA_OK;
+}
+
+int pa_condensed_rows_patches_query(pa_context *ctx, pa_degree_info di, int kind, size_t *npatches, size_t *entries)
+{
+    if (!ctx || !npatches || !entries) return PA_ERR_INVALID_ARG;
+    return rows_patches(ctx, di, kind, "pa_condensed_rows_patches_query", npatches, entries, nullptr, nullptr);
+}
+
+int pa_condensed_rows_patches(pa_context *ctx, pa_degree_info di, int kind, int64_t *d_patch_ptr, int32_t *d_patch_rows)
+{
+    if (!ctx || !d_patch_ptr || !d_patch_rows) return PA_ERR_INVALID_ARG;
+    return rows_patches(ctx, di, kind, "pa_condensed_rows_patches", nullptr, nullptr, d_patch_ptr, d_patch_rows);
+}
+
+static int rows_coarse(pa_context *ctx, pa_degree_info di, int H, int parts, const char *who, size_t *ncoarse, size_t *entries,
+                       int64_t *d_p_ptr, int32_t *d_p_cols, double *d_p_vals)
+{
+    if (H < 1) return PA_ERR_INVALID_ARG;
+    if (parts != PA_COARSE_ONE) { ctx->last_error = std::string(who) + ": PA_COARSE_ONE only (the parts of a cut mesh are a whole-mesh table's)"; return PA_ERR_INVALID_ARG; }
+    pa::SlabCoarseMesh m;
+    const int st = slab_of(ctx, di, who, &m.sm, &m.p0, &m.p1);
+    if (st != PA_OK) return st;
+    uint64_t nc = 0, ne = 0;
+    PA_HIP(ctx, pa::condensed_rows_coarse(ctx->stream, m, di.face_deg + 1, H, &nc, &ne, d_p_ptr, d_p_cols, d_p_vals));
+    if (nc < 1 || nc > (uint64_t)PA_COARSE_MAX_NODES) return coarse_count_refused(ctx, who, H, nc);
+    if (ncoarse) *ncoarse = (size_t)nc;
+    if (entries) *entries = (size_t)ne;
+    return PA_OK;
+}
+
+int pa_condensed_rows_coarse_query(pa_context *ctx, pa_degree_info di, int H, int parts, size_t *ncoarse, size_t *entries)
+{
+    if (!ctx || !ncoarse || !entries) return PA_ERR_INVALID_ARG;
+    return rows_coarse(ctx, di, H, parts, "pa_condensed_rows_coarse_query", ncoarse, entries, nullptr, nullptr, nullptr);
+}
+
+int pa_condensed_rows_coarse(pa_context *ctx, pa_degree_info di, int H, int parts, int64_t *d_p_ptr, int32_t *d_p_cols, double *d_p_vals)
+{
+    if (!ctx || !d_p_ptr || !d_p_cols || !d_p_vals) return PA_ERR_INVALID_ARG;
+    return rows_coarse(ctx, di, H, parts, "pa_condensed_rows_coarse", nullptr, nullptr, d_p_ptr, d_p_cols, d_p_vals);
 }
 
 // the refusals of the two pa_condensed_coarse entries and the mesh they read

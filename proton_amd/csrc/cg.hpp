@@ -142,4 +142,40 @@ hipError_t conjugated_gradient_rows(hipStream_t stream, const CgTransport *tp, i
                                     double convergence_threshold, double divergence_threshold, size_t max_iter, int precond,
                                     int *exit_reason, size_t *iterations, double *relative_residual, int *transport_status);
 
+// ---- a preconditioner with an explicit z for the row-partitioned loop (rows_precond.hip states the one there is).
+// What a rank knows once the counts have been exchanged: its rows, and the window of columns they read.
+struct CgRowsSystem {
+    const CgTransport *tp;                 // null: one rank
+    int64_t row_begin, row_end, need_lo, need_hi, give_lo, give_hi;
+    const int64_t *rowptr;
+    const int32_t *colind;
+    const double *values;
+};
+// This rank's status (those of conjugated_gradient_rows, and 5: a table of this rank was refused, 6: a patch of this rank or the
+// coarse matrix is not positive definite), with the HIP error behind status 4.
+struct CgRowsFail {
+    int status = 0;
+    hipError_t herr = hipSuccess;
+    bool hip_ok(hipError_t e) { if (e != hipSuccess && !status) { status = 4; herr = e; } return e == hipSuccess; }
+};
+// prepare: the local part of the set-up (tables judged, patches factored), no collective inside; a failure goes to *fail.
+// setup:   the collective part, entered by every rank after all of them have prepared; -> 0, or the status every rank leaves with.
+// apply:   z = M^-1 r and the block partials of r . z; may sum over the ranks, the flag of *fail behind the sum; -> as setup.
+// z: n doubles of the caller's.
+struct CgRowsPreconditioner {
+    void *user;
+    void (*prepare)(void *user, hipStream_t stream, const CgRowsSystem &s, CgRowsFail *fail);
+    int (*setup)(void *user, hipStream_t stream, const CgRowsSystem &s, CgRowsFail *fail);
+    int (*apply)(void *user, hipStream_t stream, const CgRowsSystem &s, const double *r, double *z, double *part_rz, CgRowsFail *fail);
+    double *z;
+};
+// The loop of conjugated_gradient_rows with z from pre: the recurrences, exit tests and exit order of the one-rank loop with a
+// CgPreconditioner, three sums over the ranks per iteration (d . y, whatever pre->apply sums, (r . r, r . z)).  The iterate lives
+// in the workspace and reaches x only with status 0: on every other exit x is untouched.
+hipError_t conjugated_gradient_rows_stored(hipStream_t stream, const CgTransport *tp, int64_t row_begin, int64_t row_end,
+                                           const int64_t *rowptr, const int32_t *colind, const double *values,
+                                           const CgRowsPreconditioner *pre, const double *b, double *x, double convergence_threshold,
+                                           double divergence_threshold, size_t max_iter, int *exit_reason, size_t *iterations,
+                                           double *relative_residual, int *transport_status);
+
 }  // namespace pa

@@ -18,8 +18,13 @@
 //   solve:  conjugated_gradient_patch_coarse validates and factors both levels and hands patch_apply + coarse_apply to the one-rank
 //           loop of solver.hip.  No iteration of its own here.
 //   table:  the hats and the kernels that count, place and write them are stated once, for the numbering of pa_condensed_csr_pattern
-//           (a non-Dirichlet face owns one block) and for interface_assembler's (a cut face owns two: the solve of
-//           cuthho_square.cpp:1737-1743); a mesh type says what a face gives (face_blocks).
+//           (a non-Dirichlet face owns one block), for the rows of it that a slab of the generator mesh owns, and for
+//           interface_assembler's (a cut face owns two: the solve of cuthho_square.cpp:1737-1743); a mesh type says what a face gives
+//           (face_blocks).
+//   ranks:  for the row-partitioned solve (rows_precond.hip) the factor and the apply come in their stages: coarse_galerkin forms a
+//           rank's addend P_r^T (A_r P_window) of A_c with P given for the window of columns the rank's rows read (its ends packed,
+//           exchanged and unpacked here), the lower triangle travels packed, coarse_cholesky factors the sum; coarse_restrict and
+//           coarse_correct are the two halves of an apply, the sum of the restrictions over the ranks between them.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -174,10 +179,11 @@ __global__ __launch_bounds__(RB) void coarse_pt_rank_kernel(const uint32_t *pt_p
     }
 }
 
-// ---- W = A P: one thread per fine row, the slots in column order, every slot summed in the row's entry order -------------------------
+// ---- W = A P: one thread per fine row, the slots in column order, every slot summed in the row's entry order.  P is given for the
+// np rows from col0 on (the system itself: col0 = 0, np = n; a rank's rows: the window of columns they read) ---------------------------
 __global__ __launch_bounds__(RB) void coarse_w_kernel(size_t n, const int64_t *rowptr, const int32_t *colind, const double *values,
-                                                      const int64_t *ptr, const int32_t *cols, const double *vals, int32_t *wcount,
-                                                      int32_t *wcols, double *wvals, int32_t *flags)
+                                                      int64_t col0, size_t np, const int64_t *ptr, const int32_t *cols, const double *vals,
+                                                      int32_t *wcount, int32_t *wcols, double *wvals, int32_t *flags)
 {
     const size_t i = (size_t)blockIdx.x * RB + threadIdx.x;
     if (i >= n) return;
@@ -186,8 +192,8 @@ __global__ __launch_bounds__(RB) void coarse_w_kernel(size_t n, const int64_t *r
     int cnt = 0;
     bool over = false;
     for (int64_t e = rowptr[i]; e < rowptr[i + 1]; ++e) {
-        const int32_t c = colind[e];
-        if (c < 0 || (size_t)c >= n) continue;           // (not a column of the system: P has no row for it)
+        const int64_t c = (int64_t)colind[e] - col0;
+        if (c < 0 || (size_t)c >= np) continue;          // (not a column of the system: P has no row for it)
         const double a = values[e];
         for (int64_t q = ptr[c]; q < ptr[c + 1]; ++q) {
             const int32_t j = cols[q];
@@ -405,12 +411,10 @@ hipError_t coarse_validate(hipStream_t stream, const CoarseTable &t, const Coars
 }
 
 // (the counts of coarse_validate are still in the scratch: the two are called back to back)
-hipError_t coarse_factor(hipStream_t stream, const int64_t *rowptr, const int32_t *colind, const double *values, const CoarseTable &t,
-                         const CoarseSizes &sz, void *pt, double *factor, void *scratch, double *coarse_matrix, int32_t *pivot,
-                         int *refusal)
+hipError_t coarse_galerkin(hipStream_t stream, const int64_t *rowptr, const int32_t *colind, const double *values, const CoarseTable &t,
+                           const CoarseSizes &sz, const CoarseWindow *win, void *pt, void *scratch, int *refusal)
 {
     *refusal = COARSE_OK;
-    *pivot = 0;
     const uint32_t nc = (uint32_t)t.ncoarse;
     const Scratch s = scratch_parts(scratch, t.n, nc, (size_t)sz.entries, nullptr);
     const Transpose tr = pt_parts(pt, nc, (size_t)sz.entries, nullptr);
@@ -422,15 +426,31 @@ hipError_t coarse_factor(hipStream_t stream, const int64_t *rowptr, const int32_
     if (t.n) hipLaunchKernelGGL(coarse_pt_fill_kernel, dim3(gr), dim3(RB), 0, stream, t.n, t.ptr, t.cols, t.vals, s.cursor, s.trow, s.tval);
     hipLaunchKernelGGL(coarse_pt_rank_kernel, dim3(nc), dim3(RB), 0, stream, tr.ptr, s.trow, s.tval, tr.rows, tr.vals);
     // W = A P, A_c = P^T W
-    if (t.n)
-        hipLaunchKernelGGL(coarse_w_kernel, dim3(gr), dim3(RB), 0, stream, t.n, rowptr, colind, values, t.ptr, t.cols, t.vals, s.wcount, s.wcols,
-                           s.wvals, s.flags);
+    if (t.n) {
+        if (win != nullptr)
+            hipLaunchKernelGGL(coarse_w_kernel, dim3(gr), dim3(RB), 0, stream, t.n, rowptr, colind, values, win->col0, win->rows, win->ptr,
+                               win->cols, win->vals, s.wcount, s.wcols, s.wvals, s.flags);
+        else
+            hipLaunchKernelGGL(coarse_w_kernel, dim3(gr), dim3(RB), 0, stream, t.n, rowptr, colind, values, (int64_t)0, t.n, t.ptr, t.cols,
+                               t.vals, s.wcount, s.wcols, s.wvals, s.flags);
+    }
     hipError_t e = hipMemcpyAsync(h, s.flags, NFLAGS * 4, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e == hipSuccess) e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (h[FLAG_REFUSAL]) { *refusal = h[FLAG_REFUSAL]; return hipSuccess; }
     hipLaunchKernelGGL(coarse_galerkin_kernel, dim3(nc), dim3(RB), 0, stream, nc, tr.ptr, tr.rows, tr.vals, s.wcount, s.wcols, s.wvals, s.G);
+    return hipGetLastError();
+}
+
+hipError_t coarse_cholesky(hipStream_t stream, const CoarseTable &t, const CoarseSizes &sz, double *factor, void *scratch,
+                           double *coarse_matrix, int32_t *pivot)
+{
+    *pivot = 0;
+    const uint32_t nc = (uint32_t)t.ncoarse;
+    const Scratch s = scratch_parts(scratch, t.n, nc, (size_t)sz.entries, nullptr);
+    int32_t h[NFLAGS] = {0, 0, 0, 0};
+    hipError_t e = hipSuccess;
     if (coarse_matrix != nullptr) {
         e = hipMemcpyAsync(coarse_matrix, s.G, (size_t)nc * nc * 8, hipMemcpyDeviceToDevice, stream);
         if (e != hipSuccess) return e;
@@ -447,15 +467,135 @@ hipError_t coarse_factor(hipStream_t stream, const int64_t *rowptr, const int32_
     return hipSuccess;
 }
 
+hipError_t coarse_factor(hipStream_t stream, const int64_t *rowptr, const int32_t *colind, const double *values, const CoarseTable &t,
+                         const CoarseSizes &sz, void *pt, double *factor, void *scratch, double *coarse_matrix, int32_t *pivot,
+                         int *refusal)
+{
+    *pivot = 0;
+    const hipError_t e = coarse_galerkin(stream, rowptr, colind, values, t, sz, nullptr, pt, scratch, refusal);
+    if (e != hipSuccess || *refusal) return e;
+    return coarse_cholesky(stream, t, sz, factor, scratch, coarse_matrix, pivot);
+}
+
+// ---- the rows of P beyond a rank's own: what the window of columns its rows read takes from the two neighbouring ranks.  A row
+// travels as 8 doubles, four (column as double, value) pairs, padded with column -1 --------------------------------------------------
+__global__ __launch_bounds__(RB) void coarse_rows_pack_kernel(size_t first, size_t count, const int64_t *ptr, const int32_t *cols,
+                                                              const double *vals, double *out)
+{
+    const size_t i = (size_t)blockIdx.x * RB + threadIdx.x;
+    if (i >= count) return;
+    const int64_t p0 = ptr[first + i];
+    const int m = (int)(ptr[first + i + 1] - p0);
+    for (int k = 0; k < COARSE_MAX_ROW_ENTRIES; ++k) {
+        out[8 * i + 2 * k] = k < m ? (double)cols[p0 + k] : -1.0;
+        out[8 * i + 2 * k + 1] = k < m ? vals[p0 + k] : 0.0;
+    }
+}
+
+// the entries of a packed row: up to the first pair whose column is no column of the table (the padding; bytes nobody wrote)
+__device__ __forceinline__ uint32_t packed_row_entries(const double *row, uint32_t nc)
+{
+    uint32_t m = 0;
+    while (m < (uint32_t)COARSE_MAX_ROW_ENTRIES && row[2 * m] >= 0.0 && row[2 * m] < (double)nc) ++m;
+    return m;
+}
+
+// one block: the pointers and entries of the ghost rows on both sides of the n own rows, whose `entries` entries lie between them
+__global__ __launch_bounds__(SCAN_BLOCK) void coarse_window_ghosts_kernel(uint32_t nc, size_t n, uint32_t entries, size_t need_lo,
+                                                                          size_t need_hi, const double *recv_lo, const double *recv_hi,
+                                                                          int64_t *wptr, int32_t *wcols, double *wvals)
+{
+    __shared__ uint32_t sh[SCAN_BLOCK / 64];
+    uint32_t carry = 0;
+    for (int side = 0; side < 2; ++side) {
+        const size_t count = side ? need_hi : need_lo, row0 = side ? need_lo + n : 0;
+        const double *recv = side ? recv_hi : recv_lo;
+        for (size_t b0 = 0; b0 < count; b0 += SCAN_BLOCK) {
+            const size_t i = b0 + threadIdx.x;
+            const uint32_t m = i < count ? packed_row_entries(recv + 8 * i, nc) : 0u;
+            uint32_t total;
+            const uint32_t at = carry + block_exclusive_scan(m, sh, total);
+            if (i < count) {
+                wptr[row0 + i] = at;
+                for (uint32_t k = 0; k < m; ++k) { wcols[at + k] = (int32_t)recv[8 * i + 2 * k]; wvals[at + k] = recv[8 * i + 2 * k + 1]; }
+            }
+            carry += total;
+        }
+        if (threadIdx.x == 0) wptr[row0 + count] = carry;      // (below: where the own rows start; above: the end of the window)
+        carry += side ? 0u : entries;
+    }
+}
+
+// the own rows between the ghosts: pointers moved by the entries of the ghosts below, entries copied
+__global__ __launch_bounds__(RB) void coarse_window_own_kernel(size_t n, uint32_t entries, size_t need_lo, const int64_t *ptr,
+                                                               const int32_t *cols, const double *vals, int64_t *wptr, int32_t *wcols,
+                                                               double *wvals)
+{
+    const size_t i = (size_t)blockIdx.x * RB + threadIdx.x;
+    const int64_t base = wptr[need_lo];
+    if (i >= 1 && i < n) wptr[need_lo + i] = base + ptr[i];
+    if (i < entries) { wcols[base + i] = cols[i]; wvals[base + i] = vals[i]; }
+}
+
+void coarse_rows_pack(hipStream_t stream, const CoarseTable &t, size_t first, size_t count, double *out)
+{
+    if (count) hipLaunchKernelGGL(coarse_rows_pack_kernel, dim3(cg_vector_grid(count)), dim3(RB), 0, stream, first, count, t.ptr, t.cols, t.vals, out);
+}
+
+void coarse_window_build(hipStream_t stream, const CoarseTable &t, const CoarseSizes &sz, size_t need_lo, size_t need_hi,
+                         const double *recv_lo, const double *recv_hi, int64_t *wptr, int32_t *wcols, double *wvals)
+{
+    const uint32_t entries = (uint32_t)sz.entries;
+    hipLaunchKernelGGL(coarse_window_ghosts_kernel, dim3(1), dim3(SCAN_BLOCK), 0, stream, (uint32_t)t.ncoarse, t.n, entries, need_lo, need_hi,
+                       recv_lo, recv_hi, wptr, wcols, wvals);
+    const size_t items = t.n > (size_t)entries ? t.n : (size_t)entries;
+    if (items)
+        hipLaunchKernelGGL(coarse_window_own_kernel, dim3(cg_vector_grid(items)), dim3(RB), 0, stream, t.n, entries, need_lo, t.ptr, t.cols,
+                           t.vals, wptr, wcols, wvals);
+}
+
+// ---- the lower triangle of A_c as the ranks add it: packed row by row (row i at i (i + 1) / 2), and back into both halves of G ------
+__global__ __launch_bounds__(RB) void coarse_triangle_kernel(uint32_t nc, int unpack, double *G, double *tri)
+{
+    const size_t q = (size_t)blockIdx.x * RB + threadIdx.x;
+    if (q >= (size_t)nc * nc) return;
+    const uint32_t i = (uint32_t)(q / nc), j = (uint32_t)(q % nc);
+    if (j > i) return;
+    const size_t at = (size_t)i * (i + 1) / 2 + j;
+    if (unpack) { const double v = tri[at]; G[(size_t)i * nc + j] = v; G[(size_t)j * nc + i] = v; }
+    else tri[at] = G[q];
+}
+
+void coarse_matrix_triangle(hipStream_t stream, const CoarseTable &t, const CoarseSizes &sz, void *scratch, int unpack, double *tri)
+{
+    const uint32_t nc = (uint32_t)t.ncoarse;
+    const Scratch s = scratch_parts(scratch, t.n, nc, (size_t)sz.entries, nullptr);
+    hipLaunchKernelGGL(coarse_triangle_kernel, dim3(cg_vector_grid((size_t)nc * nc)), dim3(RB), 0, stream, nc, unpack, s.G, tri);
+}
+
 void coarse_apply(hipStream_t stream, const CoarseTable &t, const CoarseSizes &sz, const void *pt, const double *factor, void *scratch,
                   int accumulate, const double *r, double *z, double *part_rz)
 {
     if (t.n == 0) return;
+    coarse_restrict(stream, t, sz, pt, scratch, r);
+    coarse_correct(stream, t, sz, factor, scratch, accumulate, r, z, part_rz);
+}
+
+double *coarse_restrict(hipStream_t stream, const CoarseTable &t, const CoarseSizes &sz, const void *pt, void *scratch, const double *r)
+{
     const uint32_t nc = (uint32_t)t.ncoarse;
     const Scratch s = scratch_parts(scratch, t.n, nc, (size_t)sz.entries, nullptr);
     const Transpose tr = pt_parts(pt, nc, (size_t)sz.entries, nullptr);
+    hipLaunchKernelGGL(coarse_restrict_kernel, dim3(nc), dim3(RB), 0, stream, tr.ptr, tr.rows, tr.vals, r, s.vec);
+    return s.vec;
+}
+
+void coarse_correct(hipStream_t stream, const CoarseTable &t, const CoarseSizes &sz, const double *factor, void *scratch, int accumulate,
+                    const double *r, double *z, double *part_rz)
+{
+    const uint32_t nc = (uint32_t)t.ncoarse;
+    const Scratch s = scratch_parts(scratch, t.n, nc, (size_t)sz.entries, nullptr);
     double *rc = s.vec, *tt = s.vec + nc, *u = s.vec + 2 * (size_t)nc;
-    hipLaunchKernelGGL(coarse_restrict_kernel, dim3(nc), dim3(RB), 0, stream, tr.ptr, tr.rows, tr.vals, r, rc);
     hipLaunchKernelGGL(coarse_lower_kernel, dim3((nc + RB / 64 - 1) / (RB / 64)), dim3(RB), 0, stream, nc, factor, rc, tt);
     hipLaunchKernelGGL(coarse_upper_kernel, dim3((nc + 63) / 64), dim3(RB), 0, stream, nc, factor, tt, u);
     hipLaunchKernelGGL(coarse_prolong_kernel, dim3(cg_vector_grid(t.n)), dim3(RB), 0, stream, t.n, t.ptr, t.cols, t.vals, u, accumulate, r, z,
@@ -635,6 +775,22 @@ __device__ __forceinline__ FaceBlocks face_blocks(const IfCoarseMesh &m, int H, 
     return o;
 }
 
+// a slab of the generator mesh in closed form (structured_mesh.hpp): local face f is global face sm_face_base + f, and the slab owns
+// the compressed faces [p0, p1), block q - p0 of its rows
+__device__ __forceinline__ FaceBlocks face_blocks(const SlabCoarseMesh &m, int H, uint32_t f)
+{
+    FaceBlocks o;
+    o.h.n = 0; o.nb = 0; o.unowned = -1;
+    uint32_t lo, hi;
+    bool dirichlet;
+    int32_t q;
+    sm_face_decode(m.sm, sm_face_base(m.sm) + f, lo, hi, dirichlet, q);
+    if (dirichlet || q < m.p0 || q >= m.p1) return o;
+    o.nb = 1; o.q[0] = q - m.p0; o.part[0] = 0;
+    o.h = point_hats(m.sm, H, lo, hi);
+    return o;
+}
+
 __device__ __forceinline__ uint32_t face_entries(const FaceBlocks &b, int fbs)
 {
     uint32_t e = (uint32_t)b.h.n;
@@ -645,10 +801,13 @@ __device__ __forceinline__ uint32_t face_entries(const FaceBlocks &b, int fbs)
 
 inline uint32_t coarse_faces(const CoarseMesh &m) { return m.nfaces; }
 inline uint32_t coarse_faces(const IfCoarseMesh &m) { return m.im.nfaces; }
+inline uint32_t coarse_faces(const SlabCoarseMesh &m) { return (m.sm.row1 - m.sm.row0) * sm_face_row(m.sm); }
 inline uint64_t coarse_blocks(const CoarseMesh &m) { return sm_num_other_faces(m.sm); }
 inline uint64_t coarse_blocks(const IfCoarseMesh &m) { return m.im.num_other_faces; }
+inline uint64_t coarse_blocks(const SlabCoarseMesh &m) { return (uint64_t)(m.p1 - m.p0); }
 inline bool coarse_by_side(const CoarseMesh &m) { return m.face_loc != nullptr; }
 inline bool coarse_by_side(const IfCoarseMesh &m) { return m.by_side != 0; }
+inline bool coarse_by_side(const SlabCoarseMesh &) { return false; }
 
 // by side: used[part nnodes + node] = some block of the part meets the node's hat (every writer stores the same byte)
 template <class Mesh>
@@ -771,6 +930,12 @@ hipError_t coarse_table(hipStream_t stream, const Mesh &m, int fbs, int H, uint6
 
 hipError_t condensed_coarse(hipStream_t stream, const CoarseMesh &m, int fbs, int H, uint64_t *ncoarse, uint64_t *entries, int64_t *ptr,
                             int32_t *cols, double *vals)
+{
+    return coarse_table(stream, m, fbs, H, ncoarse, entries, ptr, cols, vals);
+}
+
+hipError_t condensed_rows_coarse(hipStream_t stream, const SlabCoarseMesh &m, int fbs, int H, uint64_t *ncoarse, uint64_t *entries,
+                                 int64_t *ptr, int32_t *cols, double *vals)
 {
     return coarse_table(stream, m, fbs, H, ncoarse, entries, ptr, cols, vals);
 }

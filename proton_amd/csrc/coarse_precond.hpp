@@ -51,6 +51,37 @@ hipError_t coarse_factor(hipStream_t stream, const int64_t *rowptr, const int32_
 void coarse_apply(hipStream_t stream, const CoarseTable &t, const CoarseSizes &sz, const void *pt, const double *factor, void *scratch,
                   int accumulate, const double *r, double *z, double *part_rz);
 
+// ---- the same in stages, for a table that holds the rows [row0, row0 + n) of P on one rank of a row-partitioned system ----
+// P for the `rows` rows from global row col0 on: the columns a rank's matrix rows read (its own rows and the ends of its neighbours')
+struct CoarseWindow {
+    int64_t col0;
+    size_t rows;
+    const int64_t *ptr;                    // rows + 1
+    const int32_t *cols;
+    const double *vals;
+};
+// coarse_factor up to the coarse matrix: P^T of the table's rows, W = A P with P from win (null: the table itself), and this
+// table's addend P^T W in the scratch, both triangles.  After coarse_validate.  Waits for the stream before the last kernel.
+hipError_t coarse_galerkin(hipStream_t stream, const int64_t *rowptr, const int32_t *colind, const double *values, const CoarseTable &t,
+                           const CoarseSizes &sz, const CoarseWindow *win, void *pt, void *scratch, int *refusal);
+// the coarse matrix in the scratch: its lower triangle packed row by row into tri (ncoarse (ncoarse + 1) / 2 doubles), or (unpack)
+// from tri into both triangles
+void coarse_matrix_triangle(hipStream_t stream, const CoarseTable &t, const CoarseSizes &sz, void *scratch, int unpack, double *tri);
+// the rest of coarse_factor: Cholesky of the coarse matrix in the scratch and the packed L^-1.  Waits.
+hipError_t coarse_cholesky(hipStream_t stream, const CoarseTable &t, const CoarseSizes &sz, double *factor, void *scratch,
+                           double *coarse_matrix, int32_t *pivot);
+// the two halves of coarse_apply: -> P^T r of the table's rows (ncoarse doubles in the scratch, the caller may add the other
+// ranks' to them in place), and the rest from those
+double *coarse_restrict(hipStream_t stream, const CoarseTable &t, const CoarseSizes &sz, const void *pt, void *scratch, const double *r);
+void coarse_correct(hipStream_t stream, const CoarseTable &t, const CoarseSizes &sz, const double *factor, void *scratch, int accumulate,
+                    const double *r, double *z, double *part_rz);
+// rows [first, first + count) of the table as 8 doubles each: four (column as double, value) pairs, padded with column -1
+void coarse_rows_pack(hipStream_t stream, const CoarseTable &t, size_t first, size_t count, double *out);
+// P for the window: need_lo packed rows below the table's own, need_hi above (a row ends at the first pair whose column is no
+// column of the table); wptr: need_lo + n + need_hi + 1, wcols / wvals: entries + 4 (need_lo + need_hi)
+void coarse_window_build(hipStream_t stream, const CoarseTable &t, const CoarseSizes &sz, size_t need_lo, size_t need_hi,
+                         const double *recv_lo, const double *recv_hi, int64_t *wptr, int32_t *wcols, double *wvals);
+
 // status: 0 solved (see exit_reason), 1 patch table refused, 2 a patch is not positive definite, 3 coarse table refused
 // (*refusal: its code), 4 the coarse matrix is not positive definite (*pivot); x is written only with 0
 hipError_t conjugated_gradient_patch_coarse(hipStream_t stream, size_t n, const int64_t *rowptr, const int32_t *colind,
@@ -73,6 +104,15 @@ struct CoarseMesh {
 };
 hipError_t condensed_coarse(hipStream_t stream, const CoarseMesh &m, int fbs, int H, uint64_t *ncoarse, uint64_t *entries, int64_t *ptr,
                             int32_t *cols, double *vals);
+
+// ---- rows [row_begin, row_end) of that table for a slab of the generator mesh, from the closed forms of structured_mesh.hpp: the
+// slab owns the compressed faces [p0, p1); the columns are the whole mesh's, ptr starts at 0 ----
+struct SlabCoarseMesh {
+    StructuredMesh sm;
+    int32_t p0, p1;
+};
+hipError_t condensed_rows_coarse(hipStream_t stream, const SlabCoarseMesh &m, int fbs, int H, uint64_t *ncoarse, uint64_t *entries,
+                                 int64_t *ptr, int32_t *cols, double *vals);
 
 // ---- the same hats on the face-only system of pa_interface_condensed_csr_pattern (interface_assembler's numbering: im) ----
 // An uncut non-Dirichlet face owns block face_table[f], a cut one that block (negative side) and the next (positive side); both

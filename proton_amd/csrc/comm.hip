@@ -78,7 +78,8 @@ struct pa_comm {
     hipStream_t side = nullptr;        // the collectives' own stream, so that they overlap kernels enqueued after them
     hipEvent_t ready = nullptr, done = nullptr;
     bool pending = false;
-    double *scratch = nullptr;         // 8 doubles on the device: the scalars of a distributed solve (pa_comm_cg_transport)
+    double *scratch = nullptr;         // on the device: what a distributed solve sums over the ranks (pa_comm_cg_transport); grows
+    size_t scratch_doubles = 0;
     std::string last_error;
 };
 
@@ -231,19 +232,25 @@ int pa_comm_neighbour_exchange_start(pa_comm *c, const double *d_send_lo, size_t
 }
 
 // ---- the transport of pa_conjugated_gradient_rows over this communicator (user = the communicator) ----
-static int cgt_scratch(pa_comm *c, double **d)
+static int cgt_scratch(pa_comm *c, size_t count, double **d)
 {
-    if (!c->scratch) PA_CHIP(c, hipMalloc((void **)&c->scratch, 8 * sizeof(double)));
+    if (c->scratch_doubles < count) {              // (nothing of an earlier call is pending: every callback waits before it returns)
+        const size_t want = count < 8 ? 8 : count;
+        if (c->scratch) PA_CHIP(c, hipFree(c->scratch));
+        c->scratch = nullptr; c->scratch_doubles = 0;
+        PA_CHIP(c, hipMalloc((void **)&c->scratch, want * sizeof(double)));
+        c->scratch_doubles = want;
+    }
     *d = c->scratch;
     return PA_OK;
 }
 static int cgt_allreduce(void *user, double *vals, int n)
 {
     pa_comm *c = (pa_comm *)user;
-    if (n > 8) return 1;
+    if (n < 0) return 1;
     if (c->nranks == 1) return 0;
     double *d = nullptr;
-    if (cgt_scratch(c, &d) != PA_OK) return 1;
+    if (cgt_scratch(c, (size_t)n, &d) != PA_OK) return 1;
     if (hipMemcpyAsync(d, vals, n * sizeof(double), hipMemcpyHostToDevice, c->main) != hipSuccess) return 1;
     if (pa_comm_allreduce_sum_start(c, d, (size_t)n) != PA_OK || pa_comm_wait(c) != PA_OK) return 1;
     if (hipMemcpyAsync(vals, d, n * sizeof(double), hipMemcpyDeviceToHost, c->main) != hipSuccess) return 1;
@@ -264,7 +271,7 @@ static int cgt_counts(void *user, int64_t need_lo, int64_t need_hi, int64_t *giv
     *give_lo = *give_hi = 0;
     if (c->nranks == 1) return 0;
     double *d = nullptr;
-    if (cgt_scratch(c, &d) != PA_OK) return 1;
+    if (cgt_scratch(c, 4, &d) != PA_OK) return 1;
     double h[4] = {(double)need_lo, (double)need_hi, 0.0, 0.0};
     if (hipMemcpyAsync(d, h, sizeof(h), hipMemcpyHostToDevice, c->main) != hipSuccess) return 1;
     if (pa_comm_neighbour_exchange_start(c, d, 1, d + 1, 1, d + 2, 1, d + 3, 1) != PA_OK || pa_comm_wait(c) != PA_OK) return 1;

@@ -25,6 +25,7 @@
 #include "interface_csr.hpp"
 #include "patch_precond.hpp"
 #include "scan.hpp"
+#include "structured_mesh.hpp"
 
 namespace pa {
 
@@ -84,18 +85,18 @@ __global__ __launch_bounds__(RB) void patch_ptr_check_kernel(size_t npatches, co
 }
 
 // the rows of every patch (ptr has passed): in range, no repeats; counts[row] = patches that hold it
-__global__ __launch_bounds__(RB) void patch_rows_check_kernel(size_t n, size_t npatches, const int64_t *ptr, const int32_t *rows,
-                                                              uint32_t *counts, int32_t *flags)
+__global__ __launch_bounds__(RB) void patch_rows_check_kernel(size_t n, int64_t row0, size_t npatches, const int64_t *ptr,
+                                                              const int32_t *rows, uint32_t *counts, int32_t *flags)
 {
     const size_t p = (size_t)blockIdx.x * RB + threadIdx.x;
     if (p >= npatches) return;
     const int64_t p0 = ptr[p];
     const int m = (int)(ptr[p + 1] - p0);
     for (int l = 0; l < m; ++l) {
-        const int32_t row = rows[p0 + l];
+        const int64_t row = (int64_t)rows[p0 + l] - row0;
         if (row < 0 || (size_t)row >= n) { atomicMax(&flags[FLAG_REFUSAL], (int32_t)PATCH_BAD_INDEX); continue; }
         bool repeated = false;
-        for (int q = 0; q < l; ++q) repeated |= rows[p0 + q] == row;
+        for (int q = 0; q < l; ++q) repeated |= rows[p0 + q] == rows[p0 + l];
         if (repeated) atomicMax(&flags[FLAG_REFUSAL], (int32_t)PATCH_REPEATED_ROW);
         atomicAdd(&counts[row], 1u);
     }
@@ -126,14 +127,14 @@ __global__ __launch_bounds__(SCAN_BLOCK) void patch_slot_ptr_kernel(size_t n, ui
     if (i == 0) slot_ptr[n] = (int32_t)entries;
 }
 
-__global__ __launch_bounds__(RB) void patch_slot_fill_kernel(size_t npatches, const int64_t *ptr, const int32_t *rows, uint32_t *cursor,
-                                                             int32_t *slot_idx)
+__global__ __launch_bounds__(RB) void patch_slot_fill_kernel(size_t npatches, int64_t row0, const int64_t *ptr, const int32_t *rows,
+                                                             uint32_t *cursor, int32_t *slot_idx)
 {
     const size_t p = (size_t)blockIdx.x * RB + threadIdx.x;
     if (p >= npatches) return;
     const int64_t p0 = ptr[p];
     const int m = (int)(ptr[p + 1] - p0);
-    for (int l = 0; l < m; ++l) slot_idx[atomicAdd(&cursor[rows[p0 + l]], 1u)] = (int32_t)(p0 + l);
+    for (int l = 0; l < m; ++l) slot_idx[atomicAdd(&cursor[rows[p0 + l] - row0], 1u)] = (int32_t)(p0 + l);
 }
 
 // a row's slots ascending: the order of its patches, whatever order the fill reached them in
@@ -151,8 +152,9 @@ __global__ __launch_bounds__(RB) void patch_slot_sort_kernel(size_t n, const int
 }
 
 // ---- factor -------------------------------------------------------------------------------------------------------------------------
-// A(row, col) of a CSR matrix with ascending columns; an absent entry is zero
-__device__ __forceinline__ double csr_entry(const int64_t *rowptr, const int32_t *colind, const double *values, int32_t row, int32_t col)
+// A(row, col) of a CSR matrix with ascending columns; an absent entry is zero.  row: the storage row (CgRowsWindow, cg.hpp: a rank's
+// rows are stored from 0 on and keep global columns)
+__device__ __forceinline__ double csr_entry(const int64_t *rowptr, const int32_t *colind, const double *values, int64_t row, int32_t col)
 {
     const int64_t end = rowptr[row + 1];
     int64_t lo = rowptr[row], hi = end;
@@ -164,9 +166,9 @@ __device__ __forceinline__ double csr_entry(const int64_t *rowptr, const int32_t
 }
 
 template <int P>
-__global__ __launch_bounds__(RB) void patch_factor_kernel(size_t npatches, const int64_t *ptr, const int32_t *rows, const int64_t *rowptr,
-                                                          const int32_t *colind, const double *values, int stride, double *factors,
-                                                          int32_t *info, int32_t *flags)
+__global__ __launch_bounds__(RB) void patch_factor_kernel(size_t npatches, int64_t row0, const int64_t *ptr, const int32_t *rows,
+                                                          const int64_t *rowptr, const int32_t *colind, const double *values, int stride,
+                                                          double *factors, int32_t *info, int32_t *flags)
 {
     const size_t p = ((size_t)blockIdx.x * RB + threadIdx.x) / P;
     const int l = threadIdx.x % P;
@@ -180,7 +182,7 @@ __global__ __launch_bounds__(RB) void patch_factor_kernel(size_t npatches, const
 #pragma unroll
     for (int j = 0; j < P; ++j) {
         const int32_t gj = __shfl(gl, j, P);
-        a[j] = (act && gj >= 0) ? csr_entry(rowptr, colind, values, gl, gj) : (l == j ? 1.0 : 0.0);
+        a[j] = (act && gj >= 0) ? csr_entry(rowptr, colind, values, (int64_t)gl - row0, gj) : (l == j ? 1.0 : 0.0);
     }
     // Cholesky, right-looking: after step j, a[j] of lane i >= j is L(i, j)
     int bad = 0;
@@ -220,8 +222,8 @@ __global__ __launch_bounds__(RB) void patch_factor_kernel(size_t npatches, const
 
 // ---- apply --------------------------------------------------------------------------------------------------------------------------
 template <int P>
-__global__ __launch_bounds__(RB) void patch_apply_kernel(size_t npatches, const int64_t *ptr, const int32_t *rows, const double *factors,
-                                                         int stride, const double *r, double *zbuf)
+__global__ __launch_bounds__(RB) void patch_apply_kernel(size_t npatches, int64_t row0, const int64_t *ptr, const int32_t *rows,
+                                                         const double *factors, int stride, const double *r, double *zbuf)
 {
     const size_t p = ((size_t)blockIdx.x * RB + threadIdx.x) / P;
     const int l = threadIdx.x % P;
@@ -229,7 +231,7 @@ __global__ __launch_bounds__(RB) void patch_apply_kernel(size_t npatches, const 
     int m = 0;
     if (p < npatches) { p0 = ptr[p]; m = (int)(ptr[p + 1] - p0); }
     const bool act = l < m;
-    const double rl = act ? r[rows[p0 + l]] : 0.0;
+    const double rl = act ? r[rows[p0 + l] - row0] : 0.0;
     const double *W = factors + (p < npatches ? p : 0) * (size_t)stride;
     double t = 0.0;
 #pragma unroll
@@ -307,7 +309,7 @@ hipError_t patch_factor(hipStream_t stream, const int64_t *rowptr, const int32_t
     hipError_t e = hipMemsetAsync(s.counts, 0, (t.n + 1) * 4, stream);
     if (e == hipSuccess) e = hipMemsetAsync(s.flags, 0, NFLAGS * 4, stream);
     if (e != hipSuccess) return e;
-    if (t.npatches) hipLaunchKernelGGL(patch_rows_check_kernel, dim3(gp), dim3(RB), 0, stream, t.n, t.npatches, t.ptr, t.rows, s.counts, s.flags);
+    if (t.npatches) hipLaunchKernelGGL(patch_rows_check_kernel, dim3(gp), dim3(RB), 0, stream, t.n, t.row0, t.npatches, t.ptr, t.rows, s.counts, s.flags);
     if (t.n) hipLaunchKernelGGL(patch_cover_kernel, dim3(nb), dim3(SCAN_BLOCK), 0, stream, t.n, s.counts, s.blk, s.flags);
     e = hipMemcpyAsync(h, s.flags, NFLAGS * 4, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
@@ -317,16 +319,16 @@ hipError_t patch_factor(hipStream_t stream, const int64_t *rowptr, const int32_t
     int32_t *slot_ptr = slots, *slot_idx = slots + t.n + 1;
     hipLaunchKernelGGL(active_block_scan_kernel, dim3(1), dim3(SCAN_BLOCK), 0, stream, s.blk, nb);
     hipLaunchKernelGGL(patch_slot_ptr_kernel, dim3(nb), dim3(SCAN_BLOCK), 0, stream, t.n, (uint32_t)sz.entries, s.counts, s.blk, slot_ptr);
-    hipLaunchKernelGGL(patch_slot_fill_kernel, dim3(gp), dim3(RB), 0, stream, t.npatches, t.ptr, t.rows, s.counts, slot_idx);
+    hipLaunchKernelGGL(patch_slot_fill_kernel, dim3(gp), dim3(RB), 0, stream, t.npatches, t.row0, t.ptr, t.rows, s.counts, slot_idx);
     hipLaunchKernelGGL(patch_slot_sort_kernel, dim3(gr), dim3(RB), 0, stream, t.n, slot_ptr, slot_idx);
     const int stride = sz.max_rows * (sz.max_rows + 1) / 2;
     const unsigned gf = (unsigned)((t.npatches * (size_t)sz.lanes + RB - 1) / RB);
     if (sz.lanes == 4)
-        hipLaunchKernelGGL(patch_factor_kernel<4>, dim3(gf), dim3(RB), 0, stream, t.npatches, t.ptr, t.rows, rowptr, colind, values, stride, factors, info, s.flags);
+        hipLaunchKernelGGL(patch_factor_kernel<4>, dim3(gf), dim3(RB), 0, stream, t.npatches, t.row0, t.ptr, t.rows, rowptr, colind, values, stride, factors, info, s.flags);
     else if (sz.lanes == 8)
-        hipLaunchKernelGGL(patch_factor_kernel<8>, dim3(gf), dim3(RB), 0, stream, t.npatches, t.ptr, t.rows, rowptr, colind, values, stride, factors, info, s.flags);
+        hipLaunchKernelGGL(patch_factor_kernel<8>, dim3(gf), dim3(RB), 0, stream, t.npatches, t.row0, t.ptr, t.rows, rowptr, colind, values, stride, factors, info, s.flags);
     else
-        hipLaunchKernelGGL(patch_factor_kernel<16>, dim3(gf), dim3(RB), 0, stream, t.npatches, t.ptr, t.rows, rowptr, colind, values, stride, factors, info, s.flags);
+        hipLaunchKernelGGL(patch_factor_kernel<16>, dim3(gf), dim3(RB), 0, stream, t.npatches, t.row0, t.ptr, t.rows, rowptr, colind, values, stride, factors, info, s.flags);
     e = hipMemcpyAsync(h, s.flags, NFLAGS * 4, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e == hipSuccess) e = hipGetLastError();
@@ -343,11 +345,11 @@ void patch_apply(hipStream_t stream, const PatchTable &t, const PatchSizes &sz, 
     const int stride = sz.max_rows * (sz.max_rows + 1) / 2;
     const unsigned ga = (unsigned)((t.npatches * (size_t)sz.lanes + RB - 1) / RB);
     if (sz.lanes == 4)
-        hipLaunchKernelGGL(patch_apply_kernel<4>, dim3(ga), dim3(RB), 0, stream, t.npatches, t.ptr, t.rows, factors, stride, r, s.zbuf);
+        hipLaunchKernelGGL(patch_apply_kernel<4>, dim3(ga), dim3(RB), 0, stream, t.npatches, t.row0, t.ptr, t.rows, factors, stride, r, s.zbuf);
     else if (sz.lanes == 8)
-        hipLaunchKernelGGL(patch_apply_kernel<8>, dim3(ga), dim3(RB), 0, stream, t.npatches, t.ptr, t.rows, factors, stride, r, s.zbuf);
+        hipLaunchKernelGGL(patch_apply_kernel<8>, dim3(ga), dim3(RB), 0, stream, t.npatches, t.row0, t.ptr, t.rows, factors, stride, r, s.zbuf);
     else
-        hipLaunchKernelGGL(patch_apply_kernel<16>, dim3(ga), dim3(RB), 0, stream, t.npatches, t.ptr, t.rows, factors, stride, r, s.zbuf);
+        hipLaunchKernelGGL(patch_apply_kernel<16>, dim3(ga), dim3(RB), 0, stream, t.npatches, t.row0, t.ptr, t.rows, factors, stride, r, s.zbuf);
     hipLaunchKernelGGL(patch_sum_kernel, dim3((unsigned)((t.n + RB - 1) / RB)), dim3(RB), 0, stream, t.n, slots, slots + t.n + 1, s.zbuf, r, z,
                        part_rz);
 }
@@ -401,11 +403,11 @@ hipError_t conjugated_gradient_patch(hipStream_t stream, size_t n, const int64_t
 }
 
 // ---- the patch tables of the face-only system ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(RB) void face_patches_kernel(uint32_t nfaces, int fbs, int64_t *ptr, int32_t *rows)
+__global__ __launch_bounds__(RB) void face_patches_kernel(uint32_t nfaces, int fbs, int32_t row0, int64_t *ptr, int32_t *rows)
 {
     const size_t i = (size_t)blockIdx.x * RB + threadIdx.x;
     if (i <= nfaces) ptr[i] = (int64_t)i * fbs;
-    if (i < (size_t)nfaces * fbs) rows[i] = (int32_t)i;
+    if (i < (size_t)nfaces * fbs) rows[i] = row0 + (int32_t)i;
 }
 
 __global__ __launch_bounds__(RB) void cell_patch_flags_kernel(uint32_t ncells, const uint32_t *cprefix, uint8_t *flags)
@@ -432,10 +434,10 @@ __global__ __launch_bounds__(RB) void cell_patches_kernel(uint32_t ncells, uint3
     }
 }
 
-void face_patches(hipStream_t stream, uint32_t nfaces, int fbs, int64_t *ptr, int32_t *rows)
+void face_patches(hipStream_t stream, uint32_t nfaces, int fbs, int32_t row0, int64_t *ptr, int32_t *rows)
 {
     const size_t total = (size_t)nfaces * fbs + 1;
-    hipLaunchKernelGGL(face_patches_kernel, dim3((unsigned)((total + RB - 1) / RB)), dim3(RB), 0, stream, nfaces, fbs, ptr, rows);
+    hipLaunchKernelGGL(face_patches_kernel, dim3((unsigned)((total + RB - 1) / RB)), dim3(RB), 0, stream, nfaces, fbs, row0, ptr, rows);
 }
 
 void cell_patch_flags(hipStream_t stream, uint32_t ncells, const uint32_t *cprefix, uint8_t *flags)
@@ -448,6 +450,82 @@ void cell_patches(hipStream_t stream, uint32_t ncells, uint32_t npatches, const 
 {
     hipLaunchKernelGGL(cell_patches_kernel, dim3((ncells + RB) / RB), dim3(RB), 0, stream, ncells, npatches, cell_faces, face_compress, cprefix,
                        index, fbs, ptr, rows);
+}
+
+// ---- the cell patches of a slab of the generator mesh (pa_condensed_rows_patches), from the closed forms of structured_mesh.hpp: the
+// slab owns the compressed faces [p0, p1) -- of its top cell row's top faces none, unless it is the last slab --, and a patch names
+// its rows by their global indices ------------------------------------------------------------------------------------------------
+// -> the owned non-Dirichlet faces of local cell c in the cell's face order bottom, right, top, left
+__device__ __forceinline__ int slab_cell_faces(const StructuredMesh &sm, int32_t p0, int32_t p1, uint32_t c, int32_t *q)
+{
+    const uint32_t ci = c % sm.Nx, cj = sm.row0 + c / sm.Nx;
+    const uint32_t f[4] = {sm_hface(sm, ci, cj), sm_vface(sm, ci + 1, cj), sm_hface(sm, ci, cj + 1), sm_vface(sm, ci, cj)};
+    int n = 0;
+    for (int lf = 0; lf < 4; ++lf) {
+        uint32_t lo, hi;
+        bool dirichlet;
+        int32_t comp;
+        sm_face_decode(sm, f[lf], lo, hi, dirichlet, comp);
+        if (!dirichlet && comp >= p0 && comp < p1) q[n++] = comp;
+    }
+    return n;
+}
+
+// per block of cells: its patches (bp) and its faces (bb)
+__global__ __launch_bounds__(SCAN_BLOCK) void slab_cell_count_kernel(StructuredMesh sm, int32_t p0, int32_t p1, uint32_t ncells, uint32_t *bp,
+                                                                     uint32_t *bb)
+{
+    __shared__ uint32_t sh[SCAN_BLOCK / 64];
+    const uint32_t c = blockIdx.x * SCAN_BLOCK + threadIdx.x;
+    int32_t q[4];
+    const uint32_t nf = c < ncells ? (uint32_t)slab_cell_faces(sm, p0, p1, c, q) : 0u;
+    uint32_t tp, tb;
+    block_exclusive_scan(nf ? 1u : 0u, sh, tp);
+    block_exclusive_scan(nf, sh, tb);
+    if (threadIdx.x == 0) { bp[blockIdx.x] = tp; bb[blockIdx.x] = tb; }
+}
+
+// bp, bb scanned (their totals at [nblk]): every cell with owned faces writes its patch
+__global__ __launch_bounds__(SCAN_BLOCK) void slab_cell_fill_kernel(StructuredMesh sm, int32_t p0, int32_t p1, uint32_t ncells, int fbs,
+                                                                    const uint32_t *bp, const uint32_t *bb, uint32_t nblk, int64_t *ptr,
+                                                                    int32_t *rows)
+{
+    __shared__ uint32_t sh[SCAN_BLOCK / 64];
+    const uint32_t c = blockIdx.x * SCAN_BLOCK + threadIdx.x;
+    int32_t q[4];
+    const uint32_t nf = c < ncells ? (uint32_t)slab_cell_faces(sm, p0, p1, c, q) : 0u;
+    uint32_t tp, tb;
+    const uint32_t p = bp[blockIdx.x] + block_exclusive_scan(nf ? 1u : 0u, sh, tp);
+    const uint32_t b0 = bb[blockIdx.x] + block_exclusive_scan(nf, sh, tb);
+    if (c == 0) ptr[bp[nblk]] = (int64_t)bb[nblk] * fbs;
+    if (nf == 0) return;
+    int64_t at = (int64_t)b0 * fbs;
+    ptr[p] = at;
+    for (uint32_t i = 0; i < nf; ++i)
+        for (int k = 0; k < fbs; ++k) rows[at++] = q[i] * fbs + k;
+}
+
+hipError_t slab_cell_patches(hipStream_t stream, const StructuredMesh &sm, int32_t p0, int32_t p1, int fbs, uint64_t *npatches,
+                             uint64_t *entries, int64_t *ptr, int32_t *rows)
+{
+    const uint32_t ncells = (sm.row1 - sm.row0) * sm.Nx;
+    const uint32_t nblk = (ncells + SCAN_BLOCK - 1) / SCAN_BLOCK;
+    DeviceTmp tmp(stream);
+    uint32_t *bp = nullptr, *bb = nullptr;
+    if (!tmp.alloc(&bp, (size_t)nblk + 1) || !tmp.alloc(&bb, (size_t)nblk + 1)) return tmp.error();
+    hipLaunchKernelGGL(slab_cell_count_kernel, dim3(nblk), dim3(SCAN_BLOCK), 0, stream, sm, p0, p1, ncells, bp, bb);
+    hipLaunchKernelGGL(active_block_scan_kernel, dim3(1), dim3(SCAN_BLOCK), 0, stream, bp, nblk);
+    hipLaunchKernelGGL(active_block_scan_kernel, dim3(1), dim3(SCAN_BLOCK), 0, stream, bb, nblk);
+    uint32_t tot[2] = {0, 0};
+    if (!tmp.ok(hipGetLastError()) || !tmp.ok(hipMemcpyAsync(&tot[0], bp + nblk, sizeof(uint32_t), hipMemcpyDeviceToHost, stream)) ||
+        !tmp.ok(hipMemcpyAsync(&tot[1], bb + nblk, sizeof(uint32_t), hipMemcpyDeviceToHost, stream)) || !tmp.ok(hipStreamSynchronize(stream)))
+        return tmp.error();
+    *npatches = tot[0];
+    *entries = (uint64_t)tot[1] * fbs;
+    if (ptr == nullptr || *entries >= ((uint64_t)1 << 31)) return hipSuccess;
+    hipLaunchKernelGGL(slab_cell_fill_kernel, dim3(nblk), dim3(SCAN_BLOCK), 0, stream, sm, p0, p1, ncells, fbs, bp, bb, nblk, ptr, rows);
+    if (tmp.ok(hipGetLastError())) tmp.ok(hipStreamSynchronize(stream));       // the block offsets live until the kernel has read them
+    return tmp.error();
 }
 
 // ---- the patch tables of the interface problem's face-only system (pa_interface_condensed_patches: interface_assembler's numbering, in

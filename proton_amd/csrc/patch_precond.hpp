@@ -8,15 +8,20 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "structured_mesh.hpp"
+
 namespace pa {
 
 constexpr int PATCH_MAX_ROWS = 16;         // PA_PATCH_MAX_ROWS: 4 fbs at k = 3
 
-// the patch table: patch p holds the rows rows[ptr[p]] .. rows[ptr[p + 1] - 1] of an n-row system
+// the patch table: patch p holds the rows rows[ptr[p]] .. rows[ptr[p + 1] - 1] of an n-row system.  row0: the system is the rows
+// [row0, row0 + n) of a larger one (a rank's rows: CgRowsWindow, cg.hpp) and the table names them by their global indices; the
+// matrix is stored from row 0 on with global columns, the vectors hold the n rows
 struct PatchTable {
     size_t n, npatches;
     const int64_t *ptr;                    // npatches + 1
     const int32_t *rows;                   // ptr[npatches]
+    int64_t row0 = 0;
 };
 
 // what one table needs.  lanes: the lanes that share a patch (4, 8 or 16: the smallest that holds max_rows); every patch's factor
@@ -53,12 +58,17 @@ hipError_t conjugated_gradient_patch(hipStream_t stream, size_t n, const int64_t
 
 // ---- the patch tables of the face-only system of pa_condensed_csr_pattern (whole-mesh contexts: compressed face q owns rows
 // q fbs .. q fbs + fbs - 1) ----
-// one patch per non-Dirichlet face
-void face_patches(hipStream_t stream, uint32_t nfaces, int fbs, int64_t *ptr, int32_t *rows);
+// one patch per non-Dirichlet face; row0: the first row of the nfaces faces (a slab's: its row_begin)
+void face_patches(hipStream_t stream, uint32_t nfaces, int fbs, int32_t row0, int64_t *ptr, int32_t *rows);
 // flags[c] = cell c has a non-Dirichlet face (cprefix: non-Dirichlet faces of the cells before c, ncells + 1)
 void cell_patch_flags(hipStream_t stream, uint32_t ncells, const uint32_t *cprefix, uint8_t *flags);
 // one patch per flagged cell (index[c]: its patch, -1 none), rows in the cell's face order bottom, right, top, left
 void cell_patches(hipStream_t stream, uint32_t ncells, uint32_t npatches, const uint32_t *cell_faces, const int32_t *face_compress,
                   const uint32_t *cprefix, const int32_t *index, int fbs, int64_t *ptr, int32_t *rows);
+
+// ---- the cell patches of a slab of the generator mesh that owns the compressed faces [p0, p1): one patch per cell of the slab
+// with an owned non-Dirichlet face, the global rows of those faces in the cell's face order.  ptr = null: the sizes only.  Waits.
+hipError_t slab_cell_patches(hipStream_t stream, const StructuredMesh &sm, int32_t p0, int32_t p1, int fbs, uint64_t *npatches,
+                             uint64_t *entries, int64_t *ptr, int32_t *rows);
 
 }  // namespace pa

@@ -1,0 +1,35 @@
+// rows_precond.hpp -- host entry point of rows_precond.hip: the conjugate gradient of solver_cg.hpp:63-144 on a row-partitioned
+// system with the patches of patch_precond.hpp and the Galerkin coarse level of coarse_precond.hpp, both partitioned by rows.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "cg.hpp"
+
+namespace pa {
+
+// what this rank's status 5 or 6 was about: level 1 the patches, 2 the coarse level; refusal: the code of patch_refusal_text /
+// coarse_refusal_text (status 5); pivot: j + 1 for the first non-positive pivot j of the coarse matrix (status 6, level 2)
+struct RowsPrecondReport {
+    int level = 0, refusal = 0;
+    int32_t pivot = 0;
+};
+
+// conjugated_gradient_rows (cg.hpp: its arguments, results and statuses) with z = (patch sum) + (coarse term).  The patch table
+// holds GLOBAL row indices within [row_begin, row_end); p_ptr / p_cols / p_vals are the rank's own rows of P (p_ptr from 0,
+// global coarse columns), ncoarse the same on every rank, 0 = patches only.  Statuses beyond conjugated_gradient_rows': 5 a table
+// of this rank was refused, 6 a patch of this rank or the coarse matrix is not positive definite (*report says which); x is
+// written only with status 0.  Without a transport, from row 0 and with whole tables the call is conjugated_gradient_patch_coarse
+// (ncoarse = 0: conjugated_gradient_patch) bit for bit.
+hipError_t conjugated_gradient_rows_patch_coarse(hipStream_t stream, const CgTransport *tp, int64_t row_begin, int64_t row_end,
+                                                 const int64_t *rowptr, const int32_t *colind, const double *values, const double *b,
+                                                 double *x, size_t npatches, const int64_t *patch_ptr, const int32_t *patch_rows,
+                                                 size_t ncoarse, const int64_t *p_ptr, const int32_t *p_cols, const double *p_vals,
+                                                 double convergence_threshold, double divergence_threshold, size_t max_iter,
+                                                 int *exit_reason, size_t *iterations, double *relative_residual, int *transport_status,
+                                                 RowsPrecondReport *report);
+
+}  // namespace pa

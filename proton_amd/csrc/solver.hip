@@ -318,15 +318,18 @@ __global__ __launch_bounds__(RB) void cg_col_range_kernel(size_t nnz, const int3
 }
 
 // status: 0 ok; 1 a transport callback failed on THIS rank; 2 this rank's rows read a column no neighbour range covers (or, without a
-// transport, beyond its own range); 3 another rank failed (its status says why); 4 a HIP error on this rank.
+// transport, beyond its own range); 3 another rank failed (its status says why); 4 a HIP error on this rank; 5, 6: what a
+// preconditioner says of its tables (CgRowsFail, cg.hpp).
 // EVERY exit is collective: a rank that fails locally -- a callback, a HIP call, the range check -- does not leave the others inside a
 // reduction or a neighbour exchange.  Its failure is a flag that rides on the next all-reduce (an extra addend behind the dot products),
 // every rank sees the sum and all of them leave together, at the same point.  (What cannot be covered: the all-reduce itself failing
 // on one rank only -- then there is nothing left to tell the others with.)
-hipError_t conjugated_gradient_rows(hipStream_t stream, const CgTransport *tp, int64_t row_begin, int64_t row_end, const int64_t *rowptr,
-                                    const int32_t *colind, const double *values, const double *b, double *x,
-                                    double convergence_threshold, double divergence_threshold, size_t max_iter, int precond,
-                                    int *exit_reason, size_t *iterations, double *relative_residual, int *transport_status)
+// pre: null = Jacobi (precond != 0) or none, formed in the vector kernels; otherwise z comes from pre->apply, precond is not read, and
+// the iterate lives in a vector of the call's own until the solve has ended well.
+static hipError_t cg_rows_iterate(hipStream_t stream, const CgTransport *tp, int64_t row_begin, int64_t row_end, const int64_t *rowptr,
+                                  const int32_t *colind, const double *values, const CgRowsPreconditioner *pre, const double *b, double *x,
+                                  double convergence_threshold, double divergence_threshold, size_t max_iter, int precond,
+                                  int *exit_reason, size_t *iterations, double *relative_residual, int *transport_status)
 {
     const size_t n = (size_t)(row_end - row_begin);
     const size_t nn = n ? n : 1;
@@ -335,9 +338,10 @@ hipError_t conjugated_gradient_rows(hipStream_t stream, const CgTransport *tp, i
     DeviceTmp tmp(stream);
     int *mm = nullptr;
     if (transport_status) *transport_status = 0;
-    int fail = 0;                          // this rank's status (see above); 0 while everything went well
-    hipError_t herr = hipSuccess;
-    auto hip_ok = [&](hipError_t e) -> bool { if (e != hipSuccess && !fail) { fail = 4; herr = e; } return e == hipSuccess; };
+    CgRowsFail failure;
+    int &fail = failure.status;            // this rank's status (see above); 0 while everything went well
+    hipError_t &herr = failure.herr;
+    auto hip_ok = [&](hipError_t e) -> bool { return failure.hip_ok(e); };
     auto leave = [&](int status) -> hipError_t {
         if (transport_status) *transport_status = status;
         cg_workspace_release(&ws);
@@ -376,12 +380,22 @@ hipError_t conjugated_gradient_rows(hipStream_t stream, const CgTransport *tp, i
     if (!fail && (give_lo > (int64_t)n || give_hi > (int64_t)n)) fail = 2;
     const size_t nwin = n + (size_t)need_lo + (size_t)need_hi;
     if (!fail) (void)(hip_ok(cg_workspace_reserve(&ws, nn, nwin)) && hip_ok(hipMemsetAsync(ws.d, 0, (nwin ? nwin : 1) * 8, stream)));
+    const CgRowsSystem sys{tp, row_begin, row_end, need_lo, need_hi, give_lo, give_hi, rowptr, colind, values};
+    double *xw = x;                        // where the iterate lives
+    if (pre) {
+        if (!fail && !tmp.alloc(&xw, nn)) hip_ok(tmp.error());
+        if (!fail) pre->prepare(pre->user, stream, sys, &failure);
+    }
     {
         const int st = agree();            // nobody starts iterating unless everybody can
         if (st) return leave(st);
     }
+    if (pre) {
+        const int st = pre->setup(pre->user, stream, sys, &failure);
+        if (st) return leave(st);
+    }
     double *dwin = ws.d, *d = dwin + need_lo;            // the window, and its owned part
-    const VectorKernels k{stream, n, (unsigned)gv, x, ws.r, d, ws.y, ws.part_a, ws.part_b};
+    const VectorKernels k{stream, n, (unsigned)gv, xw, ws.r, d, ws.y, ws.part_a, ws.part_b};
     const CgJacobi jacobi{ws.iA, precond};
     const CgRowsWindow rows{row_begin, row_begin - need_lo, (size_t)need_lo};
     double hs[3];
@@ -406,9 +420,17 @@ hipError_t conjugated_gradient_rows(hipStream_t stream, const CgTransport *tp, i
     int reason = 2;
     double rr = 0.0;
     {
-        if (n) launch_inv_diag(stream, n, rows, rowptr, colind, values, ws.iA);
-        k.init(b, jacobi);                 // r = b, d = M^-1 r (x = 0), partials of r.r and r.M^-1 r       solver_cg.hpp:73-84
-        int st = reduce2(gv, ws.part_b, 2);
+        int st = 0;
+        if (pre) {
+            k.init(b, CgStoredZ{pre->z, 0});                                                                         // :73-84
+            st = pre->apply(pre->user, stream, sys, ws.r, pre->z, ws.part_b, &failure);
+            if (st) return leave(st);
+            k.direction(CgStep{nullptr, 0.0}, CgStoredZ{pre->z, 1});
+        } else {
+            if (n) launch_inv_diag(stream, n, rows, rowptr, colind, values, ws.iA);
+            k.init(b, jacobi);             // r = b, d = M^-1 r (x = 0), partials of r.r and r.M^-1 r       solver_cg.hpp:73-84
+        }
+        st = reduce2(gv, ws.part_b, 2);
         if (st) return leave(st);
         const double nr0 = sqrt(hs[0]);
         double rho = hs[1];
@@ -420,7 +442,11 @@ hipError_t conjugated_gradient_rows(hipStream_t stream, const CgTransport *tp, i
                 st = reduce2(gs, nullptr, 1);
                 if (st) return leave(st);
                 const double alpha = rho / hs[0];                                                                    // :101-102
-                k.update(CgStep{nullptr, alpha}, jacobi);                                                            // :103-105
+                if (pre) {
+                    k.update(CgStep{nullptr, alpha}, CgStoredZ{pre->z, 0});                                          // :103-105
+                    st = pre->apply(pre->user, stream, sys, ws.r, pre->z, ws.part_b, &failure);
+                    if (st) return leave(st);
+                } else k.update(CgStep{nullptr, alpha}, jacobi);
                 st = reduce2(gv, ws.part_b, 2);
                 if (st) return leave(st);
                 rr = sqrt(hs[0]) / nr0;
@@ -430,7 +456,8 @@ hipError_t conjugated_gradient_rows(hipStream_t stream, const CgTransport *tp, i
                 if (!(rr == rr)) { reason = 1; break; }
                 const double beta = hs[1] / rho;
                 rho = hs[1];
-                k.direction(CgStep{nullptr, beta}, jacobi);                                                          // :126-128
+                if (pre) k.direction(CgStep{nullptr, beta}, CgStoredZ{pre->z, 0});                                   // :126-128
+                else k.direction(CgStep{nullptr, beta}, jacobi);
                 iter++;
             }
     }
@@ -439,10 +466,32 @@ hipError_t conjugated_gradient_rows(hipStream_t stream, const CgTransport *tp, i
         const int st = agree();            // a rank whose last launches failed says so before anybody reports success
         if (st) return leave(st);
     }
+    // (the solve has ended on every rank: a copy that fails here leaves nobody waiting)
+    if (pre && n && !(hip_ok(hipMemcpyAsync(x, xw, n * 8, hipMemcpyDeviceToDevice, stream)) && hip_ok(hipStreamSynchronize(stream))))
+        return leave(4);
     if (exit_reason) *exit_reason = reason;
     if (iterations) *iterations = iter;
     if (relative_residual) *relative_residual = rr;
     return leave(0);
+}
+
+hipError_t conjugated_gradient_rows(hipStream_t stream, const CgTransport *tp, int64_t row_begin, int64_t row_end, const int64_t *rowptr,
+                                    const int32_t *colind, const double *values, const double *b, double *x,
+                                    double convergence_threshold, double divergence_threshold, size_t max_iter, int precond,
+                                    int *exit_reason, size_t *iterations, double *relative_residual, int *transport_status)
+{
+    return cg_rows_iterate(stream, tp, row_begin, row_end, rowptr, colind, values, nullptr, b, x, convergence_threshold, divergence_threshold,
+                           max_iter, precond, exit_reason, iterations, relative_residual, transport_status);
+}
+
+hipError_t conjugated_gradient_rows_stored(hipStream_t stream, const CgTransport *tp, int64_t row_begin, int64_t row_end,
+                                           const int64_t *rowptr, const int32_t *colind, const double *values,
+                                           const CgRowsPreconditioner *pre, const double *b, double *x, double convergence_threshold,
+                                           double divergence_threshold, size_t max_iter, int *exit_reason, size_t *iterations,
+                                           double *relative_residual, int *transport_status)
+{
+    return cg_rows_iterate(stream, tp, row_begin, row_end, rowptr, colind, values, pre, b, x, convergence_threshold, divergence_threshold,
+                           max_iter, 0, exit_reason, iterations, relative_residual, transport_status);
 }
 
 }  // namespace pa

@@ -4,6 +4,7 @@ twin of the one exchange of an assembly step.
 The exchange itself lives behind the C ABI (include/proton_amd.h, pa_comm_*: RCCL send / recv of the packed top-face
 rows of a slab's top cell row, one slab up).  `HostStagedHalo` moves the same buffers through torch.distributed's gloo
 backend on host copies: it is what the CPU tests (world_size 2, no GPU) and the one-GPU rehearsal of bench.py use."""
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -85,10 +86,10 @@ class HostStagedCgTransport:
 
         def allreduce(user, vals, n):
             try:
-                t = torch.tensor([vals[i] for i in range(n)], dtype=torch.float64)
+                view = np.ctypeslib.as_array(vals, shape=(n,))      # (up to 2^20 + 1 values at the set-up of the coarse level)
+                t = torch.from_numpy(view.copy())
                 dist.all_reduce(t, op=dist.ReduceOp.SUM)
-                for i in range(n):
-                    vals[i] = float(t[i])
+                view[:] = t.numpy()
                 return 0
             except Exception:       # noqa: BLE001  (a callback must not raise through C)
                 return 1
