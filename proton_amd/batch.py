@@ -544,11 +544,21 @@ class BatchAssembler:
         return {"alpha": alpha, "beta": beta, "in_A": in_A, "info": info, "num_A": hist_a, "cg_iterations": hist_cg}
 
     # ---- cutHHO fictitious domain (cuthho_square -f) ------------------------------------
-    def cut_preprocess(self, N, radius=0.35, center=(0.5, 0.5), refsteps=4, rows=None, line_y=None):
-        """cuthho_square.cpp:2026-2052: mesh, circle level set (or, line_y given, line_level_set y - line_y, :91-124), default (-D)
-        preprocessing.  rows = (row_begin, row_end): the context keeps that slab of cell rows (pa_cut_preprocess_rows)."""
+    def cut_preprocess(self, N, radius=0.35, center=(0.5, 0.5), refsteps=4, rows=None, line_y=None, Ny=None, lo=(0.0, 0.0), hi=(1.0, 1.0),
+                       agglomeration=False):
+        """cuthho_square.cpp:2026-2052: the N x Ny mesh (Ny = None: N x N) of the box [lo, hi], circle level set (or, line_y given,
+        line_level_set y - line_y, :91-124), default (-D) preprocessing or, agglomeration set, the `-A` branch
+        (pa_cut_preprocess_agglomeration: no node displacement).  rows = (row_begin, row_end): the context keeps that slab of cell
+        rows (pa_cut_preprocess_rows)."""
         self.level_set = capi.LevelSet(0, radius, center[0], center[1], 0.0) if line_y is None else capi.LevelSet(1, 0.0, 0.0, 0.0, line_y)
-        self.ctx.cut_preprocess(N, N, self.level_set, refsteps, rows=rows)
+        self.Nx, self.Ny = int(N), int(N if Ny is None else Ny)
+        self.lo, self.hi = (float(lo[0]), float(lo[1])), (float(hi[0]), float(hi[1]))
+        if agglomeration:
+            if rows is not None:
+                raise ValueError("the agglomeration branch numbers the whole mesh: no row slab")
+            self.ctx.cut_preprocess_agglomeration(self.Nx, self.Ny, self.level_set, refsteps, lo=self.lo, hi=self.hi)
+        else:
+            self.ctx.cut_preprocess(self.Nx, self.Ny, self.level_set, refsteps, lo=self.lo, hi=self.hi, rows=rows)
         self.ncut, self.cell_loc, self.cut_index = self.ctx.cut_query()
         return self.ncut
 

@@ -10,24 +10,32 @@ import scipy.sparse.linalg as spla
 import oracle_lib as o
 
 
-def oracle_cut_provider(msh, di):
-    """-> list of (lc, rhs) per cell from the oracle's cut operators."""
+def oracle_cut_provider(msh, di, truth=False):
+    """-> list of (lc, rhs) per cell from the oracle's cut operators; truth: the cut cells' from the binary128 evaluation
+    (oracle/cut_truth.c), the uncut cells' still the oracle's."""
     out = []
     for c in range(msh.nc):
-        st, oper, data = msh.laplacian(c, di)
+        t = truth and msh.cell_loc[c] == o.CUT_ON_INTERFACE
+        st, oper, data = (msh.truth_laplacian if t else msh.laplacian)(c, di)
         assert st == 0, (c, st)
-        st, stab = msh.cut_stabilization(c, di)
+        st, stab = (msh.truth_stabilization if t else msh.cut_stabilization)(c, di)
         assert st == 0
-        st, f = msh.rhs(c, di.cell_deg)
+        st, f = (msh.truth_rhs if t else msh.rhs)(c, di.cell_deg)
         assert st == 0
         out.append((data + stab, f))
     return out
 
 
-def run_fictdom(N, k, refsteps=4, provider=oracle_cut_provider):
-    msh = o.CutMesh(N, refsteps=refsteps)
+def truth_cut_provider(msh, di):
+    return oracle_cut_provider(msh, di, truth=True)
+
+
+def run_fictdom(N, k, refsteps=4, provider=oracle_cut_provider, **mesh):
+    """mesh: oracle_lib.CutMesh's further arguments (Ny, lo, hi, radius, center, line_y); the Dirichlet data is the boundary function
+    on that box's own boundary faces"""
+    msh = o.CutMesh(N, refsteps=refsteps, **mesh)
     di = o.degrees(k + 1, k)                                   # cuthho_square.cpp:871
-    mp = o.MeshParams(N, N, 0.0, 1.0, 0.0, 1.0)
+    mp = msh.mesh_params()
     asm = o.Assembler(mp, msh.points, msh.ptids, di, bf_id=2)   # make_assembler + bcs_fun = sol_fun
     local = provider(msh, di)
     rows, cols, vals = [], [], []
@@ -65,8 +73,11 @@ def run_fictdom(N, k, refsteps=4, provider=oracle_cut_provider):
     return math.sqrt(H1), msh
 
 
-def oracle_interface_provider(msh, di, kappa=(1.0, 1.0)):
-    """-> list of (lc, rhs) per cell as run_cuthho_interface builds them (cuthho_square.cpp:1664-1716)."""
+def oracle_interface_provider(msh, di, kappa=(1.0, 1.0), truth=False):
+    """-> list of (lc, rhs) per cell as run_cuthho_interface builds them (cuthho_square.cpp:1664-1716); truth: the cut cells' from
+    the binary128 evaluation (oracle/cut_truth.c), the uncut cells' still the oracle's."""
+    lap_i, stab_c, rhs_s = ((msh.truth_laplacian_interface, msh.truth_stabilization, msh.truth_rhs_side) if truth else
+                            (msh.laplacian_interface, msh.cut_stabilization, msh.rhs_side))
     cbs, nfd = di.cbs, 4 * di.fbs
     out = []
     for c in range(msh.nc):
@@ -81,11 +92,11 @@ def oracle_interface_provider(msh, di, kappa=(1.0, 1.0)):
             assert st == 0
             out.append((k * data + stab, f))
             continue
-        st, oper, lc = msh.laplacian_interface(c, di, kappa[0], kappa[1])               # :1691-1692
+        st, oper, lc = lap_i(c, di, kappa[0], kappa[1])                                 # :1691-1692
         assert st == 0
-        st, sn = msh.cut_stabilization(c, di, o.CUT_NEG)
+        st, sn = stab_c(c, di, o.CUT_NEG)
         assert st == 0
-        st, sp_ = msh.cut_stabilization(c, di, o.CUT_POS)
+        st, sp_ = stab_c(c, di, o.CUT_POS)
         assert st == 0
         sn, sp_ = kappa[0] * sn, kappa[1] * sp_                                         # :1694-1695
         cn, fn_ = slice(0, cbs), slice(2 * cbs, 2 * cbs + nfd)                          # :1697-1700
@@ -95,19 +106,23 @@ def oracle_interface_provider(msh, di, kappa=(1.0, 1.0)):
             lc[a, b] += sn[blk]
         for (a, b), blk in (((cp, cp), (sc, sc)), ((cp, fp), (sc, sf)), ((fp, cp), (sf, sc)), ((fp, fp), (sf, sf))):
             lc[a, b] += sp_[blk]
-        st, f_n = msh.rhs_side(c, di.cell_deg, o.CUT_NEG)                               # :1710-1711
+        st, f_n = rhs_s(c, di.cell_deg, o.CUT_NEG)                                      # :1710-1711
         assert st == 0
-        st, f_p = msh.rhs_side(c, di.cell_deg, o.CUT_POS)
+        st, f_p = rhs_s(c, di.cell_deg, o.CUT_POS)
         assert st == 0
         out.append((lc, np.concatenate([f_n, f_p])))
     return out
 
 
-def run_interface(N, k, refsteps=4, provider=oracle_interface_provider):
-    """cuthho_square -k K -M N -N N -r R -i : -> (energy-norm error, mesh)   (cuthho_square.cpp:1625-1846)"""
-    msh = o.CutMesh(N, refsteps=refsteps)
+def truth_interface_provider(msh, di, kappa=(1.0, 1.0)):
+    return oracle_interface_provider(msh, di, kappa, truth=True)
+
+
+def run_interface(N, k, refsteps=4, provider=oracle_interface_provider, **mesh):
+    """cuthho_square -k K -M N -N N -r R -i : -> (energy-norm error, mesh)   (cuthho_square.cpp:1625-1846); mesh: as run_fictdom's"""
+    msh = o.CutMesh(N, refsteps=refsteps, **mesh)
     di = o.degrees(k + 1, k)                                                            # :1662
-    mp = o.MeshParams(N, N, 0.0, 1.0, 0.0, 1.0)
+    mp = msh.mesh_params()
     plain = o.Assembler(mp, msh.points, msh.ptids, di, bf_id=2)                         # Dirichlet data of bcs_fun per face
     ct, ft, num_all_cells, num_other = msh.interface_tables()
     size = di.cbs * num_all_cells + di.fbs * num_other                                  # :1185

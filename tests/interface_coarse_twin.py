@@ -33,10 +33,11 @@ def block_items(face_table, face_loc, faces, num_other):
     return np.asarray(pts, dtype=np.int64).reshape(-1, 2), np.asarray(blk, dtype=np.int64), np.asarray(side, dtype=np.int64)
 
 
-def table(N, H, fbs, face_table, face_loc, faces, num_other, parts, shift=None):
-    """pa_interface_condensed_coarse on the N x N mesh: parts "one" or "side" -> coarse_twin.Table, or None where the entry refuses"""
+def table(N, H, fbs, face_table, face_loc, faces, num_other, parts, shift=None, Ny=None):
+    """pa_interface_condensed_coarse on the N x Ny mesh (Ny = None: N x N): parts "one" or "side" -> coarse_twin.Table, or None where
+    the entry refuses"""
     pts, blk, side = block_items(face_table, face_loc, faces, num_other)
-    return CT.table(N, N, H, fbs, blk, pts, num_other, side if parts == "side" else None, 0, shift)
+    return CT.table(N, N if Ny is None else Ny, H, fbs, blk, pts, num_other, side if parts == "side" else None, 0, shift)
 
 
 def mesh_table(msh, faces, k, H, parts, device_numbering=False, shift=None):
@@ -44,7 +45,7 @@ def mesh_table(msh, faces, k, H, parts, device_numbering=False, shift=None):
     _, ft, _, num_other = msh.interface_tables()
     if device_numbering:
         ft, num_other = I.device_face_table(msh.bnd, msh.face_loc)
-    return table(msh.N, H, k + 1, ft, msh.face_loc, faces, num_other, parts, shift)
+    return table(msh.Nx, H, k + 1, ft, msh.face_loc, faces, num_other, parts, shift, Ny=msh.Ny)
 
 
 @functools.lru_cache(maxsize=None)

@@ -46,9 +46,10 @@ def sorted_path(asm, t, n, system_size):
     return rowptr, colind, values, RHS
 
 
-def real_ops(asm, N, k, **kw):
+def real_ops(asm, N, k, refsteps=4, **kw):
+    """kw: BatchAssembler.cut_preprocess's further arguments (Ny, lo, hi, radius, center, line_y, rows)"""
     import proton_amd as pa
-    asm.cut_preprocess(N, refsteps=4, **kw)
+    asm.cut_preprocess(N, refsteps=refsteps, **kw)
     ops = asm.interface_local_ops(k)
     g = asm.dirichlet_data(k, pa.capi.FN_SIN_SIN_SOL)
     return ops, g

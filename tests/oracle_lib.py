@@ -462,13 +462,17 @@ class ObstacleAssembler(Assembler):
 class CutMesh:
     """cuthho_poly_mesh + the preprocessing of cuthho_square.cpp:2036-2052 (oracle side)."""
 
-    def __init__(self, N, radius=0.35, center=(0.5, 0.5), refsteps=4, agglomeration=False, line_y=None):
+    def __init__(self, N, radius=0.35, center=(0.5, 0.5), refsteps=4, agglomeration=False, line_y=None, Ny=None,
+                 lo=(0.0, 0.0), hi=(1.0, 1.0)):
+        """the N x Ny mesh (Ny = None: N x N) of the box [lo, hi]"""
         L = lib()
         self.L = L
-        self.N = N
+        self.Nx, self.Ny = int(N), int(N if Ny is None else Ny)
+        self.N = self.Nx                # the square meshes' callers
+        self.lo, self.hi = (float(lo[0]), float(lo[1])), (float(hi[0]), float(hi[1]))
         # circle_level_set (cuthho_square.cpp:56-89) or, line_y given, line_level_set y - line_y (:91-124)
         self.ls = CutLevelSet(0, radius, center[0], center[1], 0.0) if line_y is None else CutLevelSet(1, 0.0, 0.0, 0.0, line_y)
-        self.h = L.cut_mesh_create(N, N, 0.0, 1.0, 0.0, 1.0)
+        self.h = L.cut_mesh_create(self.Nx, self.Ny, self.lo[0], self.hi[0], self.lo[1], self.hi[1])
         st = (L.cut_mesh_preprocess_agglomeration if agglomeration else L.cut_mesh_preprocess)(self.h, C.byref(self.ls), refsteps)
         if st != 0:
             raise RuntimeError("cut_mesh_preprocess failed: %d" % st)
@@ -485,6 +489,9 @@ class CutMesh:
         self.niface = L.cut_mesh_interface_points(self.h)
         self.cell_faces = np.array([[L.cut_mesh_cell_face(self.h, c, lf) for lf in range(4)] for c in range(self.nc)],
                                    dtype=np.uint64)
+
+    def mesh_params(self):
+        return MeshParams(self.Nx, self.Ny, self.lo[0], self.hi[0], self.lo[1], self.hi[1])
 
     def __del__(self):
         try:

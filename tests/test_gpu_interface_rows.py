@@ -42,13 +42,14 @@ def whole_mesh(N, k, kw=(), synthetic_seed=None):
         w["ops"], w["g"] = real_ops(a, N, k, **dict(kw))
         w["rec"] = a.interface_condensed_ops(k, w["ops"])
     else:                                               # as test_gpu_interface_condensed.synthetic_records
-        a.cut_preprocess(N, refsteps=4, **dict(kw))
+        a.cut_preprocess(N, **{"refsteps": 4, **dict(kw)})
         qi = a.ctx.interface_condensed_query(k)
         gen = torch.Generator(device=a.device).manual_seed(synthetic_seed)
         f64 = dict(dtype=torch.float64, device=a.device)
         w["rec"] = {"cond": torch.rand(a.ncells * qi.cond_doubles, generator=gen, **f64) - 0.5,
                     "cond_cut": torch.rand(max(a.ncut * qi.cond_cut_doubles, 1), generator=gen, **f64) - 0.5}
-        w["g"] = (torch.rand(2 * N * (N + 1) * (k + 1), generator=gen, **f64) - 0.5).reshape(-1, k + 1)
+        Ny = dict(kw).get("Ny", N)
+        w["g"] = (torch.rand((N * (Ny + 1) + (N + 1) * Ny) * (k + 1), generator=gen, **f64) - 0.5).reshape(-1, k + 1)
     w["rp"], w["ci"] = a.interface_condensed_csr_pattern(k)
     w["va"], w["RH"] = a.interface_condensed_csr_fill(k, w["rec"], w["g"])
     a.synchronize()
@@ -58,26 +59,30 @@ def whole_mesh(N, k, kw=(), synthetic_seed=None):
     return w
 
 
-def slices_of(w, N, k, rows):
-    """the whole-mesh records and Dirichlet data of the slab `rows`: (records dict, g by the slab's own faces)"""
+def slices_of(w, N, k, rows, Ny=None):
+    """the whole-mesh records and Dirichlet data of the slab `rows` of the N x Ny mesh (Ny = None: N x N): (records dict, g by the
+    slab's own faces)"""
     import torch
     cbs, fbs, nf, NF = sizes(k)
     ntri, NTRI = nf * (nf + 1) // 2, NF * (NF + 1) // 2
-    n, ncut = N * N, int((w["cut_index"] >= 0).sum())
+    Ny = N if Ny is None else Ny
+    n, ncut = N * Ny, int((w["cut_index"] >= 0).sum())
     c0, c1 = rows[0] * N, rows[1] * N
     k0, k1 = int((w["cut_index"][:c0] >= 0).sum()), int((w["cut_index"][:c1] >= 0).sum())
     cond, cc = w["rec"]["cond"], w["rec"]["cond_cut"]
     rec = {"cond": torch.cat([cond[c0 * ntri:c1 * ntri], cond[n * ntri + c0 * nf:n * ntri + c1 * nf]]),
            "cond_cut": torch.cat([cc[k0 * NTRI:k1 * NTRI], cc[ncut * NTRI + k0 * NF:ncut * NTRI + k1 * NF]])}
     frow = 2 * N + 1
-    nfl = (rows[1] - rows[0]) * frow + (frow if rows[1] < N else N)
+    nfl = (rows[1] - rows[0]) * frow + (frow if rows[1] < Ny else N)
     g = w["g"].reshape(-1, fbs)[rows[0] * frow:rows[0] * frow + nfl].contiguous()
     return rec, g, (k0, k1)
 
 
-def partition_info(a, N, k, rows):
+def partition_info(a, N, k, rows, refsteps=4):
+    """from the mesh parameters the assembler `a` was last preprocessed with (N: its Nx)"""
     from proton_amd import capi
-    return capi.interface_rows_partition_info(N, N, a.level_set, 4, rows, k)
+    assert a.Nx == N
+    return capi.interface_rows_partition_info(a.Nx, a.Ny, a.level_set, refsteps, rows, k, lo=a.lo, hi=a.hi)
 
 
 def same_info(x, y):
@@ -87,21 +92,22 @@ def same_info(x, y):
 def assemble_slabs(N, k, bounds, kw, w, synthetic):
     """every slab in its own BatchAssembler, bottom to top -> list of dict(asm, info, ops, g, rec, rp, ci, va, RH)"""
     out, halo = [], None
+    Ny, refsteps = kw.get("Ny", N), kw.get("refsteps", 4)
     for rows in zip(bounds[:-1], bounds[1:]):
         a = new_asm()
         s = {"asm": a, "rows": rows}
         if synthetic:
-            a.cut_preprocess(N, refsteps=4, rows=rows, **kw)
-            s["rec"], s["g"], _ = slices_of(w, N, k, rows)
+            a.cut_preprocess(N, rows=rows, **{"refsteps": 4, **kw})
+            s["rec"], s["g"], _ = slices_of(w, N, k, rows, Ny)
         else:
             s["ops"], s["g"] = real_ops(a, N, k, rows=rows, **kw)
             s["rec"] = a.interface_rows_ops(k, s["ops"])
         s["info"] = a.interface_rows_info(k)
-        assert same_info(s["info"], partition_info(a, N, k, rows))
+        assert same_info(s["info"], partition_info(a, N, k, rows, refsteps))
         assert s["info"].halo_recv_doubles == (0 if halo is None else halo.numel())
         s["rp"], s["ci"] = a.interface_rows_csr_pattern(k)
         s["va"], s["RH"] = a.interface_rows_csr_fill(k, s["rec"], s["g"], halo_below=halo)
-        halo = a.interface_rows_halo_pack(k, s["rec"], s["g"]).clone() if rows[1] < N else None
+        halo = a.interface_rows_halo_pack(k, s["rec"], s["g"]).clone() if rows[1] < Ny else None
         a.synchronize()
         out.append(s)
     return out
