@@ -933,6 +933,33 @@ int pa_interface_rows_csr_fill(pa_context *ctx, int face_deg, const double *d_co
                                const double *d_halo_below, double *d_values, double *d_rhs);
 int pa_interface_rows_recover(pa_context *ctx, int face_deg, const double *d_lc, const double *d_rhs, const double *d_lc_cut,
                               const double *d_rhs_cut, const double *d_g, const double *d_xF, double *d_uT);
+/* The tables of ONE SLAB of that system for pa_conjugated_gradient_rows_patch_coarse (solver_cg.hpp:63-144 with z = patch sum +
+ * P (P^T A P)^-1 P^T r where the reference has 1 / diag(A); the solve they serve is cuthho_square.cpp:1737-1743), in
+ * interface_assembler's numbering (cuthho_square.cpp:1142-1178), in which a cut face owns two blocks, built on the device from
+ * the slab's own tables.  The context is one of pa_cut_preprocess_rows -- the owned rows [row_begin, row_end) of
+ * pa_interface_rows_query -- or of pa_cut_preprocess, the one-slab case, which gives pa_interface_condensed_patches' /
+ * pa_interface_condensed_coarse's tables exactly.  The formats are those of pa_patch_precond_* / pa_coarse_precond_*; rows are
+ * GLOBAL indices of the face-only system.  No operators, no halo and no communication are needed.
+ *   Patches, in terms of pa_interface_condensed_patches' whole-mesh table.  PA_PATCH_FACE: its patches whose rows lie in
+ *   [row_begin, row_end), in order, d_patch_ptr rebased to 0; both blocks of a cut face are owned together, so the slabs' tables
+ *   concatenated are the whole-mesh table.  PA_PATCH_CELL: its patches of the slab's OWN cells (never the halo row's), one per
+ *   uncut cell and one per side of a cut cell, negative side first, by ascending cell id, with every row outside [row_begin,
+ *   row_end) deleted and a patch that keeps no row dropped: a cell of the top row of a slab that is not the last loses its top
+ *   face, both blocks of it if it is cut.  Every row lies within the range and every owned row that exists in at least one patch;
+ *   the empty row group of a cut face on the Dirichlet boundary lies in none.
+ *   Coarse: rows [row_begin, row_end) of pa_interface_condensed_coarse's whole-mesh table BIT FOR BIT -- the same hats on the
+ *   whole mesh's vertex indices, the same arithmetic --, the same ncoarse and column ids on every rank, d_p_ptr (row_end -
+ *   row_begin + 1) from 0.  PA_COARSE_ONE and PA_COARSE_BY_SIDE; by side the columns no block touches are dropped as the WHOLE
+ *   mesh decides, from the tags every rank's own preprocessing holds, not from the slab's blocks.
+ * The queries give the sizes as their whole-mesh siblings do.  Refused, before anything is written: what pa_interface_rows_*
+ * refuses, in its order (nothing here needs the cut-cell arrays or a halo); an unknown kind / parts, H < 1 or a NULL output
+ * (PA_ERR_INVALID_ARG); no interior node, or more than PA_COARSE_MAX_NODES columns (H and the count in pa_last_error()); a table
+ * of 2^31 entries or more (a coarse table of 2^29 owned rows or more).  Pending side-stream work (pa_context_set_cut_overlap) is
+ * joined first.  All four wait for the stream; no atomics: two calls give the same bits. */
+int pa_interface_rows_patches_query(pa_context *ctx, int face_deg, int kind, size_t *npatches, size_t *entries);
+int pa_interface_rows_patches(pa_context *ctx, int face_deg, int kind, int64_t *d_patch_ptr, int32_t *d_patch_rows);
+int pa_interface_rows_coarse_query(pa_context *ctx, int face_deg, int H, int parts, size_t *ncoarse, size_t *entries);
+int pa_interface_rows_coarse(pa_context *ctx, int face_deg, int H, int parts, int64_t *d_p_ptr, int32_t *d_p_cols, double *d_p_vals);
 
 /* ---- multi-GPU exchange: one process per GPU, RCCL over xGMI ------------
  * The reference is a single process without any communication.  Cells shard by rows (pa_mesh_generate's
@@ -1038,8 +1065,9 @@ int pa_conjugated_gradient_rows_patch_coarse(pa_context *ctx, const pa_cg_transp
  *   are pa_condensed_patches' of the whole mesh; the cell tables are its table with every row outside the patch's slab deleted.
  *   Coarse (basic_mesh.hpp:230-298 gives the vertex indices the hats live on), PA_COARSE_ONE only: rows [row_begin, row_end) of
  *   pa_condensed_coarse's whole-mesh table bit for bit, the same ncoarse and column ids, d_p_ptr rebased to 0.
- * Not served: PA_COARSE_BY_SIDE (PA_ERR_INVALID_ARG), the slabs of the interface problem, the single-process C++ headers; the
- * solver above takes any caller's table.  Other refusals as pa_condensed_patches / pa_condensed_coarse. */
+ * Not served: PA_COARSE_BY_SIDE (PA_ERR_INVALID_ARG), the single-process C++ headers; the slabs of the interface problem have
+ * pa_interface_rows_patches / pa_interface_rows_coarse, and the solver above takes any caller's table.  Other refusals as
+ * pa_condensed_patches / pa_condensed_coarse. */
 int pa_condensed_rows_patches_query(pa_context *ctx, pa_degree_info di, int kind, size_t *npatches, size_t *entries);
 int pa_condensed_rows_patches(pa_context *ctx, pa_degree_info di, int kind, int64_t *d_patch_ptr, int32_t *d_patch_rows);
 int pa_condensed_rows_coarse_query(pa_context *ctx, pa_degree_info di, int H, int parts, size_t *ncoarse, size_t *entries);

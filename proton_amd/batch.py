@@ -958,6 +958,29 @@ class BatchAssembler:
                                         _ptr(g), xF.data_ptr(), uT.data_ptr())
         return uT[:n]
 
+    def interface_rows_patches(self, fd, kind):
+        """the slab's patch table for conjugated_gradient_rows_patch_coarse: kind "face" (the whole-mesh face patches of the owned
+        rows) or "cell" (the patches of the slab's own cells and cell sides, rows outside the owned range deleted); rows are global
+        -> (patch_ptr int64 [npatches + 1], patch_rows int32)"""
+        kind = {"face": capi.PATCH_FACE, "cell": capi.PATCH_CELL}.get(kind, kind)
+        npatches, entries = self.ctx.interface_rows_patches_query(fd, kind)
+        ptr = torch.empty(npatches + 1, dtype=torch.int64, device=self.device)
+        rows = torch.empty(max(entries, 1), dtype=torch.int32, device=self.device)
+        self.ctx.interface_rows_patches(fd, kind, ptr.data_ptr(), rows.data_ptr())
+        return ptr, rows[:entries]
+
+    def interface_rows_coarse(self, fd, H, parts="side"):
+        """the owned rows of interface_condensed_coarse's whole-mesh table, the same ncoarse and columns on every slab; parts "one"
+        or "side" -> (p_ptr int64 [owned rows + 1] from 0, p_cols int32, p_vals float64, ncoarse)"""
+        parts = {"one": capi.COARSE_ONE, "side": capi.COARSE_BY_SIDE}.get(parts, parts)
+        ncoarse, entries = self.ctx.interface_rows_coarse_query(fd, H, parts)
+        qi = self.ctx.interface_rows_query(fd)
+        ptr = torch.empty(qi.row_end - qi.row_begin + 1, dtype=torch.int64, device=self.device)
+        cols = torch.empty(max(entries, 1), dtype=torch.int32, device=self.device)
+        vals = torch.empty(max(entries, 1), dtype=torch.float64, device=self.device)
+        self.ctx.interface_rows_coarse(fd, H, parts, ptr.data_ptr(), cols.data_ptr(), vals.data_ptr())
+        return ptr, cols[:entries], vals[:entries], ncoarse
+
     def interface_cell_offsets(self, fd):
         out = torch.empty((self.ncells, 2), dtype=torch.int64, device=self.device)
         self.ctx.interface_cell_offsets(fd, out.data_ptr())

@@ -56,6 +56,7 @@ EXPORTS = [
     "pa_conjugated_gradient_rows_patch_coarse", "pa_condensed_rows_patches_query", "pa_condensed_rows_patches",
     "pa_condensed_rows_coarse_query", "pa_condensed_rows_coarse",
     "pa_interface_condensed_coarse_query", "pa_interface_condensed_coarse",
+    "pa_interface_rows_patches_query", "pa_interface_rows_patches", "pa_interface_rows_coarse_query", "pa_interface_rows_coarse",
 ]
 
 
@@ -307,6 +308,10 @@ def lib():
     L.pa_interface_rows_csr_pattern.argtypes = [vp, C.c_int, dp, dp]
     L.pa_interface_rows_csr_fill.argtypes = [vp, C.c_int] + [dp] * 6
     L.pa_interface_rows_recover.argtypes = [vp, C.c_int] + [dp] * 7
+    L.pa_interface_rows_patches_query.argtypes = [vp, C.c_int, C.c_int, C.POINTER(sz), C.POINTER(sz)]
+    L.pa_interface_rows_patches.argtypes = [vp, C.c_int, C.c_int, dp, dp]
+    L.pa_interface_rows_coarse_query.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(sz), C.POINTER(sz)]
+    L.pa_interface_rows_coarse.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, dp, dp]
     L.pa_condensed_ops_batch.argtypes = [vp, DegreeInfo, C.c_int, C.c_int, sz, sz, dp, dp, dp]
     L.pa_condensed_recover_batch.argtypes = [vp, DegreeInfo, C.c_int, C.c_int, sz, sz, dp, dp, dp, dp]
     L.pa_condensed_query.argtypes = [vp, DegreeInfo, C.POINTER(CondensedInfo)]
@@ -823,6 +828,24 @@ class Context:
 
     def interface_rows_recover(self, face_deg, lc, rhs, lc_cut, rhs_cut, g, xF, uT):
         self._ck(self._L.pa_interface_rows_recover(self.h, face_deg, lc, rhs, lc_cut, rhs_cut, g, xF, uT), "pa_interface_rows_recover")
+
+    def interface_rows_patches_query(self, face_deg, kind):
+        npatches, entries = C.c_size_t(0), C.c_size_t(0)
+        self._ck(self._L.pa_interface_rows_patches_query(self.h, face_deg, kind, C.byref(npatches), C.byref(entries)),
+                 "pa_interface_rows_patches_query")
+        return npatches.value, entries.value
+
+    def interface_rows_patches(self, face_deg, kind, patch_ptr, patch_rows):
+        self._ck(self._L.pa_interface_rows_patches(self.h, face_deg, kind, patch_ptr, patch_rows), "pa_interface_rows_patches")
+
+    def interface_rows_coarse_query(self, face_deg, H, parts):
+        ncoarse, entries = C.c_size_t(0), C.c_size_t(0)
+        self._ck(self._L.pa_interface_rows_coarse_query(self.h, face_deg, H, parts, C.byref(ncoarse), C.byref(entries)),
+                 "pa_interface_rows_coarse_query")
+        return ncoarse.value, entries.value
+
+    def interface_rows_coarse(self, face_deg, H, parts, p_ptr, p_cols, p_vals):
+        self._ck(self._L.pa_interface_rows_coarse(self.h, face_deg, H, parts, p_ptr, p_cols, p_vals), "pa_interface_rows_coarse")
 
     def cut_preprocess(self, Nx, Ny, ls, refsteps, lo=(0.0, 0.0), hi=(1.0, 1.0), rows=None):
         if rows is None:

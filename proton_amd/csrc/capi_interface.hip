@@ -604,3 +604,85 @@ int pa_interface_rows_recover(pa_context *ctx, int face_deg, const double *d_lc,
                                    d_lc, d_rhs, d_lc_cut, d_rhs_cut, d_xF, d_uT));
     return PA_OK;
 }
+
+// ---- the tables of a slab for pa_conjugated_gradient_rows_patch_coarse: the refusals of pa_interface_rows_* in its order (the
+// tables need no operators: neither the cut-cell arrays nor the halo), then the kind / H / parts and the outputs (with `write`);
+// counted on the device from the slab's extended tables, written only if they fit ----
+static int ifrows_patches(pa_context *ctx, int face_deg, int kind, bool write, size_t *npatches, size_t *entries, int64_t *d_patch_ptr,
+                          int32_t *d_patch_rows)
+{
+    const int st = ifrows_prepare(ctx, face_deg, true, true);
+    if (st != PA_OK) return st;
+    if (kind != PA_PATCH_FACE && kind != PA_PATCH_CELL) return PA_ERR_INVALID_ARG;
+    const pa::IfRowsHost &h = ctx->cut.ifrows.h;
+    if (write ? (!d_patch_ptr || (h.q1 > h.q0 && !d_patch_rows)) : (!npatches || !entries)) return PA_ERR_INVALID_ARG;
+    uint64_t np = 0, ne = 0;
+    PA_HIP(ctx, pa::ifrows_patches(ctx->stream, ifrows_mesh(ctx), h.nh, (int32_t)h.q0, (int32_t)h.q1, (int64_t)h.fb0, face_deg,
+                                   kind == PA_PATCH_FACE ? pa::IF_PATCH_FACE : pa::IF_PATCH_CELL, &np, &ne, write ? d_patch_ptr : nullptr,
+                                   d_patch_rows));
+    if (ne >= ((uint64_t)1 << 31)) {                      // int32 slots of pa_patch_precond_*
+        ctx->last_error = "pa_interface_rows_patches: the table has 2^31 entries or more";
+        return PA_ERR_INVALID_ARG;
+    }
+    if (npatches) *npatches = (size_t)np;
+    if (entries) *entries = (size_t)ne;
+    return PA_OK;
+}
+
+int pa_interface_rows_patches_query(pa_context *ctx, int face_deg, int kind, size_t *npatches, size_t *entries)
+{
+    if (!ctx) return PA_ERR_INVALID_ARG;
+    return ifrows_patches(ctx, face_deg, kind, false, npatches, entries, nullptr, nullptr);
+}
+
+int pa_interface_rows_patches(pa_context *ctx, int face_deg, int kind, int64_t *d_patch_ptr, int32_t *d_patch_rows)
+{
+    if (!ctx) return PA_ERR_INVALID_ARG;
+    return ifrows_patches(ctx, face_deg, kind, true, nullptr, nullptr, d_patch_ptr, d_patch_rows);
+}
+
+static int ifrows_coarse(pa_context *ctx, const char *who, int face_deg, int H, int parts, bool write, size_t *ncoarse, size_t *entries,
+                         int64_t *d_p_ptr, int32_t *d_p_cols, double *d_p_vals)
+{
+    const int st = ifrows_prepare(ctx, face_deg, true, true);
+    if (st != PA_OK) return st;
+    if (H < 1 || (parts != PA_COARSE_ONE && parts != PA_COARSE_BY_SIDE)) return PA_ERR_INVALID_ARG;
+    if (write ? (!d_p_ptr || !d_p_cols || !d_p_vals) : (!ncoarse || !entries)) return PA_ERR_INVALID_ARG;
+    auto &r = ctx->cut.ifrows;
+    const pa::CutMeshHost &cm = *ctx->cut.host;
+    if ((uint64_t)(r.h.q1 - r.h.q0) * (face_deg + 1) >= ((uint64_t)1 << 29)) {      // 4 entries a row: below 2^31 (pa_coarse_precond_*'s limit)
+        ctx->last_error = std::string(who) + ": the table may have 2^31 entries or more (2^29 owned rows and more)";
+        return PA_ERR_INVALID_ARG;
+    }
+    if (parts == PA_COARSE_BY_SIDE && !r.face_loc_all.get()) {          // the whole mesh's tags: every rank's own preprocessing left them
+        pa::DeviceBuf<int8_t> all;
+        PA_HIP(ctx, all.upload(cm.face_loc, ctx->stream));
+        PA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        r.face_loc_all = std::move(all);
+    }
+    const pa::StructuredMesh sm = ctx->faces.sm;
+    pa::IfRowsCoarseMesh m;
+    m.im = ifrows_mesh(ctx); m.sm = sm;
+    m.face0 = (sm.row0 - (sm.row0 > 0 ? 1u : 0u)) * pa::sm_face_row(sm);
+    m.q0 = (int32_t)r.h.q0; m.q1 = (int32_t)r.h.q1;
+    m.by_side = parts == PA_COARSE_BY_SIDE ? 1 : 0;
+    m.face_loc_all = r.face_loc_all.get(); m.nfaces_all = (uint32_t)cm.nfaces();
+    uint64_t nc = 0, ne = 0;
+    PA_HIP(ctx, pa::interface_rows_coarse(ctx->stream, m, face_deg + 1, H, &nc, &ne, write ? d_p_ptr : nullptr, d_p_cols, d_p_vals));
+    if (nc < 1 || nc > (uint64_t)PA_COARSE_MAX_NODES) return coarse_count_refused(ctx, who, H, nc);
+    if (ncoarse) *ncoarse = (size_t)nc;
+    if (entries) *entries = (size_t)ne;
+    return PA_OK;
+}
+
+int pa_interface_rows_coarse_query(pa_context *ctx, int face_deg, int H, int parts, size_t *ncoarse, size_t *entries)
+{
+    if (!ctx) return PA_ERR_INVALID_ARG;
+    return ifrows_coarse(ctx, "pa_interface_rows_coarse_query", face_deg, H, parts, false, ncoarse, entries, nullptr, nullptr, nullptr);
+}
+
+int pa_interface_rows_coarse(pa_context *ctx, int face_deg, int H, int parts, int64_t *d_p_ptr, int32_t *d_p_cols, double *d_p_vals)
+{
+    if (!ctx) return PA_ERR_INVALID_ARG;
+    return ifrows_coarse(ctx, "pa_interface_rows_coarse", face_deg, H, parts, true, nullptr, nullptr, d_p_ptr, d_p_cols, d_p_vals);
+}

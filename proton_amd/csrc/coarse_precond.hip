@@ -19,8 +19,8 @@
 //           loop of solver.hip.  No iteration of its own here.
 //   table:  the hats and the kernels that count, place and write them are stated once, for the numbering of pa_condensed_csr_pattern
 //           (a non-Dirichlet face owns one block), for the rows of it that a slab of the generator mesh owns, and for
-//           interface_assembler's (a cut face owns two: the solve of cuthho_square.cpp:1737-1743); a mesh type says what a face gives
-//           (face_blocks).
+//           interface_assembler's (a cut face owns two: the solve of cuthho_square.cpp:1737-1743) and the rows of it that a slab of
+//           the interface problem owns; a mesh type says what a face gives (face_blocks).
 //   ranks:  for the row-partitioned solve (rows_precond.hip) the factor and the apply come in their stages: coarse_galerkin forms a
 //           rank's addend P_r^T (A_r P_window) of A_c with P given for the window of columns the rank's rows read (its ends packed,
 //           exchanged and unpacked here), the lower triangle travels packed, coarse_cholesky factors the sum; coarse_restrict and
@@ -791,6 +791,67 @@ __device__ __forceinline__ FaceBlocks face_blocks(const SlabCoarseMesh &m, int H
     return o;
 }
 
+// a slab of the interface problem (interface_rows.hpp): im holds the extended tables -- the slab's faces and the halo row's below
+// them --, extended face f is global face face0 + f, whose end points the closed form gives, and the slab owns the extended blocks
+// [q0, q1), block q - q0 of its rows.  The halo row's faces give nothing.  An unowned block follows the nearest owning face below
+// it as on the whole mesh; where there is none in the extended range it precedes the range's first owning face, whose block is 0.
+__device__ __forceinline__ FaceBlocks face_blocks(const IfRowsCoarseMesh &m, int H, uint32_t f)
+{
+    FaceBlocks o;
+    o.h.n = 0; o.nb = 0; o.unowned = -1;
+    const int32_t b = m.im.face_table[f];
+    const bool cut = m.im.face_loc[f] == IF_LOC_CUT;
+    if (b < 0) {
+        if (!cut) return o;
+        int32_t at = 0;
+        bool found = false;
+        for (uint32_t g = f; g-- > 0;) {
+            const int32_t bg = m.im.face_table[g];
+            const bool cg = m.im.face_loc[g] == IF_LOC_CUT;
+            if (bg >= 0) { at += bg + (cg ? 2 : 1); found = true; break; }
+            at += cg ? 1 : 0;
+        }
+        if (!found) {                                    // f and the unowned blocks up to the first owning face: below block 0
+            at = 0;
+            for (uint32_t g = f; g < m.im.nfaces && m.im.face_table[g] < 0; ++g) at -= m.im.face_loc[g] == IF_LOC_CUT ? 1 : 0;
+        }
+        if (at >= m.q0 && at < m.q1) o.unowned = at - m.q0;
+        return o;
+    }
+    if (b < m.q0 || b >= m.q1) return o;                 // (both blocks of a cut face are owned together)
+    o.nb = cut ? 2 : 1;
+    o.q[0] = b - m.q0; o.q[1] = b - m.q0 + 1;
+    o.part[0] = (m.by_side && !cut && m.im.face_loc[f] == 1) ? 1 : 0;  // 1: PA_LOC_POSITIVE
+    o.part[1] = m.by_side ? 1 : 0;
+    uint32_t lo, hi;
+    bool dirichlet;
+    int32_t comp;
+    sm_face_decode(m.sm, m.face0 + f, lo, hi, dirichlet, comp);
+    o.h = point_hats(m.sm, H, lo, hi);
+    return o;
+}
+
+// the tags of the whole mesh, which every rank of a row partition holds: what face f gives to the parts by side -- the hats and
+// parts of face_blocks(IfCoarseMesh), no blocks to write to
+struct IfTagsMesh { StructuredMesh sm; const int8_t *face_loc; };
+__device__ __forceinline__ FaceBlocks face_blocks(const IfTagsMesh &m, int H, uint32_t f)
+{
+    FaceBlocks o;
+    o.h.n = 0; o.nb = 0; o.unowned = -1;
+    uint32_t lo, hi;
+    bool dirichlet;
+    int32_t comp;
+    sm_face_decode(m.sm, f, lo, hi, dirichlet, comp);
+    if (dirichlet) return o;
+    const bool cut = m.face_loc[f] == IF_LOC_CUT;
+    o.nb = cut ? 2 : 1;
+    o.q[0] = o.q[1] = 0;
+    o.part[0] = (!cut && m.face_loc[f] == 1) ? 1 : 0;
+    o.part[1] = 1;
+    o.h = point_hats(m.sm, H, lo, hi);
+    return o;
+}
+
 __device__ __forceinline__ uint32_t face_entries(const FaceBlocks &b, int fbs)
 {
     uint32_t e = (uint32_t)b.h.n;
@@ -807,7 +868,10 @@ inline uint64_t coarse_blocks(const IfCoarseMesh &m) { return m.im.num_other_fac
 inline uint64_t coarse_blocks(const SlabCoarseMesh &m) { return (uint64_t)(m.p1 - m.p0); }
 inline bool coarse_by_side(const CoarseMesh &m) { return m.face_loc != nullptr; }
 inline bool coarse_by_side(const IfCoarseMesh &m) { return m.by_side != 0; }
+inline uint32_t coarse_faces(const IfRowsCoarseMesh &m) { return m.im.nfaces; }
+inline uint64_t coarse_blocks(const IfRowsCoarseMesh &m) { return (uint64_t)(m.q1 - m.q0); }
 inline bool coarse_by_side(const SlabCoarseMesh &) { return false; }
+inline bool coarse_by_side(const IfRowsCoarseMesh &m) { return m.by_side != 0; }
 
 // by side: used[part nnodes + node] = some block of the part meets the node's hat (every writer stores the same byte)
 template <class Mesh>
@@ -818,6 +882,20 @@ __global__ __launch_bounds__(RB) void coarse_used_kernel(Mesh m, uint32_t nfaces
     const FaceBlocks b = face_blocks(m, H, f);
     for (int s = 0; s < b.nb; ++s)
         for (int k = 0; k < b.h.n; ++k) used[(size_t)b.part[s] * nnodes + b.h.node[k]] = 1;
+}
+
+// the faces that decide which columns stay: the table's own, or -- a slab -- the whole mesh's by its tags
+template <class Mesh>
+void coarse_mark_used(hipStream_t stream, const Mesh &m, int H, uint32_t nnodes, uint8_t *used)
+{
+    const uint32_t nfaces = coarse_faces(m);
+    hipLaunchKernelGGL((coarse_used_kernel<Mesh>), dim3((nfaces + RB - 1) / RB), dim3(RB), 0, stream, m, nfaces, H, nnodes, used);
+}
+void coarse_mark_used(hipStream_t stream, const IfRowsCoarseMesh &m, int H, uint32_t nnodes, uint8_t *used)
+{
+    const IfTagsMesh tags{m.sm, m.face_loc_all};
+    hipLaunchKernelGGL((coarse_used_kernel<IfTagsMesh>), dim3((m.nfaces_all + RB - 1) / RB), dim3(RB), 0, stream, tags, m.nfaces_all, H, nnodes,
+                       used);
 }
 
 // per block of faces: its entries
@@ -898,7 +976,7 @@ hipError_t coarse_table(hipStream_t stream, const Mesh &m, int fbs, int H, uint6
         if (!tmp.alloc(&used, items) || !tmp.alloc(&counts, (size_t)nb + 1) || !tmp.alloc(&unused, items) || !tmp.alloc(&index, items))
             return tmp.error();
         if (!tmp.ok(hipMemsetAsync(used, 0, items, stream))) return tmp.error();
-        hipLaunchKernelGGL((coarse_used_kernel<Mesh>), dim3((nfaces + RB - 1) / RB), dim3(RB), 0, stream, m, nfaces, H, nnodes, used);
+        coarse_mark_used(stream, m, H, nnodes, used);
         hipLaunchKernelGGL(active_count_kernel, dim3(nb), dim3(SCAN_BLOCK), 0, stream, used, items, counts);
         hipLaunchKernelGGL(active_block_scan_kernel, dim3(1), dim3(SCAN_BLOCK), 0, stream, counts, nb);
         hipLaunchKernelGGL(active_tables_kernel, dim3(nb), dim3(SCAN_BLOCK), 0, stream, used, items, counts, unused, index);
@@ -942,6 +1020,12 @@ hipError_t condensed_rows_coarse(hipStream_t stream, const SlabCoarseMesh &m, in
 
 hipError_t interface_condensed_coarse(hipStream_t stream, const IfCoarseMesh &m, int fbs, int H, uint64_t *ncoarse, uint64_t *entries,
                                       int64_t *ptr, int32_t *cols, double *vals)
+{
+    return coarse_table(stream, m, fbs, H, ncoarse, entries, ptr, cols, vals);
+}
+
+hipError_t interface_rows_coarse(hipStream_t stream, const IfRowsCoarseMesh &m, int fbs, int H, uint64_t *ncoarse, uint64_t *entries,
+                                 int64_t *ptr, int32_t *cols, double *vals)
 {
     return coarse_table(stream, m, fbs, H, ncoarse, entries, ptr, cols, vals);
 }

@@ -127,4 +127,22 @@ struct IfCoarseMesh {
 hipError_t interface_condensed_coarse(hipStream_t stream, const IfCoarseMesh &m, int fbs, int H, uint64_t *ncoarse, uint64_t *entries,
                                       int64_t *ptr, int32_t *cols, double *vals);
 
+// ---- rows [row_begin, row_end) of that table for a slab of the interface problem (pa_interface_rows_coarse) ----
+// im: the slab's extended tables (interface_rows.hpp: its own faces and those of the cell row below), extended face f being
+// global face face0 + f of sm's whole mesh, whose vertex indices the hats live on; the slab owns the extended blocks [q0, q1),
+// row (q - q0) fbs + k of the table.  by_side: the columns that stay are decided by the whole mesh, from the tags every rank
+// holds (face_loc_all, nfaces_all: device copy of the whole-mesh face_loc), never by the slab's own blocks: the same ncoarse and
+// column ids on every slab.  ptr starts at 0.
+struct IfRowsCoarseMesh {
+    IfCsrMesh im;
+    StructuredMesh sm;
+    uint32_t face0;
+    int32_t q0, q1;
+    int by_side;
+    const int8_t *face_loc_all;
+    uint32_t nfaces_all;
+};
+hipError_t interface_rows_coarse(hipStream_t stream, const IfRowsCoarseMesh &m, int fbs, int H, uint64_t *ncoarse, uint64_t *entries,
+                                 int64_t *ptr, int32_t *cols, double *vals);
+
 }  // namespace pa

@@ -87,6 +87,7 @@ struct IfRowsDev {
     bool ready() const { return d.cell_faces.get() != nullptr; }
     IfCsrOwner tables;
     uint64_t v0 = 0, nnz = 0;                 // first entry of the owned rows in the tables' cvstart; entries of the owned rows
+    DeviceBuf<int8_t> face_loc_all;           // the WHOLE mesh's face tags (pa_interface_rows_coarse by side), on first use
 };
 
 // cutHHO state: host tags and their device copies, and everything built over them

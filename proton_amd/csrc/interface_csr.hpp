@@ -168,5 +168,15 @@ constexpr int IF_PATCH_FACE = 0, IF_PATCH_CELL = 1;     // PA_PATCH_FACE, PA_PAT
 // waits for the stream
 hipError_t ifcond_patches(hipStream_t stream, const IfCsrMesh &m, int face_deg, int kind, uint64_t *npatches, uint64_t *entries,
                           int64_t *ptr, int32_t *rows);
+// The same for a slab of cell rows (pa_interface_rows_patches): m holds the slab's extended tables (interface_rows.hpp), whose
+// first halo_cells cells are the row below and give no patch; of an item's blocks those within the owned range [q0, q1) stay, and
+// block q gives the GLOBAL rows of block fb0 + q.  A patch that keeps no block is dropped; ptr starts at 0.
+struct IfPatchRange {
+    size_t item0;                               // the first item
+    int32_t q0, q1;                             // the blocks that stay
+    int64_t shift;                              // block q is block shift + q of the rows
+};
+hipError_t ifrows_patches(hipStream_t stream, const IfCsrMesh &m, uint32_t halo_cells, int32_t q0, int32_t q1, int64_t fb0, int face_deg,
+                          int kind, uint64_t *npatches, uint64_t *entries, int64_t *ptr, int32_t *rows);
 
 }  // namespace pa

@@ -528,18 +528,20 @@ hipError_t slab_cell_patches(hipStream_t stream, const StructuredMesh &sm, int32
     return tmp.error();
 }
 
-// ---- the patch tables of the interface problem's face-only system (pa_interface_condensed_patches: interface_assembler's numbering, in
-// which a cut face owns two blocks; the tables of IfCsrMesh alone, counted and placed by the scans of scan.hpp) --------------------------
+// ---- the patch tables of the interface problem's face-only system (pa_interface_condensed_patches, pa_interface_rows_patches:
+// interface_assembler's numbering, in which a cut face owns two blocks; the tables of IfCsrMesh alone -- the whole mesh's, or a slab's
+// extended ones with the part of them that counts (IfPatchRange) --, counted and placed by the scans of scan.hpp) ----------------------
 // An item is what may give a patch: a face (IF_PATCH_FACE), or side s of cell X as item 2 X + s (IF_PATCH_CELL; an uncut cell is
-// its item 2 X alone).  -> the item's face blocks in the patch's order (none: no patch)
-__device__ __forceinline__ int ifp_blocks(const IfCsrMesh &m, int kind, size_t item, int32_t *blk)
+// its item 2 X alone).  -> the item's face blocks within the range in the patch's order (none: no patch)
+__device__ __forceinline__ int ifp_blocks(const IfCsrMesh &m, const IfPatchRange &r, int kind, size_t item, int32_t *blk)
 {
     int n = 0;
+    auto take = [&](int32_t q) { if (q >= r.q0 && q < r.q1) blk[n++] = q; };
     if (kind == IF_PATCH_FACE) {
         const int32_t b = m.face_table[item];
         if (b < 0) return 0;
-        blk[n++] = b;
-        if (m.face_loc[item] == IF_LOC_CUT) blk[n++] = b + 1;
+        take(b);
+        if (m.face_loc[item] == IF_LOC_CUT) take(b + 1);
         return n;
     }
     const size_t X = item >> 1;
@@ -552,53 +554,54 @@ __device__ __forceinline__ int ifp_blocks(const IfCsrMesh &m, int kind, size_t i
         if (b < 0) continue;
         const int8_t fl = m.face_loc[f];
         if (cut && fl != IF_LOC_CUT && fl != s) continue;                                   // an uncut face: on its own side only
-        blk[n++] = b + ((cut && s == 1 && fl == IF_LOC_CUT) ? 1 : 0);                       // dup of if_global_index
+        take(b + ((cut && s == 1 && fl == IF_LOC_CUT) ? 1 : 0));                            // dup of if_global_index
     }
     return n;
 }
 
 // per block of items: its patches (bp) and its face blocks (bb)
-__global__ __launch_bounds__(SCAN_BLOCK) void ifp_count_kernel(IfCsrMesh m, int kind, size_t nitems, uint32_t *bp, uint32_t *bb)
+__global__ __launch_bounds__(SCAN_BLOCK) void ifp_count_kernel(IfCsrMesh m, IfPatchRange r, int kind, size_t nitems, uint32_t *bp, uint32_t *bb)
 {
     __shared__ uint32_t sh[SCAN_BLOCK / 64];
-    const size_t item = (size_t)blockIdx.x * SCAN_BLOCK + threadIdx.x;
+    const size_t i = (size_t)blockIdx.x * SCAN_BLOCK + threadIdx.x;
     int32_t blk[4];
-    const uint32_t nb = item < nitems ? (uint32_t)ifp_blocks(m, kind, item, blk) : 0u;
+    const uint32_t nb = i < nitems ? (uint32_t)ifp_blocks(m, r, kind, r.item0 + i, blk) : 0u;
     uint32_t tp, tb;
     block_exclusive_scan(nb ? 1u : 0u, sh, tp);
     block_exclusive_scan(nb, sh, tb);
     if (threadIdx.x == 0) { bp[blockIdx.x] = tp; bb[blockIdx.x] = tb; }
 }
 
-// bp, bb scanned (their totals at [nblk]): every item with blocks writes its patch
-__global__ __launch_bounds__(SCAN_BLOCK) void ifp_fill_kernel(IfCsrMesh m, int kind, size_t nitems, int fbs, const uint32_t *bp,
+// bp, bb scanned (their totals at [nblk]): every item with blocks writes its patch; block q gives the rows of block r.shift + q,
+// formed in 64 bits (the system has fewer than 2^31 rows, the extended numbering's blocks need not start at the system's)
+__global__ __launch_bounds__(SCAN_BLOCK) void ifp_fill_kernel(IfCsrMesh m, IfPatchRange r, int kind, size_t nitems, int fbs, const uint32_t *bp,
                                                               const uint32_t *bb, uint32_t nblk, int64_t *ptr, int32_t *rows)
 {
     __shared__ uint32_t sh[SCAN_BLOCK / 64];
-    const size_t item = (size_t)blockIdx.x * SCAN_BLOCK + threadIdx.x;
+    const size_t i = (size_t)blockIdx.x * SCAN_BLOCK + threadIdx.x;
     int32_t blk[4];
-    const uint32_t nb = item < nitems ? (uint32_t)ifp_blocks(m, kind, item, blk) : 0u;
+    const uint32_t nb = i < nitems ? (uint32_t)ifp_blocks(m, r, kind, r.item0 + i, blk) : 0u;
     uint32_t tp, tb;
     const uint32_t p = bp[blockIdx.x] + block_exclusive_scan(nb ? 1u : 0u, sh, tp);
     const uint32_t b0 = bb[blockIdx.x] + block_exclusive_scan(nb, sh, tb);
-    if (item == 0) ptr[bp[nblk]] = (int64_t)bb[nblk] * fbs;
+    if (i == 0) ptr[bp[nblk]] = (int64_t)bb[nblk] * fbs;
     if (nb == 0) return;
     int64_t at = (int64_t)b0 * fbs;
     ptr[p] = at;
-    for (uint32_t i = 0; i < nb; ++i)
-        for (int k = 0; k < fbs; ++k) rows[at++] = blk[i] * fbs + k;
+    for (uint32_t j = 0; j < nb; ++j)
+        for (int k = 0; k < fbs; ++k) rows[at++] = (int32_t)((r.shift + blk[j]) * fbs + k);
 }
 
-hipError_t ifcond_patches(hipStream_t stream, const IfCsrMesh &m, int face_deg, int kind, uint64_t *npatches, uint64_t *entries,
-                          int64_t *ptr, int32_t *rows)
+// the table of nitems items from r.item0 on
+static hipError_t ifp_table(hipStream_t stream, const IfCsrMesh &m, const IfPatchRange &r, int face_deg, int kind, size_t nitems,
+                            uint64_t *npatches, uint64_t *entries, int64_t *ptr, int32_t *rows)
 {
     const int fbs = if_dims(face_deg).fbs;
-    const size_t nitems = kind == IF_PATCH_FACE ? (size_t)m.nfaces : 2 * (size_t)m.ncells;
     const uint32_t nblk = (uint32_t)(nitems ? (nitems + SCAN_BLOCK - 1) / SCAN_BLOCK : 1);
     DeviceTmp tmp(stream);
     uint32_t *bp = nullptr, *bb = nullptr;
     if (!tmp.alloc(&bp, (size_t)nblk + 1) || !tmp.alloc(&bb, (size_t)nblk + 1)) return tmp.error();
-    hipLaunchKernelGGL(ifp_count_kernel, dim3(nblk), dim3(SCAN_BLOCK), 0, stream, m, kind, nitems, bp, bb);
+    hipLaunchKernelGGL(ifp_count_kernel, dim3(nblk), dim3(SCAN_BLOCK), 0, stream, m, r, kind, nitems, bp, bb);
     hipLaunchKernelGGL(active_block_scan_kernel, dim3(1), dim3(SCAN_BLOCK), 0, stream, bp, nblk);
     hipLaunchKernelGGL(active_block_scan_kernel, dim3(1), dim3(SCAN_BLOCK), 0, stream, bb, nblk);
     uint32_t tot[2] = {0, 0};
@@ -608,9 +611,28 @@ hipError_t ifcond_patches(hipStream_t stream, const IfCsrMesh &m, int face_deg, 
     *npatches = tot[0];
     *entries = (uint64_t)tot[1] * fbs;
     if (ptr == nullptr || *entries >= ((uint64_t)1 << 31)) return hipSuccess;
-    hipLaunchKernelGGL(ifp_fill_kernel, dim3(nblk), dim3(SCAN_BLOCK), 0, stream, m, kind, nitems, fbs, bp, bb, nblk, ptr, rows);
+    hipLaunchKernelGGL(ifp_fill_kernel, dim3(nblk), dim3(SCAN_BLOCK), 0, stream, m, r, kind, nitems, fbs, bp, bb, nblk, ptr, rows);
     if (tmp.ok(hipGetLastError())) tmp.ok(hipStreamSynchronize(stream));       // the block offsets live until the kernel has read them
     return tmp.error();
+}
+
+hipError_t ifcond_patches(hipStream_t stream, const IfCsrMesh &m, int face_deg, int kind, uint64_t *npatches, uint64_t *entries,
+                          int64_t *ptr, int32_t *rows)
+{
+    const IfPatchRange whole{0, 0, INT32_MAX, 0};
+    return ifp_table(stream, m, whole, face_deg, kind, kind == IF_PATCH_FACE ? (size_t)m.nfaces : 2 * (size_t)m.ncells, npatches, entries,
+                     ptr, rows);
+}
+
+// a slab: every face of the extended tables may give a patch (its blocks are owned or not, both of a cut face together), of the
+// cells the slab's own, which follow the halo_cells cells of the row below
+hipError_t ifrows_patches(hipStream_t stream, const IfCsrMesh &m, uint32_t halo_cells, int32_t q0, int32_t q1, int64_t fb0, int face_deg,
+                          int kind, uint64_t *npatches, uint64_t *entries, int64_t *ptr, int32_t *rows)
+{
+    const bool faces = kind == IF_PATCH_FACE;
+    const IfPatchRange slab{faces ? (size_t)0 : 2 * (size_t)halo_cells, q0, q1, fb0};
+    return ifp_table(stream, m, slab, face_deg, kind, faces ? (size_t)m.nfaces : 2 * (size_t)(m.ncells - halo_cells), npatches, entries, ptr,
+                     rows);
 }
 
 }  // namespace pa
