@@ -1,5 +1,5 @@
 // capi.hip -- the C ABI declared in include/proton_amd.h: the registry of instantiated kernels, sizes, the context and its memory,
-// the mesh entry points.  The workloads are in capi_local_ops.hip, capi_assembly.hip, capi_obstacle.hip, capi_cut.hip and
+// the mesh entry points.  The workloads are in capi_local_ops.hip, capi_assembly.hip, capi_solver.hip, capi_obstacle.hip, capi_cut.hip and
 // capi_interface.hip.  Thin: argument validation, kernel selection, launches on the context's stream.
 #include <hip/hip_runtime.h>
 

@@ -15,8 +15,8 @@
 //   apply:  restrict (a workgroup per coarse row: lane-strided sums, block_sum's tree), t = W (P^T r) (a wavefront per row), u = W^T t
 //           (64 columns x 4 row groups per workgroup), prolong (a gather of at most 4 terms per fine row, added to z or not, with the
 //           block partials of r . z).  No dependent chain of length ncoarse, no floating-point atomics: the same bits on every call.
-//   solve:  conjugated_gradient_patch_coarse validates and factors both levels and hands patch_apply + coarse_apply to the one-rank
-//           loop of solver.hip.  No iteration of its own here.
+//   solve:  not here: rows_precond.hip calls coarse_query, coarse_validate, the factor and the apply in their order, after the patch
+//           level's, for every solver (TwoLevel).
 //   table:  the hats and the kernels that count, place and write them are stated once, for the numbering of pa_condensed_csr_pattern
 //           (a non-Dirichlet face owns one block), for the rows of it that a slab of the generator mesh owns, and for
 //           interface_assembler's (a cut face owns two: the solve of cuthho_square.cpp:1737-1743) and the rows of it that a slab of
@@ -33,7 +33,6 @@
 #include "cg.hpp"
 #include "coarse_precond.hpp"
 #include "device_tmp.hpp"
-#include "patch_precond.hpp"
 #include "scan.hpp"
 
 namespace pa {
@@ -602,80 +601,6 @@ void coarse_correct(hipStream_t stream, const CoarseTable &t, const CoarseSizes 
                        part_rz);
 }
 
-// ---- the solver ---------------------------------------------------------------------------------------------------------------------
-// both tables are validated and factored here; the iteration is solver.hip's one-rank loop with the two applies as its preconditioner
-hipError_t conjugated_gradient_patch_coarse(hipStream_t stream, size_t n, const int64_t *rowptr, const int32_t *colind,
-                                            const double *values, const double *b, double *x, size_t npatches, const int64_t *patch_ptr,
-                                            const int32_t *patch_rows, size_t ncoarse, const int64_t *p_ptr, const int32_t *p_cols,
-                                            const double *p_vals, double convergence_threshold, double divergence_threshold,
-                                            size_t max_iter, int *exit_reason, size_t *iterations, double *relative_residual, int *status,
-                                            int *refusal, int32_t *pivot)
-{
-    *status = 0;
-    *refusal = 0;
-    *pivot = 0;
-    size_t iter = 0;
-    int reason = 0;
-    double rr = 0.0;
-    hipError_t e = hipSuccess;
-    if (n) {
-        // the patches: table, then factors (a failed pivot is reported after the coarse table has been judged)
-        PatchSizes sz;
-        e = patch_query(stream, n, npatches, patch_ptr, &sz, refusal);
-        if (e != hipSuccess) return e;
-        if (*refusal) { *status = 1; return hipSuccess; }
-        const PatchTable t{n, npatches, patch_ptr, patch_rows};
-        DeviceTmp tmp(stream);
-        double *factors = nullptr, *z = nullptr;
-        int32_t *slots = nullptr, *info = nullptr;
-        char *scratch = nullptr;
-        if (!tmp.alloc(&factors, (size_t)sz.factor_doubles + 1) || !tmp.alloc(&z, n) || !tmp.alloc(&slots, (size_t)sz.slot_ints) ||
-            !tmp.alloc(&info, npatches + 1) || !tmp.alloc(&scratch, (size_t)sz.scratch_bytes))
-            return tmp.error();
-        size_t failed = 0;
-        e = patch_factor(stream, rowptr, colind, values, t, sz, factors, slots, scratch, info, refusal, &failed);
-        if (e != hipSuccess) return e;
-        if (*refusal) { *status = 1; return hipSuccess; }
-        // the coarse level
-        CoarseSizes csz;
-        e = coarse_query(stream, n, ncoarse, p_ptr, &csz, refusal);
-        if (e != hipSuccess) return e;
-        if (*refusal) { *status = 3; return hipSuccess; }
-        const CoarseTable ct{n, ncoarse, p_ptr, p_cols, p_vals};
-        char *cpt = nullptr, *cscratch = nullptr;
-        double *cfactor = nullptr;
-        if (!tmp.alloc(&cpt, (size_t)csz.pt_bytes) || !tmp.alloc(&cfactor, (size_t)csz.factor_doubles) ||
-            !tmp.alloc(&cscratch, (size_t)csz.scratch_bytes))
-            return tmp.error();
-        e = coarse_validate(stream, ct, csz, cscratch, refusal);
-        if (e != hipSuccess) return e;
-        if (*refusal) { *status = 3; return hipSuccess; }
-        if (failed) { *status = 2; return hipSuccess; }
-        e = coarse_factor(stream, rowptr, colind, values, ct, csz, cpt, cfactor, cscratch, nullptr, pivot, refusal);
-        if (e != hipSuccess) return e;
-        if (*refusal) { *status = 3; return hipSuccess; }
-        if (*pivot) { *status = 4; return hipSuccess; }
-        struct Applied {
-            const PatchTable &t; const PatchSizes &sz; const double *factors; const int32_t *slots; void *scratch;
-            const CoarseTable &ct; const CoarseSizes &csz; const void *cpt; const double *cfactor; void *cscratch;
-        };
-        Applied ap{t, sz, factors, slots, scratch, ct, csz, cpt, cfactor, cscratch};
-        auto apply = [](void *user, hipStream_t s, const double *r, double *zr, double *part_rz) {
-            const Applied &a = *(const Applied *)user;
-            patch_apply(s, a.t, a.sz, a.factors, a.slots, a.scratch, r, zr, nullptr);
-            coarse_apply(s, a.ct, a.csz, a.cpt, a.cfactor, a.cscratch, 1, r, zr, part_rz);
-        };
-        const CgPreconditioner pre{&ap, apply, z};
-        e = conjugated_gradient_one_rank(stream, n, CgCsr{rowptr, colind, values, nullptr}, &pre, nullptr, b, x, convergence_threshold,
-                                         divergence_threshold, max_iter, 0, &reason, &iter, &rr);
-        if (e != hipSuccess) return e;
-    }
-    if (exit_reason) *exit_reason = reason;
-    if (iterations) *iterations = iter;
-    if (relative_residual) *relative_residual = rr;
-    return hipSuccess;
-}
-
 // ---- the coarse table of the face-only system ---------------------------------------------------------------------------------------
 // Coarse lines of a direction with N cells: the vertex indices 0, H, 2 H, .. below N, and N.  Hats live in index space; the values
 // below are the table's definition and are formed without contraction: one division per 1-D hat, one product per 2-D hat.
@@ -699,14 +624,13 @@ __device__ __forceinline__ double cl_hat(int j, int i, int N, int H)
     return 0.0;
 }
 
-struct FaceHats { int n; int32_t node[4]; double v0[4], v1[4]; };
+struct FaceHats { int n = 0; int32_t node[4]; double v0[4], v1[4]; };
 
 // the interior nodes whose hat does not vanish at both of the points pa, pb (a face's ends), in node order, with the values of the
 // face's two lowest modes
 __device__ __forceinline__ FaceHats point_hats(const StructuredMesh &sm, int H, uint32_t pa, uint32_t pb)
 {
     FaceHats o;
-    o.n = 0;
     const int Nx = (int)sm.Nx, Ny = (int)sm.Ny, npr = Nx + 1;
     const int ax = (int)(pa % npr), ay = (int)(pa / npr), bx = (int)(pb % npr), by = (int)(pb / npr);
     const int nlx = cl_lines(Nx, H), nly = cl_lines(Ny, H), nix = nlx - 2;
@@ -727,14 +651,13 @@ __device__ __forceinline__ FaceHats point_hats(const StructuredMesh &sm, int H, 
 }
 
 // what face f gives: its hats, and the nb blocks that take them, each with its part; unowned: the block a face counted by the
-// numbering leaves without an owner (-1: none), whose pointers are still due
-struct FaceBlocks { FaceHats h; int nb; int32_t q[2]; int part[2]; int32_t unowned; };
+// numbering leaves without an owner (-1: none), whose pointers are still due.  The default value is a face that gives nothing.
+struct FaceBlocks { FaceHats h; int nb = 0; int32_t q[2]; int part[2]; int32_t unowned = -1; };
 
 // the numbering of pa_condensed_csr_pattern: the one block of a non-Dirichlet face
 __device__ __forceinline__ FaceBlocks face_blocks(const CoarseMesh &m, int H, uint32_t f)
 {
     FaceBlocks o;
-    o.h.n = 0; o.nb = 0; o.unowned = -1;
     const int32_t q = m.face_compress[f];
     if (q < 0) return o;
     o.nb = 1; o.q[0] = q; o.part[0] = 0;
@@ -747,30 +670,44 @@ __device__ __forceinline__ FaceBlocks face_blocks(const CoarseMesh &m, int H, ui
 }
 
 // interface_assembler's numbering: the two blocks of a cut face take the same values (the face basis of a cut face is the whole
-// face's, cuthho_square.cpp:371, 471, 594).  A cut face on the Dirichlet boundary is counted and owns nothing: its block follows
-// the blocks of the nearest owning face below it and the unowned blocks between the two.
+// face's, cuthho_square.cpp:371, 471, 594), block b in part 0 and block b + 1 in part 1 by side; an uncut face's block is in the
+// part of its side
+__device__ __forceinline__ void if_owned_blocks(FaceBlocks &o, int32_t b, bool cut, int loc, bool by_side)
+{
+    o.nb = cut ? 2 : 1;
+    o.q[0] = b; o.q[1] = b + 1;
+    o.part[0] = (by_side && !cut && loc == 1) ? 1 : 0;                 // 1: PA_LOC_POSITIVE
+    o.part[1] = by_side ? 1 : 0;
+}
+
+// A cut face on the Dirichlet boundary is counted and owns nothing: its block follows the blocks of the nearest owning face below
+// it and the unowned blocks between the two.  -> that block; *found: there is an owning face below f (none: the unowned blocks
+// below f alone were counted)
+__device__ __forceinline__ int32_t if_unowned_block(const IfCsrMesh &im, uint32_t f, bool *found)
+{
+    int32_t at = 0;
+    *found = false;
+    for (uint32_t g = f; g-- > 0;) {
+        const int32_t bg = im.face_table[g];
+        const bool cg = im.face_loc[g] == IF_LOC_CUT;
+        if (bg >= 0) { *found = true; return at + bg + (cg ? 2 : 1); }
+        at += cg ? 1 : 0;
+    }
+    return at;
+}
+
+// the whole mesh of the interface problem: a face's end points from face_pts
 __device__ __forceinline__ FaceBlocks face_blocks(const IfCoarseMesh &m, int H, uint32_t f)
 {
     FaceBlocks o;
-    o.h.n = 0; o.nb = 0; o.unowned = -1;
     const int32_t b = m.im.face_table[f];
     const bool cut = m.im.face_loc[f] == IF_LOC_CUT;
     if (b < 0) {
-        if (!cut) return o;
-        int32_t at = 0;
-        for (uint32_t g = f; g-- > 0;) {
-            const int32_t bg = m.im.face_table[g];
-            const bool cg = m.im.face_loc[g] == IF_LOC_CUT;
-            if (bg >= 0) { at += bg + (cg ? 2 : 1); break; }
-            at += cg ? 1 : 0;
-        }
-        o.unowned = at;
+        bool found;
+        if (cut) o.unowned = if_unowned_block(m.im, f, &found);
         return o;
     }
-    o.nb = cut ? 2 : 1;
-    o.q[0] = b; o.q[1] = b + 1;
-    o.part[0] = (m.by_side && !cut && m.im.face_loc[f] == 1) ? 1 : 0;  // 1: PA_LOC_POSITIVE
-    o.part[1] = m.by_side ? 1 : 0;
+    if_owned_blocks(o, b, cut, m.im.face_loc[f], m.by_side != 0);
     o.h = point_hats(m.sm, H, m.face_pts[2 * f], m.face_pts[2 * f + 1]);
     return o;
 }
@@ -780,7 +717,6 @@ __device__ __forceinline__ FaceBlocks face_blocks(const IfCoarseMesh &m, int H, 
 __device__ __forceinline__ FaceBlocks face_blocks(const SlabCoarseMesh &m, int H, uint32_t f)
 {
     FaceBlocks o;
-    o.h.n = 0; o.nb = 0; o.unowned = -1;
     uint32_t lo, hi;
     bool dirichlet;
     int32_t q;
@@ -798,19 +734,12 @@ __device__ __forceinline__ FaceBlocks face_blocks(const SlabCoarseMesh &m, int H
 __device__ __forceinline__ FaceBlocks face_blocks(const IfRowsCoarseMesh &m, int H, uint32_t f)
 {
     FaceBlocks o;
-    o.h.n = 0; o.nb = 0; o.unowned = -1;
     const int32_t b = m.im.face_table[f];
     const bool cut = m.im.face_loc[f] == IF_LOC_CUT;
     if (b < 0) {
         if (!cut) return o;
-        int32_t at = 0;
-        bool found = false;
-        for (uint32_t g = f; g-- > 0;) {
-            const int32_t bg = m.im.face_table[g];
-            const bool cg = m.im.face_loc[g] == IF_LOC_CUT;
-            if (bg >= 0) { at += bg + (cg ? 2 : 1); found = true; break; }
-            at += cg ? 1 : 0;
-        }
+        bool found;
+        int32_t at = if_unowned_block(m.im, f, &found);
         if (!found) {                                    // f and the unowned blocks up to the first owning face: below block 0
             at = 0;
             for (uint32_t g = f; g < m.im.nfaces && m.im.face_table[g] < 0; ++g) at -= m.im.face_loc[g] == IF_LOC_CUT ? 1 : 0;
@@ -819,10 +748,7 @@ __device__ __forceinline__ FaceBlocks face_blocks(const IfRowsCoarseMesh &m, int
         return o;
     }
     if (b < m.q0 || b >= m.q1) return o;                 // (both blocks of a cut face are owned together)
-    o.nb = cut ? 2 : 1;
-    o.q[0] = b - m.q0; o.q[1] = b - m.q0 + 1;
-    o.part[0] = (m.by_side && !cut && m.im.face_loc[f] == 1) ? 1 : 0;  // 1: PA_LOC_POSITIVE
-    o.part[1] = m.by_side ? 1 : 0;
+    if_owned_blocks(o, b - m.q0, cut, m.im.face_loc[f], m.by_side != 0);
     uint32_t lo, hi;
     bool dirichlet;
     int32_t comp;
@@ -837,17 +763,12 @@ struct IfTagsMesh { StructuredMesh sm; const int8_t *face_loc; };
 __device__ __forceinline__ FaceBlocks face_blocks(const IfTagsMesh &m, int H, uint32_t f)
 {
     FaceBlocks o;
-    o.h.n = 0; o.nb = 0; o.unowned = -1;
     uint32_t lo, hi;
     bool dirichlet;
     int32_t comp;
     sm_face_decode(m.sm, f, lo, hi, dirichlet, comp);
     if (dirichlet) return o;
-    const bool cut = m.face_loc[f] == IF_LOC_CUT;
-    o.nb = cut ? 2 : 1;
-    o.q[0] = o.q[1] = 0;
-    o.part[0] = (!cut && m.face_loc[f] == 1) ? 1 : 0;
-    o.part[1] = 1;
+    if_owned_blocks(o, 0, m.face_loc[f] == IF_LOC_CUT, m.face_loc[f], true);
     o.h = point_hats(m.sm, H, lo, hi);
     return o;
 }
@@ -921,7 +842,6 @@ __global__ __launch_bounds__(SCAN_BLOCK) void coarse_fill_kernel(Mesh m, uint32_
     __shared__ uint32_t sh[SCAN_BLOCK / 64];
     const uint32_t f = blockIdx.x * SCAN_BLOCK + threadIdx.x;
     FaceBlocks b;
-    b.h.n = 0; b.nb = 0; b.unowned = -1;
     if (f < nfaces) b = face_blocks(m, H, f);
     const uint32_t e = face_entries(b, fbs);
     uint32_t total;
@@ -969,32 +889,23 @@ hipError_t coarse_table(hipStream_t stream, const Mesh &m, int fbs, int H, uint6
     if (!coarse_by_side(m)) {
         *ncoarse = nnodes;
     } else {
-        const uint32_t items = 2 * nnodes, nb = (items + SCAN_TILE - 1) / SCAN_TILE;
+        const uint32_t items = 2 * nnodes;
         uint8_t *used = nullptr;
-        uint32_t *counts = nullptr;
+        uint32_t *counts = nullptr, total = 0;
         int32_t *unused = nullptr;
-        if (!tmp.alloc(&used, items) || !tmp.alloc(&counts, (size_t)nb + 1) || !tmp.alloc(&unused, items) || !tmp.alloc(&index, items))
+        if (!tmp.alloc(&used, items) || !tmp.alloc(&counts, (size_t)scan_tiles(items) + 1) || !tmp.alloc(&unused, items) ||
+            !tmp.alloc(&index, items))
             return tmp.error();
         if (!tmp.ok(hipMemsetAsync(used, 0, items, stream))) return tmp.error();
         coarse_mark_used(stream, m, H, nnodes, used);
-        hipLaunchKernelGGL(active_count_kernel, dim3(nb), dim3(SCAN_BLOCK), 0, stream, used, items, counts);
-        hipLaunchKernelGGL(active_block_scan_kernel, dim3(1), dim3(SCAN_BLOCK), 0, stream, counts, nb);
-        hipLaunchKernelGGL(active_tables_kernel, dim3(nb), dim3(SCAN_BLOCK), 0, stream, used, items, counts, unused, index);
-        uint32_t total = 0;
-        if (!tmp.ok(hipGetLastError()) || !tmp.ok(hipMemcpyAsync(&total, counts + nb, sizeof(uint32_t), hipMemcpyDeviceToHost, stream)) ||
-            !tmp.ok(hipStreamSynchronize(stream)))
-            return tmp.error();
+        if (!tmp.ok(scan_flags(stream, used, items, counts, unused, index, &total))) return tmp.error();
         *ncoarse = total;
     }
     const uint32_t nblk = (nfaces + SCAN_BLOCK - 1) / SCAN_BLOCK;
-    uint32_t *blk = nullptr;
+    uint32_t *blk = nullptr, total = 0;
     if (!tmp.alloc(&blk, (size_t)nblk + 1)) return tmp.error();
     hipLaunchKernelGGL((coarse_count_kernel<Mesh>), dim3(nblk), dim3(SCAN_BLOCK), 0, stream, m, nfaces, H, fbs, blk);
-    hipLaunchKernelGGL(active_block_scan_kernel, dim3(1), dim3(SCAN_BLOCK), 0, stream, blk, nblk);
-    uint32_t total = 0;
-    if (!tmp.ok(hipGetLastError()) || !tmp.ok(hipMemcpyAsync(&total, blk + nblk, sizeof(uint32_t), hipMemcpyDeviceToHost, stream)) ||
-        !tmp.ok(hipStreamSynchronize(stream)))
-        return tmp.error();
+    if (!tmp.ok(scan_block_counts(stream, nblk, blk, &total))) return tmp.error();
     *entries = total;
     if (ptr == nullptr || *ncoarse < 1 || *ncoarse > (uint64_t)COARSE_MAX_NODES) return hipSuccess;
     const uint64_t nrows = coarse_blocks(m) * fbs;

@@ -1,7 +1,8 @@
 // coarse_precond.hpp -- host entry points of coarse_precond.hip: a Galerkin coarse level for the device conjugate gradient
 //   z = (accumulate ? z : 0) + P (P^T A P)^-1 P^T r
 // added to the patch sum of patch_precond.hpp in the conjugate gradient of solver_cg.hpp:63-144 (the solve of
-// cuthho_square.cpp:915-919), and the coarse table of the face-only system: bilinear hats on every H-th mesh line.
+// cuthho_square.cpp:915-919; the solver with both: rows_precond.hpp), and the coarse table of the face-only system: bilinear hats
+// on every H-th mesh line.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -81,15 +82,6 @@ void coarse_rows_pack(hipStream_t stream, const CoarseTable &t, size_t first, si
 // column of the table); wptr: need_lo + n + need_hi + 1, wcols / wvals: entries + 4 (need_lo + need_hi)
 void coarse_window_build(hipStream_t stream, const CoarseTable &t, const CoarseSizes &sz, size_t need_lo, size_t need_hi,
                          const double *recv_lo, const double *recv_hi, int64_t *wptr, int32_t *wcols, double *wvals);
-
-// status: 0 solved (see exit_reason), 1 patch table refused, 2 a patch is not positive definite, 3 coarse table refused
-// (*refusal: its code), 4 the coarse matrix is not positive definite (*pivot); x is written only with 0
-hipError_t conjugated_gradient_patch_coarse(hipStream_t stream, size_t n, const int64_t *rowptr, const int32_t *colind,
-                                            const double *values, const double *b, double *x, size_t npatches, const int64_t *patch_ptr,
-                                            const int32_t *patch_rows, size_t ncoarse, const int64_t *p_ptr, const int32_t *p_cols,
-                                            const double *p_vals, double convergence_threshold, double divergence_threshold,
-                                            size_t max_iter, int *exit_reason, size_t *iterations, double *relative_residual, int *status,
-                                            int *refusal, int32_t *pivot);
 
 // ---- the coarse table of the face-only system of pa_condensed_csr_pattern (whole-mesh structured contexts) ----
 // The mesh and what a face is: its two points (face_pts, point p = vertex (p % (Nx + 1), p / (Nx + 1))), its compressed id (-1

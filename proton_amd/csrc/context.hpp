@@ -185,6 +185,8 @@ PA_INTERNAL int cond_prepare(pa_context *ctx);
 PA_INTERNAL int asm_prepare(pa_context *ctx);
 // the tables of face_system.hpp as the context holds them: the condensed part after cond_prepare, all of it after asm_prepare
 PA_INTERNAL pa::FaceSystemView face_system_view(const pa_context *ctx);
+
+// capi_solver.hip
 // a coarse table without an interior node or with more than PA_COARSE_MAX_NODES columns: PA_ERR_INVALID_ARG, H and the count in
 // pa_last_error()
 PA_INTERNAL int coarse_count_refused(pa_context *ctx, const char *who, int H, uint64_t ncoarse);

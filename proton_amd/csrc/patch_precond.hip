@@ -13,8 +13,11 @@
 //           chain, symmetric by construction.  z_p goes to a patch-major buffer (slot = position in patch_rows); a second kernel
 //           sums each row's slots in ascending order (= ascending patch order) and forms the block partials of r . z.  No
 //           floating-point atomics: z is the same bits from call to call.
-//   solve:  conjugated_gradient_patch validates and factors the table, then hands patch_apply to the one-rank loop of solver.hip as
-//           its preconditioner (CgPreconditioner, cg.hpp).  The iteration has no kernel and no loop of its own here.
+//   solve:  not here: rows_precond.hip calls patch_query, patch_factor and patch_apply in their order for every solver (TwoLevel).
+//   tables: the closed-form ones (a patch per face; per cell of a loaded mesh from its cprefix), and one builder for the tables that
+//           have to be counted first (item_patches: a count kernel, the scans of scan.hpp, a fill kernel), instantiated for the cells
+//           of a slab of the generator mesh (SlabCellItems) and for the faces or cell sides of the interface problem, whole or by
+//           slab (IfItems).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -354,54 +357,6 @@ void patch_apply(hipStream_t stream, const PatchTable &t, const PatchSizes &sz, 
                        part_rz);
 }
 
-// ---- the solver ---------------------------------------------------------------------------------------------------------------------
-// the table is validated and factored here; the iteration is solver.hip's one-rank loop with patch_apply as its preconditioner
-hipError_t conjugated_gradient_patch(hipStream_t stream, size_t n, const int64_t *rowptr, const int32_t *colind, const double *values,
-                                     const double *b, double *x, size_t npatches, const int64_t *patch_ptr, const int32_t *patch_rows,
-                                     double convergence_threshold, double divergence_threshold, size_t max_iter, int *exit_reason,
-                                     size_t *iterations, double *relative_residual, int *status, int *refusal)
-{
-    *status = 0;
-    *refusal = PATCH_OK;
-    size_t iter = 0;
-    int reason = 0;
-    double rr = 0.0;
-    hipError_t e = hipSuccess;
-    if (n) {
-        PatchSizes sz;
-        e = patch_query(stream, n, npatches, patch_ptr, &sz, refusal);
-        if (e != hipSuccess) return e;
-        if (*refusal) { *status = 1; return hipSuccess; }
-        const PatchTable t{n, npatches, patch_ptr, patch_rows};
-        DeviceTmp tmp(stream);
-        double *factors = nullptr, *z = nullptr;
-        int32_t *slots = nullptr, *info = nullptr;
-        char *scratch = nullptr;
-        if (!tmp.alloc(&factors, (size_t)sz.factor_doubles + 1) || !tmp.alloc(&z, n) || !tmp.alloc(&slots, (size_t)sz.slot_ints) ||
-            !tmp.alloc(&info, npatches + 1) || !tmp.alloc(&scratch, (size_t)sz.scratch_bytes))
-            return tmp.error();
-        size_t failed = 0;
-        e = patch_factor(stream, rowptr, colind, values, t, sz, factors, slots, scratch, info, refusal, &failed);
-        if (e != hipSuccess) return e;
-        if (*refusal) { *status = 1; return hipSuccess; }
-        if (failed) { *status = 2; return hipSuccess; }
-        struct Applied { const PatchTable &t; const PatchSizes &sz; const double *factors; const int32_t *slots; void *scratch; };
-        Applied ap{t, sz, factors, slots, scratch};
-        auto apply = [](void *user, hipStream_t s, const double *r, double *zr, double *part_rz) {
-            const Applied &a = *(const Applied *)user;
-            patch_apply(s, a.t, a.sz, a.factors, a.slots, a.scratch, r, zr, part_rz);
-        };
-        const CgPreconditioner pre{&ap, apply, z};
-        e = conjugated_gradient_one_rank(stream, n, CgCsr{rowptr, colind, values, nullptr}, &pre, nullptr, b, x, convergence_threshold,
-                                         divergence_threshold, max_iter, 0, &reason, &iter, &rr);
-        if (e != hipSuccess) return e;
-    }
-    if (exit_reason) *exit_reason = reason;
-    if (iterations) *iterations = iter;
-    if (relative_residual) *relative_residual = rr;
-    return hipSuccess;
-}
-
 // ---- the patch tables of the face-only system ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(RB) void face_patches_kernel(uint32_t nfaces, int fbs, int32_t row0, int64_t *ptr, int32_t *rows)
 {
@@ -452,135 +407,34 @@ void cell_patches(hipStream_t stream, uint32_t ncells, uint32_t npatches, const 
                        index, fbs, ptr, rows);
 }
 
-// ---- the cell patches of a slab of the generator mesh (pa_condensed_rows_patches), from the closed forms of structured_mesh.hpp: the
-// slab owns the compressed faces [p0, p1) -- of its top cell row's top faces none, unless it is the last slab --, and a patch names
-// its rows by their global indices ------------------------------------------------------------------------------------------------
-// -> the owned non-Dirichlet faces of local cell c in the cell's face order bottom, right, top, left
-__device__ __forceinline__ int slab_cell_faces(const StructuredMesh &sm, int32_t p0, int32_t p1, uint32_t c, int32_t *q)
-{
-    const uint32_t ci = c % sm.Nx, cj = sm.row0 + c / sm.Nx;
-    const uint32_t f[4] = {sm_hface(sm, ci, cj), sm_vface(sm, ci + 1, cj), sm_hface(sm, ci, cj + 1), sm_vface(sm, ci, cj)};
-    int n = 0;
-    for (int lf = 0; lf < 4; ++lf) {
-        uint32_t lo, hi;
-        bool dirichlet;
-        int32_t comp;
-        sm_face_decode(sm, f[lf], lo, hi, dirichlet, comp);
-        if (!dirichlet && comp >= p0 && comp < p1) q[n++] = comp;
-    }
-    return n;
-}
 
-// per block of cells: its patches (bp) and its faces (bb)
-__global__ __launch_bounds__(SCAN_BLOCK) void slab_cell_count_kernel(StructuredMesh sm, int32_t p0, int32_t p1, uint32_t ncells, uint32_t *bp,
-                                                                     uint32_t *bb)
-{
-    __shared__ uint32_t sh[SCAN_BLOCK / 64];
-    const uint32_t c = blockIdx.x * SCAN_BLOCK + threadIdx.x;
-    int32_t q[4];
-    const uint32_t nf = c < ncells ? (uint32_t)slab_cell_faces(sm, p0, p1, c, q) : 0u;
-    uint32_t tp, tb;
-    block_exclusive_scan(nf ? 1u : 0u, sh, tp);
-    block_exclusive_scan(nf, sh, tb);
-    if (threadIdx.x == 0) { bp[blockIdx.x] = tp; bb[blockIdx.x] = tb; }
-}
-
-// bp, bb scanned (their totals at [nblk]): every cell with owned faces writes its patch
-__global__ __launch_bounds__(SCAN_BLOCK) void slab_cell_fill_kernel(StructuredMesh sm, int32_t p0, int32_t p1, uint32_t ncells, int fbs,
-                                                                    const uint32_t *bp, const uint32_t *bb, uint32_t nblk, int64_t *ptr,
-                                                                    int32_t *rows)
-{
-    __shared__ uint32_t sh[SCAN_BLOCK / 64];
-    const uint32_t c = blockIdx.x * SCAN_BLOCK + threadIdx.x;
-    int32_t q[4];
-    const uint32_t nf = c < ncells ? (uint32_t)slab_cell_faces(sm, p0, p1, c, q) : 0u;
-    uint32_t tp, tb;
-    const uint32_t p = bp[blockIdx.x] + block_exclusive_scan(nf ? 1u : 0u, sh, tp);
-    const uint32_t b0 = bb[blockIdx.x] + block_exclusive_scan(nf, sh, tb);
-    if (c == 0) ptr[bp[nblk]] = (int64_t)bb[nblk] * fbs;
-    if (nf == 0) return;
-    int64_t at = (int64_t)b0 * fbs;
-    ptr[p] = at;
-    for (uint32_t i = 0; i < nf; ++i)
-        for (int k = 0; k < fbs; ++k) rows[at++] = q[i] * fbs + k;
-}
-
-hipError_t slab_cell_patches(hipStream_t stream, const StructuredMesh &sm, int32_t p0, int32_t p1, int fbs, uint64_t *npatches,
-                             uint64_t *entries, int64_t *ptr, int32_t *rows)
-{
-    const uint32_t ncells = (sm.row1 - sm.row0) * sm.Nx;
-    const uint32_t nblk = (ncells + SCAN_BLOCK - 1) / SCAN_BLOCK;
-    DeviceTmp tmp(stream);
-    uint32_t *bp = nullptr, *bb = nullptr;
-    if (!tmp.alloc(&bp, (size_t)nblk + 1) || !tmp.alloc(&bb, (size_t)nblk + 1)) return tmp.error();
-    hipLaunchKernelGGL(slab_cell_count_kernel, dim3(nblk), dim3(SCAN_BLOCK), 0, stream, sm, p0, p1, ncells, bp, bb);
-    hipLaunchKernelGGL(active_block_scan_kernel, dim3(1), dim3(SCAN_BLOCK), 0, stream, bp, nblk);
-    hipLaunchKernelGGL(active_block_scan_kernel, dim3(1), dim3(SCAN_BLOCK), 0, stream, bb, nblk);
-    uint32_t tot[2] = {0, 0};
-    if (!tmp.ok(hipGetLastError()) || !tmp.ok(hipMemcpyAsync(&tot[0], bp + nblk, sizeof(uint32_t), hipMemcpyDeviceToHost, stream)) ||
-        !tmp.ok(hipMemcpyAsync(&tot[1], bb + nblk, sizeof(uint32_t), hipMemcpyDeviceToHost, stream)) || !tmp.ok(hipStreamSynchronize(stream)))
-        return tmp.error();
-    *npatches = tot[0];
-    *entries = (uint64_t)tot[1] * fbs;
-    if (ptr == nullptr || *entries >= ((uint64_t)1 << 31)) return hipSuccess;
-    hipLaunchKernelGGL(slab_cell_fill_kernel, dim3(nblk), dim3(SCAN_BLOCK), 0, stream, sm, p0, p1, ncells, fbs, bp, bb, nblk, ptr, rows);
-    if (tmp.ok(hipGetLastError())) tmp.ok(hipStreamSynchronize(stream));       // the block offsets live until the kernel has read them
-    return tmp.error();
-}
-
-// ---- the patch tables of the interface problem's face-only system (pa_interface_condensed_patches, pa_interface_rows_patches:
-// interface_assembler's numbering, in which a cut face owns two blocks; the tables of IfCsrMesh alone -- the whole mesh's, or a slab's
-// extended ones with the part of them that counts (IfPatchRange) --, counted and placed by the scans of scan.hpp) ----------------------
-// An item is what may give a patch: a face (IF_PATCH_FACE), or side s of cell X as item 2 X + s (IF_PATCH_CELL; an uncut cell is
-// its item 2 X alone).  -> the item's face blocks within the range in the patch's order (none: no patch)
-__device__ __forceinline__ int ifp_blocks(const IfCsrMesh &m, const IfPatchRange &r, int kind, size_t item, int32_t *blk)
-{
-    int n = 0;
-    auto take = [&](int32_t q) { if (q >= r.q0 && q < r.q1) blk[n++] = q; };
-    if (kind == IF_PATCH_FACE) {
-        const int32_t b = m.face_table[item];
-        if (b < 0) return 0;
-        take(b);
-        if (m.face_loc[item] == IF_LOC_CUT) take(b + 1);
-        return n;
-    }
-    const size_t X = item >> 1;
-    const int s = (int)(item & 1);
-    const bool cut = m.cell_loc[X] == IF_LOC_CUT;
-    if (!cut && s == 1) return 0;
-    for (int lf = 0; lf < 4; ++lf) {                     // bottom, right, top, left
-        const uint32_t f = m.cell_faces[4 * X + lf];
-        const int32_t b = m.face_table[f];
-        if (b < 0) continue;
-        const int8_t fl = m.face_loc[f];
-        if (cut && fl != IF_LOC_CUT && fl != s) continue;                                   // an uncut face: on its own side only
-        take(b + ((cut && s == 1 && fl == IF_LOC_CUT) ? 1 : 0));                            // dup of if_global_index
-    }
-    return n;
-}
-
+// ---- a patch table from items, counted and placed by the scans of scan.hpp.  An item is what may give a patch; an Items type says
+//   int blocks(size_t i, int32_t *q) const      the face blocks item i gives, at most 4, in the patch's order (none: no patch)
+//   int32_t first_row(int32_t q, int fbs) const  the first of the fbs rows of block q
+// ------------------------------------------------------------------------------------------------------------------------------------
 // per block of items: its patches (bp) and its face blocks (bb)
-__global__ __launch_bounds__(SCAN_BLOCK) void ifp_count_kernel(IfCsrMesh m, IfPatchRange r, int kind, size_t nitems, uint32_t *bp, uint32_t *bb)
+template <class Items>
+__global__ __launch_bounds__(SCAN_BLOCK) void item_count_kernel(Items it, size_t nitems, uint32_t *bp, uint32_t *bb)
 {
     __shared__ uint32_t sh[SCAN_BLOCK / 64];
     const size_t i = (size_t)blockIdx.x * SCAN_BLOCK + threadIdx.x;
-    int32_t blk[4];
-    const uint32_t nb = i < nitems ? (uint32_t)ifp_blocks(m, r, kind, r.item0 + i, blk) : 0u;
+    int32_t q[4];
+    const uint32_t nb = i < nitems ? (uint32_t)it.blocks(i, q) : 0u;
     uint32_t tp, tb;
     block_exclusive_scan(nb ? 1u : 0u, sh, tp);
     block_exclusive_scan(nb, sh, tb);
     if (threadIdx.x == 0) { bp[blockIdx.x] = tp; bb[blockIdx.x] = tb; }
 }
 
-// bp, bb scanned (their totals at [nblk]): every item with blocks writes its patch; block q gives the rows of block r.shift + q,
-// formed in 64 bits (the system has fewer than 2^31 rows, the extended numbering's blocks need not start at the system's)
-__global__ __launch_bounds__(SCAN_BLOCK) void ifp_fill_kernel(IfCsrMesh m, IfPatchRange r, int kind, size_t nitems, int fbs, const uint32_t *bp,
-                                                              const uint32_t *bb, uint32_t nblk, int64_t *ptr, int32_t *rows)
+// bp, bb scanned (their totals at [nblk]): every item with blocks writes its patch
+template <class Items>
+__global__ __launch_bounds__(SCAN_BLOCK) void item_fill_kernel(Items it, size_t nitems, int fbs, const uint32_t *bp, const uint32_t *bb,
+                                                               uint32_t nblk, int64_t *ptr, int32_t *rows)
 {
     __shared__ uint32_t sh[SCAN_BLOCK / 64];
     const size_t i = (size_t)blockIdx.x * SCAN_BLOCK + threadIdx.x;
-    int32_t blk[4];
-    const uint32_t nb = i < nitems ? (uint32_t)ifp_blocks(m, r, kind, r.item0 + i, blk) : 0u;
+    int32_t q[4];
+    const uint32_t nb = i < nitems ? (uint32_t)it.blocks(i, q) : 0u;
     uint32_t tp, tb;
     const uint32_t p = bp[blockIdx.x] + block_exclusive_scan(nb ? 1u : 0u, sh, tp);
     const uint32_t b0 = bb[blockIdx.x] + block_exclusive_scan(nb, sh, tb);
@@ -588,40 +442,106 @@ __global__ __launch_bounds__(SCAN_BLOCK) void ifp_fill_kernel(IfCsrMesh m, IfPat
     if (nb == 0) return;
     int64_t at = (int64_t)b0 * fbs;
     ptr[p] = at;
-    for (uint32_t j = 0; j < nb; ++j)
-        for (int k = 0; k < fbs; ++k) rows[at++] = (int32_t)((r.shift + blk[j]) * fbs + k);
+    for (uint32_t j = 0; j < nb; ++j) {
+        const int32_t row = it.first_row(q[j], fbs);
+        for (int k = 0; k < fbs; ++k) rows[at++] = row + k;
+    }
 }
 
-// the table of nitems items from r.item0 on
-static hipError_t ifp_table(hipStream_t stream, const IfCsrMesh &m, const IfPatchRange &r, int face_deg, int kind, size_t nitems,
-                            uint64_t *npatches, uint64_t *entries, int64_t *ptr, int32_t *rows)
+// the table of nitems items.  ptr = null, or 2^31 entries and more: the sizes only.  Waits for the stream.
+template <class Items>
+static hipError_t item_patches(hipStream_t stream, const Items &it, size_t nitems, int fbs, uint64_t *npatches, uint64_t *entries,
+                               int64_t *ptr, int32_t *rows)
 {
-    const int fbs = if_dims(face_deg).fbs;
     const uint32_t nblk = (uint32_t)(nitems ? (nitems + SCAN_BLOCK - 1) / SCAN_BLOCK : 1);
     DeviceTmp tmp(stream);
-    uint32_t *bp = nullptr, *bb = nullptr;
-    if (!tmp.alloc(&bp, (size_t)nblk + 1) || !tmp.alloc(&bb, (size_t)nblk + 1)) return tmp.error();
-    hipLaunchKernelGGL(ifp_count_kernel, dim3(nblk), dim3(SCAN_BLOCK), 0, stream, m, r, kind, nitems, bp, bb);
-    hipLaunchKernelGGL(active_block_scan_kernel, dim3(1), dim3(SCAN_BLOCK), 0, stream, bp, nblk);
-    hipLaunchKernelGGL(active_block_scan_kernel, dim3(1), dim3(SCAN_BLOCK), 0, stream, bb, nblk);
-    uint32_t tot[2] = {0, 0};
-    if (!tmp.ok(hipGetLastError()) || !tmp.ok(hipMemcpyAsync(&tot[0], bp + nblk, sizeof(uint32_t), hipMemcpyDeviceToHost, stream)) ||
-        !tmp.ok(hipMemcpyAsync(&tot[1], bb + nblk, sizeof(uint32_t), hipMemcpyDeviceToHost, stream)) || !tmp.ok(hipStreamSynchronize(stream)))
-        return tmp.error();
+    uint32_t *b[2] = {nullptr, nullptr}, tot[2] = {0, 0};
+    if (!tmp.alloc(&b[0], (size_t)nblk + 1) || !tmp.alloc(&b[1], (size_t)nblk + 1)) return tmp.error();
+    hipLaunchKernelGGL((item_count_kernel<Items>), dim3(nblk), dim3(SCAN_BLOCK), 0, stream, it, nitems, b[0], b[1]);
+    if (!tmp.ok(scan_block_counts(stream, nblk, 2, b, tot))) return tmp.error();
     *npatches = tot[0];
     *entries = (uint64_t)tot[1] * fbs;
     if (ptr == nullptr || *entries >= ((uint64_t)1 << 31)) return hipSuccess;
-    hipLaunchKernelGGL(ifp_fill_kernel, dim3(nblk), dim3(SCAN_BLOCK), 0, stream, m, r, kind, nitems, fbs, bp, bb, nblk, ptr, rows);
+    hipLaunchKernelGGL((item_fill_kernel<Items>), dim3(nblk), dim3(SCAN_BLOCK), 0, stream, it, nitems, fbs, b[0], b[1], nblk, ptr, rows);
     if (tmp.ok(hipGetLastError())) tmp.ok(hipStreamSynchronize(stream));       // the block offsets live until the kernel has read them
     return tmp.error();
 }
+
+// ---- the cell patches of a slab of the generator mesh (pa_condensed_rows_patches), from the closed forms of structured_mesh.hpp: the
+// slab owns the compressed faces [p0, p1) -- of its top cell row's top faces none, unless it is the last slab --, and a patch names
+// its rows by their global indices.  Item c: local cell c -> its owned non-Dirichlet faces in the cell's face order bottom, right,
+// top, left; compressed face q owns the rows from q fbs on ------------------------------------------------------------------------
+struct SlabCellItems {
+    StructuredMesh sm;
+    int32_t p0, p1;
+    __device__ int blocks(size_t item, int32_t *q) const
+    {
+        const uint32_t c = (uint32_t)item, ci = c % sm.Nx, cj = sm.row0 + c / sm.Nx;
+        const uint32_t f[4] = {sm_hface(sm, ci, cj), sm_vface(sm, ci + 1, cj), sm_hface(sm, ci, cj + 1), sm_vface(sm, ci, cj)};
+        int n = 0;
+        for (int lf = 0; lf < 4; ++lf) {
+            uint32_t lo, hi;
+            bool dirichlet;
+            int32_t comp;
+            sm_face_decode(sm, f[lf], lo, hi, dirichlet, comp);
+            if (!dirichlet && comp >= p0 && comp < p1) q[n++] = comp;
+        }
+        return n;
+    }
+    __device__ int32_t first_row(int32_t q, int fbs) const { return q * fbs; }
+};
+
+hipError_t slab_cell_patches(hipStream_t stream, const StructuredMesh &sm, int32_t p0, int32_t p1, int fbs, uint64_t *npatches,
+                             uint64_t *entries, int64_t *ptr, int32_t *rows)
+{
+    return item_patches(stream, SlabCellItems{sm, p0, p1}, (size_t)(sm.row1 - sm.row0) * sm.Nx, fbs, npatches, entries, ptr, rows);
+}
+
+// ---- the patch tables of the interface problem's face-only system (pa_interface_condensed_patches, pa_interface_rows_patches:
+// interface_assembler's numbering, in which a cut face owns two blocks; the tables of IfCsrMesh alone -- the whole mesh's, or a slab's
+// extended ones with the part of them that counts (IfPatchRange)).  Item r.item0 + i is a face (IF_PATCH_FACE), or side s of cell X
+// as 2 X + s (IF_PATCH_CELL; an uncut cell is its item 2 X alone) -> its face blocks within the range; block q gives the rows of
+// block r.shift + q, formed in 64 bits (the system has fewer than 2^31 rows, the extended numbering's blocks need not start at the
+// system's) ------------------------------------------------------------------------------------------------------------------------
+struct IfItems {
+    IfCsrMesh m;
+    IfPatchRange r;
+    int kind;
+    __device__ int blocks(size_t i, int32_t *blk) const
+    {
+        const size_t item = r.item0 + i;
+        int n = 0;
+        auto take = [&](int32_t q) { if (q >= r.q0 && q < r.q1) blk[n++] = q; };
+        if (kind == IF_PATCH_FACE) {
+            const int32_t b = m.face_table[item];
+            if (b < 0) return 0;
+            take(b);
+            if (m.face_loc[item] == IF_LOC_CUT) take(b + 1);
+            return n;
+        }
+        const size_t X = item >> 1;
+        const int s = (int)(item & 1);
+        const bool cut = m.cell_loc[X] == IF_LOC_CUT;
+        if (!cut && s == 1) return 0;
+        for (int lf = 0; lf < 4; ++lf) {                     // bottom, right, top, left
+            const uint32_t f = m.cell_faces[4 * X + lf];
+            const int32_t b = m.face_table[f];
+            if (b < 0) continue;
+            const int8_t fl = m.face_loc[f];
+            if (cut && fl != IF_LOC_CUT && fl != s) continue;                                   // an uncut face: on its own side only
+            take(b + ((cut && s == 1 && fl == IF_LOC_CUT) ? 1 : 0));                            // dup of if_global_index
+        }
+        return n;
+    }
+    __device__ int32_t first_row(int32_t q, int fbs) const { return (int32_t)((r.shift + q) * fbs); }
+};
 
 hipError_t ifcond_patches(hipStream_t stream, const IfCsrMesh &m, int face_deg, int kind, uint64_t *npatches, uint64_t *entries,
                           int64_t *ptr, int32_t *rows)
 {
     const IfPatchRange whole{0, 0, INT32_MAX, 0};
-    return ifp_table(stream, m, whole, face_deg, kind, kind == IF_PATCH_FACE ? (size_t)m.nfaces : 2 * (size_t)m.ncells, npatches, entries,
-                     ptr, rows);
+    return item_patches(stream, IfItems{m, whole, kind}, kind == IF_PATCH_FACE ? (size_t)m.nfaces : 2 * (size_t)m.ncells,
+                        if_dims(face_deg).fbs, npatches, entries, ptr, rows);
 }
 
 // a slab: every face of the extended tables may give a patch (its blocks are owned or not, both of a cut face together), of the
@@ -631,8 +551,8 @@ hipError_t ifrows_patches(hipStream_t stream, const IfCsrMesh &m, uint32_t halo_
 {
     const bool faces = kind == IF_PATCH_FACE;
     const IfPatchRange slab{faces ? (size_t)0 : 2 * (size_t)halo_cells, q0, q1, fb0};
-    return ifp_table(stream, m, slab, face_deg, kind, faces ? (size_t)m.nfaces : 2 * (size_t)(m.ncells - halo_cells), npatches, entries, ptr,
-                     rows);
+    return item_patches(stream, IfItems{m, slab, kind}, faces ? (size_t)m.nfaces : 2 * (size_t)(m.ncells - halo_cells),
+                        if_dims(face_deg).fbs, npatches, entries, ptr, rows);
 }
 
 }  // namespace pa

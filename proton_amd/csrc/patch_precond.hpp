@@ -1,6 +1,7 @@
 // patch_precond.hpp -- host entry points of patch_precond.hip: the additive Schwarz preconditioner over patches of rows
 //   z = sum_p R_p^T (R_p A R_p^T)^-1 R_p r
-// and the conjugate gradient of solver_cg.hpp:63-144 with it in place of the point Jacobi (the solve of cuthho_square.cpp:915-919).
+// for the conjugate gradient of solver_cg.hpp:63-144 in place of the point Jacobi (the solve of cuthho_square.cpp:915-919; the solver
+// with it: rows_precond.hpp), and the patch tables of the face-only systems.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -49,12 +50,6 @@ hipError_t patch_factor(hipStream_t stream, const int64_t *rowptr, const int32_t
 // z = M r with the factors and slots of patch_factor; part_rz (may be null): the partial sums of r . z per block of RB rows
 void patch_apply(hipStream_t stream, const PatchTable &t, const PatchSizes &sz, const double *factors, const int32_t *slots,
                  void *scratch, const double *r, double *z, double *part_rz);
-
-// status: 0 solved (see exit_reason), 1 table refused (*refusal), 2 a patch is not positive definite; x is written only with 0
-hipError_t conjugated_gradient_patch(hipStream_t stream, size_t n, const int64_t *rowptr, const int32_t *colind, const double *values,
-                                     const double *b, double *x, size_t npatches, const int64_t *patch_ptr, const int32_t *patch_rows,
-                                     double convergence_threshold, double divergence_threshold, size_t max_iter, int *exit_reason,
-                                     size_t *iterations, double *relative_residual, int *status, int *refusal);
 
 // ---- the patch tables of the face-only system of pa_condensed_csr_pattern (whole-mesh contexts: compressed face q owns rows
 // q fbs .. q fbs + fbs - 1) ----

@@ -1,21 +1,27 @@
-// rows_precond.hip -- the two-level preconditioner of patch_precond.hip and coarse_precond.hip on a ROW-PARTITIONED system: the
-// conjugate gradient of solver_cg.hpp:63-144 (the solve of cuthho_square.cpp:915-919 on the face-only system) with
+// rows_precond.hip -- the order in which the two levels of patch_precond.hip and coarse_precond.hip are called: the conjugate
+// gradient of solver_cg.hpp:63-144 (the solve of cuthho_square.cpp:915-919 on the face-only system) with
 //   z = sum_p R_p^T (R_p A R_p^T)^-1 R_p r + P (P^T A P)^-1 P^T r
-// where every rank holds the rows [row_begin, row_end) of A (global columns), its own patches and its own rows of P.
+// on one rank (conjugated_gradient_patch: the first term alone; conjugated_gradient_patch_coarse) and on a ROW-PARTITIONED system
+// (conjugated_gradient_rows_patch_coarse), where every rank holds the rows [row_begin, row_end) of A (global columns), its own
+// patches and its own rows of P.
 //
-// There is no kernel and no loop here: the iteration is solver.hip's row-partitioned loop (conjugated_gradient_rows_stored), the
-// kernels are those of the one-rank preconditioners, and this file is the order in which a rank calls them between the sums.
-//   patches:  a patch lies inside the rank's rows, so its block R_p A R_p^T lies inside the rank's rows and their own columns: the
-//             level needs no communication.  The table names global rows (PatchTable::row0), the matrix is read through the window
-//             view: storage row r - row_begin, global columns.
+// There is no kernel and no loop here: the iterations are solver.hip's (conjugated_gradient_one_rank,
+// conjugated_gradient_rows_stored), the kernels are those of the two levels, and this file is the order of the calls.
+//   TwoLevel: both tables, what they need on the device, and the local set-up every front end shares (prepare): the patch table
+//             judged and factored, then the coarse table judged.  A refusal of either table wins over a failed patch pivot, which
+//             prepare only counts; the front ends map its result to their own statuses.  apply: the patch sum, then the coarse term.
+//   one rank: prepare, coarse_factor, the one-rank loop with TwoLevel's apply.
+//   patches:  on a rank a patch lies inside the rank's rows, so its block R_p A R_p^T lies inside the rank's rows and their own
+//             columns: the level needs no communication.  The table names global rows (PatchTable::row0), the matrix is read through
+//             the window view: storage row r - row_begin, global columns.
 //   set-up:   the rows of P for the two ends of the window come from the neighbours through the transport's halo callback, 8 doubles
 //             a row; W = A_r P_window (16 slots a row), the rank's addend P_r^T W of A_c in the fixed order of the one-rank product;
 //             the lower triangle is summed over the ranks and mirrored, so A_c is the same bits on every rank, and every rank
 //             factors it.
 //   apply:    patch sum (local), P_r^T r (local), its sum over the ranks, the two packed triangular products (redundant), the
 //             gather added onto the patch sum with the block partials of r . z.
-// Every exit is collective (solver.hip): a local failure -- a refused table (5), a matrix that is not positive definite (6), a
-// callback (1), HIP (4) -- is a flag behind the next sum, and nobody iterates unless everybody can.
+// Every exit of the row-partitioned solve is collective (solver.hip): a local failure -- a refused table (5), a matrix that is not
+// positive definite (6), a callback (1), HIP (4) -- is a flag behind the next sum, and nobody iterates unless everybody can.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,16 +39,101 @@ namespace {
 
 constexpr size_t SUM_PIECE = (size_t)1 << 20;      // doubles of A_c's triangle per sum over the ranks (the callback counts in int)
 
-struct RowsPrecond {
-    DeviceTmp *tmp;
-    size_t n;
+struct TwoLevel {
     PatchTable pt;
-    CoarseTable ct;                        // ncoarse = 0: patches only
-    PatchSizes psz;
-    CoarseSizes csz;
+    CoarseTable ct;                        // ncoarse = 0 after prepare(coarse = false): patches only
+    PatchSizes psz = PatchSizes();
+    CoarseSizes csz = CoarseSizes();
     double *factors = nullptr, *cfactor = nullptr;
     int32_t *slots = nullptr, *info = nullptr;
     char *pscratch = nullptr, *cpt = nullptr, *cscratch = nullptr;
+    // what prepare found: the level whose table was refused (1 the patches, 2 the coarse level, 0 neither) with the refusal's code,
+    // and the patches whose pivot failed -- to be reported only where no table was refused
+    int level = 0, refusal = 0;
+    size_t failed = 0;
+
+    bool refused(int lv) { level = refusal ? lv : 0; return refusal != 0; }
+
+    // the local set-up: the patch table judged and factored (a system without rows has none), then -- coarse -- the coarse table
+    // judged.  Returns at the first refusal.  The temporaries are tmp's.
+    hipError_t prepare(hipStream_t stream, DeviceTmp &tmp, const int64_t *rowptr, const int32_t *colind, const double *values, bool coarse)
+    {
+        hipError_t e = hipSuccess;
+        if (pt.n) {
+            e = patch_query(stream, pt.n, pt.npatches, pt.ptr, &psz, &refusal);
+            if (e != hipSuccess || refused(1)) return e;
+            if (!tmp.alloc(&factors, (size_t)psz.factor_doubles + 1) || !tmp.alloc(&slots, (size_t)psz.slot_ints) ||
+                !tmp.alloc(&info, pt.npatches + 1) || !tmp.alloc(&pscratch, (size_t)psz.scratch_bytes))
+                return tmp.error();
+            e = patch_factor(stream, rowptr, colind, values, pt, psz, factors, slots, pscratch, info, &refusal, &failed);
+            if (e != hipSuccess || refused(1)) return e;
+        }
+        if (coarse) {
+            e = coarse_query(stream, ct.n, ct.ncoarse, ct.ptr, &csz, &refusal);
+            if (e != hipSuccess || refused(2)) return e;
+            if (!tmp.alloc(&cpt, (size_t)csz.pt_bytes) || !tmp.alloc(&cfactor, (size_t)csz.factor_doubles) ||
+                !tmp.alloc(&cscratch, (size_t)csz.scratch_bytes))
+                return tmp.error();
+            e = coarse_validate(stream, ct, csz, cscratch, &refusal);
+            if (e != hipSuccess || refused(2)) return e;
+        }
+        return hipSuccess;
+    }
+};
+
+// z = M^-1 r of a prepared and factored TwoLevel: the patch sum, and the coarse term onto it where there is one (the block partials
+// of r . z come from whichever kernel writes z last)
+void two_level_apply(void *user, hipStream_t stream, const double *r, double *z, double *part_rz)
+{
+    const TwoLevel &l = *(const TwoLevel *)user;
+    patch_apply(stream, l.pt, l.psz, l.factors, l.slots, l.pscratch, r, z, l.ct.ncoarse ? nullptr : part_rz);
+    if (l.ct.ncoarse) coarse_apply(stream, l.ct, l.csz, l.cpt, l.cfactor, l.cscratch, 1, r, z, part_rz);
+}
+
+// both one-rank solvers.  coarse = false: the patches alone, status 0 .. 2
+hipError_t conjugated_gradient_two_level(hipStream_t stream, size_t n, const int64_t *rowptr, const int32_t *colind, const double *values,
+                                         const double *b, double *x, const PatchTable &pt, bool coarse, const CoarseTable &ct,
+                                         double convergence_threshold, double divergence_threshold, size_t max_iter, int *exit_reason,
+                                         size_t *iterations, double *relative_residual, int *status, int *refusal, int32_t *pivot)
+{
+    *status = 0;
+    *refusal = 0;
+    *pivot = 0;
+    size_t iter = 0;
+    int reason = 0;
+    double rr = 0.0;
+    if (n) {
+        DeviceTmp tmp(stream);
+        TwoLevel l;
+        l.pt = pt;
+        l.ct = coarse ? ct : CoarseTable{n, 0, nullptr, nullptr, nullptr};
+        double *z = nullptr;
+        if (!tmp.alloc(&z, n)) return tmp.error();
+        hipError_t e = l.prepare(stream, tmp, rowptr, colind, values, coarse);
+        if (e != hipSuccess) return e;
+        *refusal = l.refusal;
+        if (l.level) { *status = l.level == 1 ? 1 : 3; return hipSuccess; }
+        if (l.failed) { *status = 2; return hipSuccess; }
+        if (coarse) {
+            e = coarse_factor(stream, rowptr, colind, values, l.ct, l.csz, l.cpt, l.cfactor, l.cscratch, nullptr, pivot, refusal);
+            if (e != hipSuccess) return e;
+            if (*refusal) { *status = 3; return hipSuccess; }
+            if (*pivot) { *status = 4; return hipSuccess; }
+        }
+        const CgPreconditioner pre{&l, two_level_apply, z};
+        e = conjugated_gradient_one_rank(stream, n, CgCsr{rowptr, colind, values, nullptr}, &pre, nullptr, b, x, convergence_threshold,
+                                         divergence_threshold, max_iter, 0, &reason, &iter, &rr);
+        if (e != hipSuccess) return e;
+    }
+    if (exit_reason) *exit_reason = reason;
+    if (iterations) *iterations = iter;
+    if (relative_residual) *relative_residual = rr;
+    return hipSuccess;
+}
+
+struct RowsPrecond {
+    DeviceTmp *tmp;
+    TwoLevel lv;
     std::vector<double> host;              // what goes through allreduce_sum
     RowsPrecondReport rep;
 };
@@ -52,34 +143,14 @@ template <class T> bool take(RowsPrecond &p, CgRowsFail *fail, T **q, size_t cou
     return p.tmp->alloc(q, count) || fail->hip_ok(p.tmp->error());
 }
 
-// the local part: both tables judged, the patches factored (a failed pivot is reported after the coarse table has been judged, as
-// conjugated_gradient_patch_coarse reports it)
+// the local part
 void rows_prepare(void *user, hipStream_t stream, const CgRowsSystem &s, CgRowsFail *fail)
 {
     RowsPrecond &p = *(RowsPrecond *)user;
-    int refusal = 0;
-    size_t failed = 0;
-    if (p.n) {
-        if (!fail->hip_ok(patch_query(stream, p.n, p.pt.npatches, p.pt.ptr, &p.psz, &refusal))) return;
-        if (refusal) { p.rep.level = 1; p.rep.refusal = refusal; fail->status = 5; return; }
-        if (!take(p, fail, &p.factors, (size_t)p.psz.factor_doubles + 1) || !take(p, fail, &p.slots, (size_t)p.psz.slot_ints) ||
-            !take(p, fail, &p.info, p.pt.npatches + 1) || !take(p, fail, &p.pscratch, (size_t)p.psz.scratch_bytes))
-            return;
-        if (!fail->hip_ok(patch_factor(stream, s.rowptr, s.colind, s.values, p.pt, p.psz, p.factors, p.slots, p.pscratch, p.info, &refusal,
-                                       &failed)))
-            return;
-        if (refusal) { p.rep.level = 1; p.rep.refusal = refusal; fail->status = 5; return; }
-    }
-    if (p.ct.ncoarse) {
-        if (!fail->hip_ok(coarse_query(stream, p.n, p.ct.ncoarse, p.ct.ptr, &p.csz, &refusal))) return;
-        if (refusal) { p.rep.level = 2; p.rep.refusal = refusal; fail->status = 5; return; }
-        if (!take(p, fail, &p.cpt, (size_t)p.csz.pt_bytes) || !take(p, fail, &p.cfactor, (size_t)p.csz.factor_doubles) ||
-            !take(p, fail, &p.cscratch, (size_t)p.csz.scratch_bytes))
-            return;
-        if (!fail->hip_ok(coarse_validate(stream, p.ct, p.csz, p.cscratch, &refusal))) return;
-        if (refusal) { p.rep.level = 2; p.rep.refusal = refusal; fail->status = 5; return; }
-    }
-    if (failed) { p.rep.level = 1; fail->status = 6; }
+    TwoLevel &l = p.lv;
+    if (!fail->hip_ok(l.prepare(stream, *p.tmp, s.rowptr, s.colind, s.values, l.ct.ncoarse != 0))) return;
+    if (l.level) { p.rep.level = l.level; p.rep.refusal = l.refusal; fail->status = 5; }
+    else if (l.failed) { p.rep.level = 1; fail->status = 6; }
 }
 
 // host doubles summed over the ranks in place, the rank's flag behind them -> 0, or the status every rank leaves with
@@ -94,9 +165,10 @@ int rows_sum(const CgTransport *tp, double *vals, size_t count, const CgRowsFail
 int rows_setup(void *user, hipStream_t stream, const CgRowsSystem &s, CgRowsFail *fail)
 {
     RowsPrecond &p = *(RowsPrecond *)user;
-    if (!p.ct.ncoarse) return 0;
+    TwoLevel &l = p.lv;
+    if (!l.ct.ncoarse) return 0;
     const CgTransport *tp = s.tp;
-    const size_t nc = p.ct.ncoarse, ntri = nc * (nc + 1) / 2;
+    const size_t n = l.ct.n, nc = l.ct.ncoarse, ntri = nc * (nc + 1) / 2;
     const size_t need_lo = (size_t)s.need_lo, need_hi = (size_t)s.need_hi, give_lo = (size_t)s.give_lo, give_hi = (size_t)s.give_hi;
     int refusal = 0;
     CoarseWindow win{};
@@ -106,27 +178,27 @@ int rows_setup(void *user, hipStream_t stream, const CgRowsSystem &s, CgRowsFail
         double *send_lo = nullptr, *send_hi = nullptr, *recv_lo = nullptr, *recv_hi = nullptr, *wvals = nullptr;
         int64_t *wptr = nullptr;
         int32_t *wcols = nullptr;
-        const size_t wentries = (size_t)p.csz.entries + COARSE_MAX_ROW_ENTRIES * (need_lo + need_hi);
+        const size_t wentries = (size_t)l.csz.entries + COARSE_MAX_ROW_ENTRIES * (need_lo + need_hi);
         if (!fail->status)
             (void)(take(p, fail, &send_lo, 8 * give_lo) && take(p, fail, &send_hi, 8 * give_hi) && take(p, fail, &recv_lo, 8 * need_lo) &&
-                   take(p, fail, &recv_hi, 8 * need_hi) && take(p, fail, &wptr, need_lo + p.n + need_hi + 1) &&
+                   take(p, fail, &recv_hi, 8 * need_hi) && take(p, fail, &wptr, need_lo + n + need_hi + 1) &&
                    take(p, fail, &wcols, wentries) && take(p, fail, &wvals, wentries));
         if (!fail->status)
             (void)(fail->hip_ok(hipMemsetAsync(recv_lo, 0xff, need_lo ? 64 * need_lo : 8, stream)) &&
                    fail->hip_ok(hipMemsetAsync(recv_hi, 0xff, need_hi ? 64 * need_hi : 8, stream)));
         if (!fail->status) {
-            coarse_rows_pack(stream, p.ct, 0, give_lo, send_lo);
-            coarse_rows_pack(stream, p.ct, p.n - give_hi, give_hi, send_hi);
+            coarse_rows_pack(stream, l.ct, 0, give_lo, send_lo);
+            coarse_rows_pack(stream, l.ct, n - give_hi, give_hi, send_hi);
             if (tp->halo(tp->user, send_lo, 8 * give_lo, send_hi, 8 * give_hi, recv_lo, 8 * need_lo, recv_hi, 8 * need_hi, (void *)stream) != 0)
                 fail->status = 1;
         }
         if (!fail->status) {
-            coarse_window_build(stream, p.ct, p.csz, need_lo, need_hi, recv_lo, recv_hi, wptr, wcols, wvals);
-            win = CoarseWindow{s.row_begin - s.need_lo, need_lo + p.n + need_hi, wptr, wcols, wvals};
+            coarse_window_build(stream, l.ct, l.csz, need_lo, need_hi, recv_lo, recv_hi, wptr, wcols, wvals);
+            win = CoarseWindow{s.row_begin - s.need_lo, need_lo + n + need_hi, wptr, wcols, wvals};
         }
     }
-    if (!fail->status && fail->hip_ok(coarse_galerkin(stream, s.rowptr, s.colind, s.values, p.ct, p.csz, tp ? &win : nullptr, p.cpt,
-                                                      p.cscratch, &refusal)) && refusal) {
+    if (!fail->status && fail->hip_ok(coarse_galerkin(stream, s.rowptr, s.colind, s.values, l.ct, l.csz, tp ? &win : nullptr, l.cpt,
+                                                      l.cscratch, &refusal)) && refusal) {
         p.rep.level = 2; p.rep.refusal = refusal; fail->status = 5;
     }
     if (tp) {
@@ -134,7 +206,7 @@ int rows_setup(void *user, hipStream_t stream, const CgRowsSystem &s, CgRowsFail
         double *tri = nullptr;
         std::vector<double> h(ntri, 0.0), piece(std::min(ntri, SUM_PIECE) + 1);
         if (!fail->status && take(p, fail, &tri, ntri)) {
-            coarse_matrix_triangle(stream, p.ct, p.csz, p.cscratch, 0, tri);
+            coarse_matrix_triangle(stream, l.ct, l.csz, l.cscratch, 0, tri);
             (void)(fail->hip_ok(hipMemcpyAsync(h.data(), tri, ntri * 8, hipMemcpyDeviceToHost, stream)) && fail->hip_ok(hipStreamSynchronize(stream)));
         }
         for (size_t off = 0; off < ntri; off += SUM_PIECE) {
@@ -146,9 +218,9 @@ int rows_setup(void *user, hipStream_t stream, const CgRowsSystem &s, CgRowsFail
             std::copy(piece.begin(), piece.begin() + m, h.begin() + off);
         }
         if (fail->hip_ok(hipMemcpyAsync(tri, h.data(), ntri * 8, hipMemcpyHostToDevice, stream)) && fail->hip_ok(hipStreamSynchronize(stream)))
-            coarse_matrix_triangle(stream, p.ct, p.csz, p.cscratch, 1, tri);
+            coarse_matrix_triangle(stream, l.ct, l.csz, l.cscratch, 1, tri);
     }
-    if (!fail->status && fail->hip_ok(coarse_cholesky(stream, p.ct, p.csz, p.cfactor, p.cscratch, nullptr, &p.rep.pivot)) && p.rep.pivot) {
+    if (!fail->status && fail->hip_ok(coarse_cholesky(stream, l.ct, l.csz, l.cfactor, l.cscratch, nullptr, &p.rep.pivot)) && p.rep.pivot) {
         p.rep.level = 2; fail->status = 6;       // (the same pivot on every rank: they factor the same bits)
     }
     p.host.assign(nc + 1, 0.0);
@@ -157,18 +229,20 @@ int rows_setup(void *user, hipStream_t stream, const CgRowsSystem &s, CgRowsFail
     return rows_sum(tp, flag, 0, fail);
 }
 
+// TwoLevel's apply in its stages, the sum of the restrictions over the ranks between the two halves of the coarse term
 int rows_apply(void *user, hipStream_t stream, const CgRowsSystem &s, const double *r, double *z, double *part_rz, CgRowsFail *fail)
 {
     RowsPrecond &p = *(RowsPrecond *)user;
+    const TwoLevel &l = p.lv;
     const CgTransport *tp = s.tp;
-    const size_t nc = p.ct.ncoarse;
+    const size_t n = l.pt.n, nc = l.ct.ncoarse;
     if (!fail->status) {
-        if (p.n) patch_apply(stream, p.pt, p.psz, p.factors, p.slots, p.pscratch, r, z, nc ? nullptr : part_rz);
+        if (n) patch_apply(stream, l.pt, l.psz, l.factors, l.slots, l.pscratch, r, z, nc ? nullptr : part_rz);
         else (void)fail->hip_ok(hipMemsetAsync(part_rz, 0, 8, stream));      // (no rows: the one block's partial is zero)
     }
     if (!nc) return 0;
     double *rc = nullptr;
-    if (!fail->status) rc = coarse_restrict(stream, p.ct, p.csz, p.cpt, p.cscratch, r);
+    if (!fail->status) rc = coarse_restrict(stream, l.ct, l.csz, l.cpt, l.cscratch, r);
     if (tp) {
         std::fill(p.host.begin(), p.host.end(), 0.0);
         if (!fail->status)
@@ -178,11 +252,34 @@ int rows_apply(void *user, hipStream_t stream, const CgRowsSystem &s, const doub
         if (st) return st;
         (void)fail->hip_ok(hipMemcpyAsync(rc, p.host.data(), nc * 8, hipMemcpyHostToDevice, stream));
     }
-    if (!fail->status && p.n) coarse_correct(stream, p.ct, p.csz, p.cfactor, p.cscratch, 1, r, z, part_rz);
+    if (!fail->status && n) coarse_correct(stream, l.ct, l.csz, l.cfactor, l.cscratch, 1, r, z, part_rz);
     return 0;
 }
 
 }  // namespace
+
+hipError_t conjugated_gradient_patch(hipStream_t stream, size_t n, const int64_t *rowptr, const int32_t *colind, const double *values,
+                                     const double *b, double *x, size_t npatches, const int64_t *patch_ptr, const int32_t *patch_rows,
+                                     double convergence_threshold, double divergence_threshold, size_t max_iter, int *exit_reason,
+                                     size_t *iterations, double *relative_residual, int *status, int *refusal)
+{
+    int32_t pivot = 0;
+    return conjugated_gradient_two_level(stream, n, rowptr, colind, values, b, x, PatchTable{n, npatches, patch_ptr, patch_rows}, false,
+                                         CoarseTable{}, convergence_threshold, divergence_threshold, max_iter, exit_reason, iterations,
+                                         relative_residual, status, refusal, &pivot);
+}
+
+hipError_t conjugated_gradient_patch_coarse(hipStream_t stream, size_t n, const int64_t *rowptr, const int32_t *colind,
+                                            const double *values, const double *b, double *x, size_t npatches, const int64_t *patch_ptr,
+                                            const int32_t *patch_rows, size_t ncoarse, const int64_t *p_ptr, const int32_t *p_cols,
+                                            const double *p_vals, double convergence_threshold, double divergence_threshold,
+                                            size_t max_iter, int *exit_reason, size_t *iterations, double *relative_residual, int *status,
+                                            int *refusal, int32_t *pivot)
+{
+    return conjugated_gradient_two_level(stream, n, rowptr, colind, values, b, x, PatchTable{n, npatches, patch_ptr, patch_rows}, true,
+                                         CoarseTable{n, ncoarse, p_ptr, p_cols, p_vals}, convergence_threshold, divergence_threshold,
+                                         max_iter, exit_reason, iterations, relative_residual, status, refusal, pivot);
+}
 
 hipError_t conjugated_gradient_rows_patch_coarse(hipStream_t stream, const CgTransport *tp, int64_t row_begin, int64_t row_end,
                                                  const int64_t *rowptr, const int32_t *colind, const double *values, const double *b,
@@ -196,11 +293,8 @@ hipError_t conjugated_gradient_rows_patch_coarse(hipStream_t stream, const CgTra
     DeviceTmp tmp(stream);
     RowsPrecond p;
     p.tmp = &tmp;
-    p.n = n;
-    p.pt = PatchTable{n, npatches, patch_ptr, patch_rows, row_begin};
-    p.ct = CoarseTable{n, ncoarse, p_ptr, p_cols, p_vals};
-    p.psz = PatchSizes();
-    p.csz = CoarseSizes();
+    p.lv.pt = PatchTable{n, npatches, patch_ptr, patch_rows, row_begin};
+    p.lv.ct = CoarseTable{n, ncoarse, p_ptr, p_cols, p_vals};
     double *z = nullptr;
     if (!tmp.alloc(&z, n)) return tmp.error();
     const CgRowsPreconditioner pre{&p, rows_prepare, rows_setup, rows_apply, z};

@@ -1,5 +1,6 @@
-// rows_precond.hpp -- host entry point of rows_precond.hip: the conjugate gradient of solver_cg.hpp:63-144 on a row-partitioned
-// system with the patches of patch_precond.hpp and the Galerkin coarse level of coarse_precond.hpp, both partitioned by rows.
+// rows_precond.hpp -- host entry points of rows_precond.hip: the conjugate gradient of solver_cg.hpp:63-144 with the patches of
+// patch_precond.hpp and the Galerkin coarse level of coarse_precond.hpp, on one rank and on a row-partitioned system with both
+// partitioned by rows.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -11,6 +12,23 @@
 
 namespace pa {
 
+// ---- one rank: z = (patch sum), and z = (patch sum) + (coarse term) ----
+// status: 0 solved (see exit_reason), 1 table refused (*refusal), 2 a patch is not positive definite; x is written only with 0
+hipError_t conjugated_gradient_patch(hipStream_t stream, size_t n, const int64_t *rowptr, const int32_t *colind, const double *values,
+                                     const double *b, double *x, size_t npatches, const int64_t *patch_ptr, const int32_t *patch_rows,
+                                     double convergence_threshold, double divergence_threshold, size_t max_iter, int *exit_reason,
+                                     size_t *iterations, double *relative_residual, int *status, int *refusal);
+// status: 0 solved (see exit_reason), 1 patch table refused, 2 a patch is not positive definite, 3 coarse table refused
+// (*refusal: its code), 4 the coarse matrix is not positive definite (*pivot); x is written only with 0.  A refused table of either
+// level is reported before a patch that is not positive definite.
+hipError_t conjugated_gradient_patch_coarse(hipStream_t stream, size_t n, const int64_t *rowptr, const int32_t *colind,
+                                            const double *values, const double *b, double *x, size_t npatches, const int64_t *patch_ptr,
+                                            const int32_t *patch_rows, size_t ncoarse, const int64_t *p_ptr, const int32_t *p_cols,
+                                            const double *p_vals, double convergence_threshold, double divergence_threshold,
+                                            size_t max_iter, int *exit_reason, size_t *iterations, double *relative_residual, int *status,
+                                            int *refusal, int32_t *pivot);
+
+// ---- a row-partitioned system ----
 // what this rank's status 5 or 6 was about: level 1 the patches, 2 the coarse level; refusal: the code of patch_refusal_text /
 // coarse_refusal_text (status 5); pivot: j + 1 for the first non-positive pivot j of the coarse matrix (status 6, level 2)
 struct RowsPrecondReport {

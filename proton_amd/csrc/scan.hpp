@@ -1,7 +1,10 @@
 // scan.hpp -- exclusive prefix count of byte flags over n items: a three-pass scan (per-block
 // counts, scan of the block counts by one block, per-block rescan with the block offset).  Used for
 // the compress tables of obstacle_assembler (hho.hpp:538-578) and for the run heads of the device
-// CSR build (csr.hip).  Kernels have internal linkage: the header is included in several units.
+// CSR build (csr.hip), and for the tables of the preconditioners (patch_precond.hip, coarse_precond.hip,
+// capi_solver.hip), whose host side -- scan, read the total, wait -- is stated here too: scan_block_counts
+// for per-block counts a kernel left, scan_flags for byte flags.  Kernels and host helpers have internal
+// linkage: the header is included in several units.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -86,6 +89,36 @@ static __global__ __launch_bounds__(SCAN_BLOCK) void active_tables_kernel(const 
         }
         active_before += flag[k];
     }
+}
+
+// ---- "scan and read the total" on the host: what follows a kernel that left per-block counts.  One wait for the stream each.
+// k arrays of nblocks block counts (room for nblocks + 1 each): scanned in place, their totals to counts[j][nblocks] and to totals[j]
+static inline hipError_t scan_block_counts(hipStream_t stream, uint32_t nblocks, int k, uint32_t *const *counts, uint32_t *totals)
+{
+    for (int j = 0; j < k; ++j) hipLaunchKernelGGL(active_block_scan_kernel, dim3(1), dim3(SCAN_BLOCK), 0, stream, counts[j], nblocks);
+    hipError_t e = hipGetLastError();
+    for (int j = 0; j < k && e == hipSuccess; ++j)
+        e = hipMemcpyAsync(&totals[j], counts[j] + nblocks, sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+    return e == hipSuccess ? hipStreamSynchronize(stream) : e;
+}
+static inline hipError_t scan_block_counts(hipStream_t stream, uint32_t nblocks, uint32_t *counts, uint32_t *total)
+{
+    return scan_block_counts(stream, nblocks, 1, &counts, total);
+}
+
+// the tiles of n flags, and the whole scan of them: the two compress tables of active_tables_kernel and the number of set flags.
+// counts: scan_tiles(n) + 1
+inline uint32_t scan_tiles(uint32_t n) { return (n + SCAN_TILE - 1) / SCAN_TILE; }
+static inline hipError_t scan_flags(hipStream_t stream, const uint8_t *flags, uint32_t n, uint32_t *counts, int32_t *A_ct, int32_t *B_ct,
+                                    uint32_t *total)
+{
+    const uint32_t nb = scan_tiles(n);
+    hipLaunchKernelGGL(active_count_kernel, dim3(nb), dim3(SCAN_BLOCK), 0, stream, flags, n, counts);
+    hipLaunchKernelGGL(active_block_scan_kernel, dim3(1), dim3(SCAN_BLOCK), 0, stream, counts, nb);
+    hipLaunchKernelGGL(active_tables_kernel, dim3(nb), dim3(SCAN_BLOCK), 0, stream, flags, n, counts, A_ct, B_ct);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(total, counts + nb, sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+    return e == hipSuccess ? hipStreamSynchronize(stream) : e;
 }
 
 }  // namespace pa
