@@ -98,6 +98,12 @@ const char *pa_last_error(pa_context *ctx);      /* text of the last HIP failure
  * between its two kernels) -- and stays with the
  * context for reuse.  pa_context_trim waits for the context's stream and gives it back to the device. */
 int pa_context_set_record_cap(pa_context *ctx, size_t bytes);
+/* The columns up to which the whole-mesh table builders pa_condensed_coarse[_query] and pa_interface_condensed_coarse[_query]
+ * serve a table (the coarse spaces of solver_cg.hpp:63-144's preconditioner, cuthho_square.cpp:915-919): PA_COARSE_MAX_NODES by
+ * default -- what the exactly solved level of pa_coarse_precond_* takes --, up to PA_SMOOTHED_MAX_NODES for the tables of smoothed
+ * levels (pa_smoothed_level_*); 0 restores the default, a larger value is PA_ERR_INVALID_ARG.  The builders of a slab's rows
+ * (pa_condensed_rows_coarse, pa_interface_rows_coarse) and pa_coarse_precond_* keep PA_COARSE_MAX_NODES. */
+int pa_context_set_coarse_table_cap(pa_context *ctx, size_t max_columns);
 int pa_context_trim(pa_context *ctx);
 int pa_abi_version(void);
 
@@ -607,6 +613,72 @@ enum { PA_COARSE_ONE = 0, PA_COARSE_BY_SIDE = 1 };
 int pa_condensed_coarse_query(pa_context *ctx, pa_degree_info di, int H, int parts, int where, size_t *ncoarse, size_t *entries);
 int pa_condensed_coarse(pa_context *ctx, pa_degree_info di, int H, int parts, int where, int64_t *d_p_ptr, int32_t *d_p_cols,
                         double *d_p_vals);
+
+/* ---- smoothed hat levels next to the patches and the exact level: the additive multilevel form ------------
+ * One exactly solved level is bound to PA_COARSE_MAX_NODES columns by its dense factor, so its H grows with the mesh and the
+ * iteration count with H / h.  A SMOOTHED level is a coarse table whose Galerkin matrix is replaced by its diagonal:
+ *     z = (accumulate ? z : 0) + P D^-1 P^T r,   D = diag(P^T A P),   d_j = sum_i P_ij (sum_k A_ik P_kj)
+ * With smoothed levels on nested hat spaces (H = 2, 4, 8, ..) below one small exact level,
+ *     z = sum_p R_p^T A_p^-1 R_p r + sum_l P_l D_l^-1 P_l^T r + P_c (P_c^T A P_c)^-1 P_c^T r,
+ * the count stops growing with 1 / h.  The table format and row rules are those of pa_coarse_precond_* (rows of 0 to
+ * PA_COARSE_MAX_ROW_ENTRIES entries, columns ascending within [0, ncoarse), finite values), with ncoarse from 1 to
+ * PA_SMOOTHED_MAX_NODES: there is no dense matrix.  A table that breaks a rule is refused with PA_ERR_INVALID_ARG and text in
+ * pa_last_error(), checked on the device before anything is indexed with it, and no output buffer is touched (d_scratch is no
+ * output).  Every level prolongs straight to the fine rows: there is no table between levels.
+ * Sums: entry e of a column (by fine row ascending) goes to slot e mod 64; a slot adds its entries in ascending order with fused
+ * multiply-adds; the 64 slots are added by the xor tree 32, 16, 8, 4, 2, 1.  A column is owned by a wavefront or by a quarter of
+ * one (lanes_per_column, chosen from the mean column length: 16 up to 32 entries, else 64); the bits do not depend on the choice.
+ * No floating-point atomics: the same bits from call to call. */
+#define PA_SMOOTHED_MAX_NODES (1u << 24)
+#define PA_MULTILEVEL_MAX_LEVELS 8
+typedef struct {
+    uint64_t entries;            /* d_p_ptr[nrows]                                                                     */
+    uint64_t pt_bytes;           /* bytes of d_pt: P^T in CSR (row pointer, fine rows ascending within a row, values)   */
+    uint64_t dinv_doubles;       /* doubles of d_dinv: ncoarse                                                          */
+    uint64_t scratch_bytes;      /* bytes of d_scratch (the coarse vector of an apply, the work space of the set-up)    */
+    int32_t lanes_per_column;    /* 16 or 64                                                                            */
+} pa_smoothed_level_info;
+/* solver_cg.hpp:63-144, cuthho_square.cpp:915-919: what a smoothed level needs; reads d_p_ptr only (ncoarse within
+ * 1..PA_SMOOTHED_MAX_NODES and rows of 0..4 entries, else PA_ERR_INVALID_ARG).  Waits for the stream. */
+int pa_smoothed_level_query(pa_context *ctx, size_t nrows, size_t ncoarse, const int64_t *d_p_ptr, pa_smoothed_level_info *out);
+/* The set-up of solver_cg.hpp:63-144 (its lines 77-80: the inverse diagonal, here of P^T A P) for a smoothed level: validates the
+ * table, builds P^T into d_pt -- the entries keyed by (column, entry index) and radix-sorted, linear in the entries whatever the
+ * columns' lengths --, forms d_j in the order stated above (row i of A walked in its entry order, column j looked up in row k of
+ * P) and stores 1 / d_j into d_dinv.  A column whose d_j is not a positive finite number, an empty column included: *column =
+ * j + 1 for the first such j (host, may be NULL; 0 otherwise) and PA_ERR_NOT_SPD; d_dinv is then not written (d_pt is work space,
+ * not a result).  Waits for the stream. */
+int pa_smoothed_level_setup(pa_context *ctx, size_t nrows, const int64_t *d_rowptr, const int32_t *d_colind, const double *d_values,
+                            size_t ncoarse, const int64_t *d_p_ptr, const int32_t *d_p_cols, const double *d_p_vals, void *d_pt,
+                            double *d_dinv, void *d_scratch, int32_t *column);
+/* The preconditioner's product of solver_cg.hpp:63-144 (its lines 84 and 126) for a smoothed level: d_z = (accumulate ? d_z : 0)
+ * + P D^-1 P^T d_r with the table, d_pt, d_dinv and d_scratch of a pa_smoothed_level_setup that returned PA_OK: one restriction
+ * scaled by d_dinv, one gather of at most 4 terms per row added in entry order. */
+int pa_smoothed_level_apply(pa_context *ctx, size_t nrows, size_t ncoarse, const int64_t *d_p_ptr, const int32_t *d_p_cols,
+                            const double *d_p_vals, const void *d_pt, const double *d_dinv, void *d_scratch, int accumulate,
+                            const double *d_r, double *d_z);
+typedef struct {
+    size_t ncoarse;
+    const int64_t *d_p_ptr;
+    const int32_t *d_p_cols;
+    const double *d_p_vals;
+} pa_coarse_table;
+/* conjugated_gradient (solver_cg.hpp:63-144; the solve of cuthho_square.cpp:915-919) with the multilevel z above: the arguments
+ * and the three results of pa_conjugated_gradient_patch, `levels` (a HOST array of nlevels smoothed tables, 0 to
+ * PA_MULTILEVEL_MAX_LEVELS; NULL only with nlevels = 0) and `exact` (the table of the exactly solved level as
+ * pa_conjugated_gradient_patch_coarse takes it; NULL: none).  The same recurrences, exit tests and exit order.  The terms of z are
+ * added in the order patches, levels 0, 1, .., exact level; the gathers of all levels share one pass over z, which also forms the
+ * partial sums of r . z.  The factors and the D^-1 vectors live for the call.  Refusals leave d_x untouched, in this order: the
+ * patch table, each level's table in the caller's order (its index in pa_last_error()), the exact table (PA_ERR_INVALID_ARG);
+ * then, before the first iteration, PA_ERR_NOT_SPD of the patches, of a level (its index and the column in pa_last_error()) or of
+ * the exact level (whose product A P is judged with its factor).  nlevels = 0: d_x and the three results are
+ * pa_conjugated_gradient_patch_coarse's bit for bit, and pa_conjugated_gradient_patch's with exact = NULL as well.  One rank: the
+ * row-partitioned solver (pa_conjugated_gradient_rows_patch_coarse) takes no smoothed levels. */
+int pa_conjugated_gradient_multilevel(pa_context *ctx, size_t nrows, const int64_t *d_rowptr, const int32_t *d_colind,
+                                      const double *d_values, const double *d_b, double *d_x,
+                                      size_t npatches, const int64_t *d_patch_ptr, const int32_t *d_patch_rows,
+                                      size_t nlevels, const pa_coarse_table *levels, const pa_coarse_table *exact,
+                                      double convergence_threshold, double divergence_threshold, size_t max_iter,
+                                      int32_t *exit_reason, size_t *iterations, double *relative_residual);
 
 /* ---- cutHHO (fictitious domain, `cuthho_square -f`) -----------------------------------------
  * circle_level_set / line_level_set, apps/cuthho/cuthho_square.cpp:56-124 */

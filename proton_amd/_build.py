@@ -2,7 +2,7 @@
 
 One translation unit per (cell degree, face degree, quadrature kind) listed in
 csrc/pa_configs.def, compiled in parallel, plus the C ABI by workload (csrc/capi.hip, csrc/capi_local_ops.hip,
-csrc/capi_assembly.hip, csrc/capi_solver.hip, csrc/capi_obstacle.hip, csrc/capi_cut.hip, csrc/capi_interface.hip), csrc/csr.hip, csrc/solver.hip, csrc/patch_precond.hip, csrc/coarse_precond.hip, csrc/rows_precond.hip,
+csrc/capi_assembly.hip, csrc/capi_solver.hip, csrc/capi_obstacle.hip, csrc/capi_cut.hip, csrc/capi_interface.hip), csrc/csr.hip, csrc/solver.hip, csrc/patch_precond.hip, csrc/coarse_precond.hip, csrc/multilevel_precond.hip, csrc/rows_precond.hip,
 csrc/condensed.hip, csrc/assembler_csr.hip, csrc/interface_csr.hip, csrc/interface_condensed.hip, csrc/fictdom_condensed.hip,
 csrc/obstacle_csr.hip, csrc/obstacle_solve.hip and csrc/comm.hip; linked into
 proton_amd/lib/libproton_amd.so.  hipcc cross-compiles without a GPU.
@@ -140,7 +140,7 @@ def build(force=False, verbose=False, jobs=None):
              else PER_CONFIG_FLAGS.get((cd, fd, q), []))
         if force or _stale(obj, defs, newest):
             todo.append((os.path.join(CSRC, "hho_inst.hip"), obj, defs))
-    for unit in ("capi", "capi_local_ops", "capi_assembly", "capi_solver", "capi_obstacle", "capi_cut", "capi_interface", "csr", "solver", "patch_precond", "coarse_precond", "rows_precond", "condensed", "assembler_csr", "interface_csr", "interface_condensed", "fictdom_condensed", "obstacle_csr", "obstacle_solve", "comm"):
+    for unit in ("capi", "capi_local_ops", "capi_assembly", "capi_solver", "capi_obstacle", "capi_cut", "capi_interface", "csr", "solver", "patch_precond", "coarse_precond", "multilevel_precond", "rows_precond", "condensed", "assembler_csr", "interface_csr", "interface_condensed", "fictdom_condensed", "obstacle_csr", "obstacle_solve", "comm"):
         unit_obj = os.path.join(OBJ_DIR, unit + ".o")
         objs.append(unit_obj)
         if force or _stale(unit_obj, [], newest):

@@ -364,6 +364,68 @@ class BatchAssembler:
             rows.data_ptr(), ncoarse, cptr.data_ptr(), ccols.data_ptr(), cvals.data_ptr(), tol, div, max_iter)
         return x, reason, iters, rr
 
+    # ---- smoothed levels (multilevel_precond.hip) and the conjugate gradient with patches, smoothed levels and an exact level ----
+    def smoothed_level_setup(self, rowptr, colind, values, coarse):
+        """pa_smoothed_level_query + pa_smoothed_level_setup on the table `coarse` = (p_ptr, p_cols, p_vals, ncoarse) -> dict(pt,
+        dinv, scratch, column, sizes, coarse, n): what smoothed_level_apply takes.  column > 0: d_j of column - 1 is not a positive
+        finite number (dinv is then not written)."""
+        ptr, cols, vals, ncoarse = coarse
+        n = rowptr.numel() - 1
+        sz = self.ctx.smoothed_level_query(n, ncoarse, ptr.data_ptr())
+        pt = torch.zeros(max(sz.pt_bytes, 1), dtype=torch.uint8, device=self.device)       # (its parts are padded to 256 bytes)
+        dinv = torch.zeros(max(sz.dinv_doubles, 1), dtype=torch.float64, device=self.device)
+        scratch = torch.empty(max(sz.scratch_bytes, 1), dtype=torch.uint8, device=self.device)
+        column = self.ctx.smoothed_level_setup(n, rowptr.data_ptr(), colind.data_ptr(), values.data_ptr(), ncoarse, ptr.data_ptr(),
+                                               cols.data_ptr(), vals.data_ptr(), pt.data_ptr(), dinv.data_ptr(), scratch.data_ptr())
+        return {"pt": pt, "dinv": dinv[:ncoarse], "scratch": scratch, "column": column, "sizes": sz, "coarse": coarse, "n": n}
+
+    def smoothed_level_apply(self, pre, r, z=None, accumulate=False):
+        """z = (accumulate ? z : 0) + P diag(P^T A P)^-1 P^T r with what smoothed_level_setup returned"""
+        ptr, cols, vals, ncoarse = pre["coarse"]
+        if z is None:
+            z = torch.zeros_like(r) if accumulate else torch.empty_like(r)
+        self.ctx.smoothed_level_apply(pre["n"], ncoarse, ptr.data_ptr(), cols.data_ptr(), vals.data_ptr(), pre["pt"].data_ptr(),
+                                      pre["dinv"].data_ptr(), pre["scratch"].data_ptr(), accumulate, r.data_ptr(), z.data_ptr())
+        return z
+
+    def conjugated_gradient_multilevel(self, rowptr, colind, values, b, patches, levels, exact=None, tol=1e-9, div=100.0, max_iter=1000,
+                                       x=None):
+        """solver_cg.hpp:63-144 with z = (patch sum) + (the smoothed levels in their order) + (the exact level, if any); levels: a
+        sequence of tables (p_ptr, p_cols, p_vals, ncoarse), exact: one or None -> (x, exit_reason, iterations, relative residual)"""
+        ptr, rows = patches
+        tup = lambda t: (t[3], t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
+        if x is None:
+            x = torch.empty_like(b)
+        reason, iters, rr = self.ctx.conjugated_gradient_multilevel(
+            b.numel(), rowptr.data_ptr(), colind.data_ptr(), values.data_ptr(), b.data_ptr(), x.data_ptr(), ptr.numel() - 1, ptr.data_ptr(),
+            rows.data_ptr(), [tup(t) for t in levels], None if exact is None else tup(exact), tol, div, max_iter)
+        return x, reason, iters, rr
+
+    @staticmethod
+    def _nested_levels(coarse_levels, coarse, patches):
+        """the H of the smoothed levels as a list: each divides the next, the last divides `coarse`"""
+        hs = [int(h) for h in coarse_levels]
+        if patches is None:
+            raise ValueError("coarse_levels needs patches")
+        if len(hs) > capi.MULTILEVEL_MAX_LEVELS or any(h < 1 or h != g for h, g in zip(hs, coarse_levels)):
+            raise ValueError("coarse_levels: up to %d integers >= 1" % capi.MULTILEVEL_MAX_LEVELS)
+        for a, nxt in zip(hs, hs[1:] + ([int(coarse)] if coarse is not None else [])):
+            if nxt % a:
+                raise ValueError("coarse_levels: %d does not divide %d (the hat spaces must be nested)" % (a, nxt))
+        return hs
+
+    def _multilevel_solve(self, rowptr, colind, values, b, patches, hs, coarse, table, **kw):
+        """conjugated_gradient_multilevel on the tables table(H) of hs and of coarse (None: no exact level); the context's table cap
+        is raised for the smoothed levels' tables and put back"""
+        cap = self.ctx.coarse_table_cap
+        self.ctx.set_coarse_table_cap(capi.SMOOTHED_MAX_NODES)
+        try:
+            levels = [table(h) for h in hs]
+        finally:
+            self.ctx.set_coarse_table_cap(cap)
+        exact = table(int(coarse)) if coarse is not None else None
+        return self.conjugated_gradient_multilevel(rowptr, colind, values, b, patches, levels, exact, **kw)
+
     # ---- both levels on the row-partitioned system (rows_precond.hip): the tables of this context's slab ----
     def condensed_rows_patches(self, cd, fd, kind):
         """condensed_patches for the rows this context's slab owns (generate_mesh(.., rows=..); a whole mesh is the slab of all
@@ -401,19 +463,26 @@ class BatchAssembler:
             ptr.numel() - 1, ptr.data_ptr(), rows.data_ptr(), ncoarse, _ptr(cptr), _ptr(ccols), _ptr(cvals), tol, div, max_iter)
         return x, reason, iters, rr
 
-    def condensed_solve(self, cd, fd, cond, g=None, tol=1e-9, div=100.0, max_iter=None, precond=True, patches=None, coarse=None):
+    def condensed_solve(self, cd, fd, cond, g=None, tol=1e-9, div=100.0, max_iter=None, precond=True, patches=None, coarse=None,
+                        coarse_levels=None):
         """the face-only system of the records `cond` (condensed_ops) assembled (condensed_csr_pattern / condensed_csr_fill) and
         solved: patches None = conjugated_gradient (precond: Jacobi), "face" / "cell" = conjugated_gradient_patch on that table;
-        coarse = H (needs patches): conjugated_gradient_patch_coarse with the table condensed_coarse(H, "one") as well
+        coarse = H (needs patches): conjugated_gradient_patch_coarse with the table condensed_coarse(H, "one") as well;
+        coarse_levels = (H_0, H_1, ..) (needs patches; each divides the next, the last divides coarse): conjugated_gradient_multilevel
+        with a smoothed level on each of these tables below the exact one (coarse = None: no exact level)
         -> (xF, exit_reason, iterations, relative residual).  Whole-mesh contexts."""
         if coarse is not None and patches is None:
             raise ValueError("coarse needs patches")
+        hs = None if coarse_levels is None else self._nested_levels(coarse_levels, coarse, patches)
         rowptr, colind = self.condensed_csr_pattern(cd, fd)
         values, b = self.condensed_csr_fill(cd, fd, cond, g)
         if max_iter is None:
             max_iter = 4 * b.numel()
         if patches is None:
             return self.conjugated_gradient(rowptr, colind, values, b, tol=tol, div=div, max_iter=max_iter, precond=precond)
+        if hs is not None:
+            return self._multilevel_solve(rowptr, colind, values, b, self.condensed_patches(cd, fd, patches), hs, coarse,
+                                          lambda H: self.condensed_coarse(cd, fd, H, "one"), tol=tol, div=div, max_iter=max_iter)
         if coarse is not None:
             return self.conjugated_gradient_patch_coarse(rowptr, colind, values, b, self.condensed_patches(cd, fd, patches),
                                                          self.condensed_coarse(cd, fd, int(coarse), "one"), tol=tol, div=div,
@@ -695,16 +764,20 @@ class BatchAssembler:
         return full
 
     def fictdom_condensed_solve(self, fd, where=capi.LOC_NEGATIVE, rhs_fn=capi.FN_SIN_SIN_RHS, bcs_fn=capi.FN_SIN_SIN_SOL, tol=1e-13,
-                                g=None, max_iter=None, precond=True, overlap=False, patches=None, coarse=None):
+                                g=None, max_iter=None, precond=True, overlap=False, patches=None, coarse=None, coarse_levels=None,
+                                coarse_parts="side"):
         """cuthho_square.cpp:881-919 and :959-962 on the face-only system: the operators (pa_cut_uncut_rhs_batch,
         pa_cut_local_ops_batch; overlap: on the context's side stream), the records, condensed_csr_pattern / condensed_csr_fill,
         conjugated_gradient and the recovery -> (full solution vector, iterations, exit reason).  g: the boundary data
         (default: dirichlet_data of bcs_fn).  patches "face" / "cell": conjugated_gradient_patch on that table of condensed_patches
         in place of conjugated_gradient; coarse = H (needs patches): conjugated_gradient_patch_coarse with the table
-        condensed_coarse(H, "side") as well.  Whole-mesh contexts."""
+        condensed_coarse(H, "side") as well; coarse_levels = (H_0, H_1, ..) (needs patches; each divides the next, the last divides
+        coarse): conjugated_gradient_multilevel with a smoothed level on each of these tables of condensed_coarse(H, coarse_parts)
+        below the exact one (coarse = None: no exact level; coarse_parts is read with coarse_levels only).  Whole-mesh contexts."""
         cd = fd + 1
         if coarse is not None and patches is None:
             raise ValueError("coarse needs patches")
+        hs = None if coarse_levels is None else self._nested_levels(coarse_levels, coarse, patches)
         if g is None:
             g = self.dirichlet_data(fd, bcs_fn)
         cut = None
@@ -726,6 +799,10 @@ class BatchAssembler:
             max_iter = 4 * b.numel()
         if patches is None:
             xF, reason, iters, _ = self.conjugated_gradient(rowptr, colind, values, b, tol=tol, max_iter=max_iter, precond=precond)
+        elif hs is not None:
+            xF, reason, iters, _ = self._multilevel_solve(rowptr, colind, values, b, self.condensed_patches(cd, fd, patches), hs, coarse,
+                                                          lambda H: self.condensed_coarse(cd, fd, H, coarse_parts, where), tol=tol,
+                                                          max_iter=max_iter)
         elif coarse is not None:
             xF, reason, iters, _ = self.conjugated_gradient_patch_coarse(rowptr, colind, values, b, self.condensed_patches(cd, fd, patches),
                                                                          self.condensed_coarse(cd, fd, int(coarse), "side", where), tol=tol,
@@ -878,13 +955,17 @@ class BatchAssembler:
         return ptr, cols[:entries], vals[:entries], ncoarse
 
     def interface_condensed_solve(self, fd, ops, g=None, tol=1e-9, div=100.0, max_iter=None, precond=True, patches=None, coarse=None,
-                                  coarse_parts="side"):
+                                  coarse_parts="side", coarse_levels=None):
         """cuthho_square.cpp:1664-1743 on the face-only system from interface_local_ops' dict: the records, the pattern, the fill,
         conjugated_gradient (precond: Jacobi) or, patches "face" / "cell", conjugated_gradient_patch on that table of
         interface_condensed_patches, and the recovery; coarse = H (needs patches): conjugated_gradient_patch_coarse with the table
-        interface_condensed_coarse(H, coarse_parts) as well -> (full solution vector, iterations, exit reason)"""
+        interface_condensed_coarse(H, coarse_parts) as well; coarse_levels = (H_0, H_1, ..) (needs patches; each divides the next,
+        the last divides coarse): conjugated_gradient_multilevel with a smoothed level on each of these tables of
+        interface_condensed_coarse(H, coarse_parts) below the exact one (coarse = None: no exact level)
+        -> (full solution vector, iterations, exit reason)"""
         if coarse is not None and patches is None:
             raise ValueError("coarse needs patches")
+        hs = None if coarse_levels is None else self._nested_levels(coarse_levels, coarse, patches)
         rec = self.interface_condensed_ops(fd, ops)
         rowptr, colind = self.interface_condensed_csr_pattern(fd)
         values, b = self.interface_condensed_csr_fill(fd, rec, g)
@@ -892,6 +973,10 @@ class BatchAssembler:
             max_iter = 20 * b.numel()
         if patches is None:
             xF, reason, iters, _ = self.conjugated_gradient(rowptr, colind, values, b, tol=tol, div=div, max_iter=max_iter, precond=precond)
+        elif hs is not None:
+            xF, reason, iters, _ = self._multilevel_solve(rowptr, colind, values, b, self.interface_condensed_patches(fd, patches), hs, coarse,
+                                                          lambda H: self.interface_condensed_coarse(fd, H, coarse_parts), tol=tol, div=div,
+                                                          max_iter=max_iter)
         elif coarse is not None:
             xF, reason, iters, _ = self.conjugated_gradient_patch_coarse(rowptr, colind, values, b, self.interface_condensed_patches(fd, patches),
                                                                          self.interface_condensed_coarse(fd, int(coarse), coarse_parts),

@@ -20,7 +20,7 @@ STATUS = {0: "PA_OK", 1: "PA_ERR_INVALID_ARG", 2: "PA_ERR_INVALID_DEGREE", 3: "P
 EXPORTS = [
     "pa_abi_version", "pa_degree_info_equal", "pa_degree_info_make", "pa_sizes_for",
     "pa_context_create", "pa_context_destroy", "pa_context_synchronize", "pa_context_set_cut_overlap", "pa_last_error",
-    "pa_context_trim", "pa_context_set_record_cap",
+    "pa_context_trim", "pa_context_set_record_cap", "pa_context_set_coarse_table_cap",
     "pa_malloc", "pa_free", "pa_memcpy_h2d", "pa_memcpy_d2h", "pa_memset",
     "pa_mesh_upload", "pa_mesh_attach_device", "pa_mesh_generate", "pa_mesh_counts",
     "pa_local_ops_batch", "pa_cell_rhs_batch", "pa_cell_quadrature_points",
@@ -53,6 +53,7 @@ EXPORTS = [
     "pa_interface_condensed_patches_query", "pa_interface_condensed_patches",
     "pa_coarse_precond_query", "pa_coarse_precond_factor", "pa_coarse_precond_apply", "pa_conjugated_gradient_patch_coarse",
     "pa_condensed_coarse_query", "pa_condensed_coarse",
+    "pa_smoothed_level_query", "pa_smoothed_level_setup", "pa_smoothed_level_apply", "pa_conjugated_gradient_multilevel",
     "pa_conjugated_gradient_rows_patch_coarse", "pa_condensed_rows_patches_query", "pa_condensed_rows_patches",
     "pa_condensed_rows_coarse_query", "pa_condensed_rows_coarse",
     "pa_interface_condensed_coarse_query", "pa_interface_condensed_coarse",
@@ -152,6 +153,17 @@ class CoarsePrecondInfo(C.Structure):
 
 COARSE_ONE, COARSE_BY_SIDE = 0, 1
 COARSE_MAX_ROW_ENTRIES, COARSE_MAX_NODES = 4, 4096
+SMOOTHED_MAX_NODES, MULTILEVEL_MAX_LEVELS = 1 << 24, 8
+
+
+class SmoothedLevelInfo(C.Structure):
+    _fields_ = [("entries", C.c_uint64), ("pt_bytes", C.c_uint64), ("dinv_doubles", C.c_uint64), ("scratch_bytes", C.c_uint64),
+                ("lanes_per_column", C.c_int32)]
+
+
+class CoarseTable(C.Structure):
+    """pa_coarse_table: one table of pa_conjugated_gradient_multilevel (device pointers)"""
+    _fields_ = [("ncoarse", C.c_size_t), ("d_p_ptr", C.c_void_p), ("d_p_cols", C.c_void_p), ("d_p_vals", C.c_void_p)]
 
 
 class LevelSet(C.Structure):
@@ -200,6 +212,7 @@ def lib():
     L.pa_context_set_cut_overlap.argtypes = [vp, C.c_int]
     L.pa_context_trim.argtypes = [vp]
     L.pa_context_set_record_cap.argtypes = [vp, sz]
+    L.pa_context_set_coarse_table_cap.argtypes = [vp, sz]
     L.pa_last_error.argtypes = [vp]
     L.pa_last_error.restype = C.c_char_p
     L.pa_malloc.argtypes = [vp, sz, C.POINTER(vp)]
@@ -239,6 +252,11 @@ def lib():
                                                       C.POINTER(C.c_int32), C.POINTER(sz), C.POINTER(C.c_double)]
     L.pa_condensed_coarse_query.argtypes = [vp, DegreeInfo, C.c_int, C.c_int, C.c_int, C.POINTER(sz), C.POINTER(sz)]
     L.pa_condensed_coarse.argtypes = [vp, DegreeInfo, C.c_int, C.c_int, C.c_int, dp, dp, dp]
+    L.pa_smoothed_level_query.argtypes = [vp, sz, sz, dp, C.POINTER(SmoothedLevelInfo)]
+    L.pa_smoothed_level_setup.argtypes = [vp, sz, dp, dp, dp, sz, dp, dp, dp, dp, dp, dp, C.POINTER(C.c_int32)]
+    L.pa_smoothed_level_apply.argtypes = [vp, sz, sz, dp, dp, dp, dp, dp, dp, C.c_int, dp, dp]
+    L.pa_conjugated_gradient_multilevel.argtypes = [vp, sz, dp, dp, dp, dp, dp, sz, dp, dp, sz, C.POINTER(CoarseTable), C.POINTER(CoarseTable),
+                                                    C.c_double, C.c_double, sz, C.POINTER(C.c_int32), C.POINTER(sz), C.POINTER(C.c_double)]
     L.pa_conjugated_gradient_rows_patch_coarse.argtypes = [vp, C.POINTER(CgTransport), C.c_int64, C.c_int64, dp, dp, dp, dp, dp, sz, dp, dp, sz,
                                                            dp, dp, dp, C.c_double, C.c_double, sz, C.POINTER(C.c_int32), C.POINTER(sz),
                                                            C.POINTER(C.c_double), C.POINTER(C.c_int32)]
@@ -448,6 +466,7 @@ class Context:
             raise ProtonAmdError(st, "pa_context_create", "is a GPU visible?")
         self.h = h
         self.device = device
+        self.coarse_table_cap = COARSE_MAX_NODES
 
     def _ck(self, st, where):
         if st != 0:
@@ -472,6 +491,11 @@ class Context:
 
     def set_record_cap(self, nbytes):
         self._ck(self._L.pa_context_set_record_cap(self.h, nbytes), "pa_context_set_record_cap")
+
+    def set_coarse_table_cap(self, max_columns):
+        """the columns up to which condensed_coarse / interface_condensed_coarse serve a table; 0: the default, COARSE_MAX_NODES"""
+        self._ck(self._L.pa_context_set_coarse_table_cap(self.h, max_columns), "pa_context_set_coarse_table_cap")
+        self.coarse_table_cap = max_columns or COARSE_MAX_NODES
 
     def set_cut_overlap(self, on):
         self._ck(self._L.pa_context_set_cut_overlap(self.h, 1 if on else 0), "pa_context_set_cut_overlap")
@@ -609,6 +633,37 @@ class Context:
         self._ck(self._L.pa_conjugated_gradient_patch_coarse(self.h, nrows, rowptr, colind, values, b, x, npatches, patch_ptr, patch_rows,
                                                              ncoarse, p_ptr, p_cols, p_vals, tol, div, max_iter, C.byref(reason),
                                                              C.byref(iters), C.byref(rr)), "pa_conjugated_gradient_patch_coarse")
+        return reason.value, iters.value, rr.value
+
+    def smoothed_level_query(self, nrows, ncoarse, p_ptr):
+        out = SmoothedLevelInfo()
+        self._ck(self._L.pa_smoothed_level_query(self.h, nrows, ncoarse, p_ptr, C.byref(out)), "pa_smoothed_level_query")
+        return out
+
+    def smoothed_level_setup(self, nrows, rowptr, colind, values, ncoarse, p_ptr, p_cols, p_vals, pt, dinv, scratch):
+        """-> 0, or j + 1 for the first column j whose d_j is not a positive finite number; other refusals raise"""
+        column = C.c_int32(0)
+        st = self._L.pa_smoothed_level_setup(self.h, nrows, rowptr, colind, values, ncoarse, p_ptr, p_cols, p_vals, pt, dinv, scratch,
+                                             C.byref(column))
+        if st != 6:
+            self._ck(st, "pa_smoothed_level_setup")
+        return column.value
+
+    def smoothed_level_apply(self, nrows, ncoarse, p_ptr, p_cols, p_vals, pt, dinv, scratch, accumulate, r, z):
+        self._ck(self._L.pa_smoothed_level_apply(self.h, nrows, ncoarse, p_ptr, p_cols, p_vals, pt, dinv, scratch, int(accumulate), r, z),
+                 "pa_smoothed_level_apply")
+
+    def conjugated_gradient_multilevel(self, nrows, rowptr, colind, values, b, x, npatches, patch_ptr, patch_rows, levels, exact=None,
+                                       tol=1e-9, div=100.0, max_iter=1000):
+        """levels: a sequence of (ncoarse, p_ptr, p_cols, p_vals) with device addresses, exact: one such tuple or None
+        -> (reason, iterations, rr)"""
+        arr = (CoarseTable * max(len(levels), 1))(*[CoarseTable(*t) for t in levels])
+        ex = CoarseTable(*exact) if exact is not None else None
+        reason, iters, rr = C.c_int32(0), C.c_size_t(0), C.c_double(0.0)
+        self._ck(self._L.pa_conjugated_gradient_multilevel(self.h, nrows, rowptr, colind, values, b, x, npatches, patch_ptr, patch_rows,
+                                                           len(levels), arr if len(levels) else None, C.byref(ex) if ex is not None else None,
+                                                           tol, div, max_iter, C.byref(reason), C.byref(iters), C.byref(rr)),
+                 "pa_conjugated_gradient_multilevel")
         return reason.value, iters.value, rr.value
 
     def condensed_coarse_query(self, di, H, parts, where):

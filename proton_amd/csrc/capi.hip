@@ -189,6 +189,13 @@ int pa_context_trim(pa_context *ctx)
     return PA_OK;
 }
 
+int pa_context_set_coarse_table_cap(pa_context *ctx, size_t max_columns)
+{
+    if (!ctx || max_columns > ((size_t)1 << 24)) return PA_ERR_INVALID_ARG;
+    ctx->coarse_table_cap = max_columns ? max_columns : (size_t)PA_COARSE_MAX_NODES;
+    return PA_OK;
+}
+
 int pa_context_set_record_cap(pa_context *ctx, size_t bytes)
 {
     if (!ctx || bytes < ((size_t)1 << 20)) return PA_ERR_INVALID_ARG;

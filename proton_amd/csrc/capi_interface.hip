@@ -375,7 +375,7 @@ int pa_interface_condensed_patches(pa_context *ctx, int face_deg, int kind, int6
 }
 
 // the coarse table of the face-only system: the refusals of pa_interface_csr_* in its order, then H, the parts and the outputs
-// (with `write`), then the side stream joined; sized on the device, written only if the columns are within 1..PA_COARSE_MAX_NODES
+// (with `write`), then the side stream joined; sized on the device, written only if the columns are within 1..the context's cap (PA_COARSE_MAX_NODES unless set)
 static int if_coarse(pa_context *ctx, const char *who, int face_deg, int H, int parts, bool write, size_t *ncoarse, size_t *entries,
                      int64_t *d_p_ptr, int32_t *d_p_cols, double *d_p_vals)
 {
@@ -387,8 +387,9 @@ static int if_coarse(pa_context *ctx, const char *who, int face_deg, int H, int 
     PA_HIP(ctx, join_side_stream(ctx));      // cut-cell work still out on the side stream
     const pa::IfCoarseMesh m{ifcsr_mesh(ctx), ctx->faces.sm, ctx->faces.face_pts.get(), parts == PA_COARSE_BY_SIDE ? 1 : 0};
     uint64_t nc = 0, ne = 0;
-    PA_HIP(ctx, pa::interface_condensed_coarse(ctx->stream, m, face_deg + 1, H, &nc, &ne, write ? d_p_ptr : nullptr, d_p_cols, d_p_vals));
-    if (nc < 1 || nc > (uint64_t)PA_COARSE_MAX_NODES) return coarse_count_refused(ctx, who, H, nc);
+    const uint64_t cap = ctx->coarse_table_cap;
+    PA_HIP(ctx, pa::interface_condensed_coarse(ctx->stream, m, face_deg + 1, H, cap, &nc, &ne, write ? d_p_ptr : nullptr, d_p_cols, d_p_vals));
+    if (nc < 1 || nc > cap) return coarse_count_refused(ctx, who, H, nc, cap);
     if (ncoarse) *ncoarse = (size_t)nc;
     if (entries) *entries = (size_t)ne;
     return PA_OK;

@@ -11,6 +11,7 @@
 #include "coarse_precond.hpp"
 #include "context.hpp"
 #include "device_tmp.hpp"
+#include "multilevel_precond.hpp"
 #include "patch_precond.hpp"
 #include "rows_precond.hpp"
 #include "scan.hpp"
@@ -38,6 +39,14 @@ static int patch_not_spd(pa_context *ctx, const char *who, const char *what)
 static int coarse_not_spd(pa_context *ctx, const char *who, int32_t pivot)
 {
     ctx->last_error = std::string(who) + ": the coarse matrix is not positive definite (pivot " + std::to_string(pivot - 1) + ")";
+    return PA_ERR_NOT_SPD;
+}
+
+// level < 0: the one level of the call
+static int level_not_spd(pa_context *ctx, const char *who, int level, int32_t column)
+{
+    ctx->last_error = std::string(who) + ": the diagonal of P^T A P is not positive (column " + std::to_string(column - 1) +
+                      (level >= 0 ? ", smoothed level " + std::to_string(level) + ")" : std::string(")"));
     return PA_ERR_NOT_SPD;
 }
 
@@ -302,6 +311,102 @@ int pa_conjugated_gradient_patch_coarse(pa_context *ctx, size_t nrows, const int
     return PA_OK;
 }
 
+// ---- a smoothed level (multilevel_precond.hip) and the conjugate gradient with patches, smoothed levels and an exact level ---------
+static int smoothed_sizes(pa_context *ctx, const char *who, size_t nrows, size_t ncoarse, const int64_t *d_p_ptr, pa::SmoothedSizes *sz)
+{
+    int refusal = 0;
+    PA_HIP(ctx, pa::smoothed_query(ctx->stream, nrows, ncoarse, d_p_ptr, sz, &refusal));
+    return refusal ? coarse_refused(ctx, who, refusal) : PA_OK;
+}
+
+int pa_smoothed_level_query(pa_context *ctx, size_t nrows, size_t ncoarse, const int64_t *d_p_ptr, pa_smoothed_level_info *out)
+{
+    if (!ctx || !d_p_ptr || !out) return PA_ERR_INVALID_ARG;
+    PA_HIP(ctx, hipSetDevice(ctx->device));
+    pa::SmoothedSizes sz;
+    const int st = smoothed_sizes(ctx, "pa_smoothed_level_query", nrows, ncoarse, d_p_ptr, &sz);
+    if (st != PA_OK) return st;
+    out->entries = sz.entries; out->pt_bytes = sz.pt_bytes; out->dinv_doubles = sz.dinv_doubles; out->scratch_bytes = sz.scratch_bytes;
+    out->lanes_per_column = sz.lanes;
+    return PA_OK;
+}
+
+int pa_smoothed_level_setup(pa_context *ctx, size_t nrows, const int64_t *d_rowptr, const int32_t *d_colind, const double *d_values,
+                            size_t ncoarse, const int64_t *d_p_ptr, const int32_t *d_p_cols, const double *d_p_vals, void *d_pt,
+                            double *d_dinv, void *d_scratch, int32_t *column)
+{
+    if (!ctx || !d_rowptr || !d_p_ptr || !d_pt || !d_dinv || !d_scratch) return PA_ERR_INVALID_ARG;
+    if (nrows && (!d_colind || !d_values || !d_p_cols || !d_p_vals)) return PA_ERR_INVALID_ARG;
+    PA_HIP(ctx, hipSetDevice(ctx->device));
+    const char *who = "pa_smoothed_level_setup";
+    pa::SmoothedSizes sz;
+    const int st = smoothed_sizes(ctx, who, nrows, ncoarse, d_p_ptr, &sz);
+    if (st != PA_OK) return st;
+    const pa::CoarseTable t{nrows, ncoarse, d_p_ptr, d_p_cols, d_p_vals};
+    int refusal = 0;
+    PA_HIP(ctx, pa::smoothed_validate(ctx->stream, t, sz, d_scratch, &refusal));
+    if (refusal) return coarse_refused(ctx, who, refusal);
+    int32_t col = 0;
+    PA_HIP(ctx, pa::smoothed_setup(ctx->stream, d_rowptr, d_colind, d_values, t, sz, d_pt, d_dinv, d_scratch, &col));
+    if (column) *column = col;
+    return col ? level_not_spd(ctx, who, -1, col) : PA_OK;
+}
+
+int pa_smoothed_level_apply(pa_context *ctx, size_t nrows, size_t ncoarse, const int64_t *d_p_ptr, const int32_t *d_p_cols,
+                            const double *d_p_vals, const void *d_pt, const double *d_dinv, void *d_scratch, int accumulate,
+                            const double *d_r, double *d_z)
+{
+    if (!ctx || !d_p_ptr || !d_pt || !d_dinv || !d_scratch) return PA_ERR_INVALID_ARG;
+    if (nrows && (!d_p_cols || !d_p_vals || !d_r || !d_z)) return PA_ERR_INVALID_ARG;
+    PA_HIP(ctx, hipSetDevice(ctx->device));
+    pa::SmoothedSizes sz;
+    const int st = smoothed_sizes(ctx, "pa_smoothed_level_apply", nrows, ncoarse, d_p_ptr, &sz);
+    if (st != PA_OK) return st;
+    const pa::CoarseTable t{nrows, ncoarse, d_p_ptr, d_p_cols, d_p_vals};
+    pa::smoothed_apply(ctx->stream, t, sz, d_pt, d_dinv, d_scratch, accumulate, d_r, d_z, nullptr);
+    PA_HIP(ctx, hipGetLastError());
+    return PA_OK;
+}
+
+int pa_conjugated_gradient_multilevel(pa_context *ctx, size_t nrows, const int64_t *d_rowptr, const int32_t *d_colind, const double *d_values,
+                                      const double *d_b, double *d_x, size_t npatches, const int64_t *d_patch_ptr,
+                                      const int32_t *d_patch_rows, size_t nlevels, const pa_coarse_table *levels,
+                                      const pa_coarse_table *exact, double convergence_threshold, double divergence_threshold,
+                                      size_t max_iter, int32_t *exit_reason, size_t *iterations, double *relative_residual)
+{
+    if (!ctx || !d_rowptr || nlevels > (size_t)PA_MULTILEVEL_MAX_LEVELS || (nlevels && !levels)) return PA_ERR_INVALID_ARG;
+    if (nrows && (!d_colind || !d_values || !d_b || !d_x || !d_patch_ptr || !d_patch_rows)) return PA_ERR_INVALID_ARG;
+    pa::CoarseTable lt[PA_MULTILEVEL_MAX_LEVELS], et{};
+    for (size_t k = 0; k <= nlevels; ++k) {
+        const pa_coarse_table *t = k < nlevels ? &levels[k] : exact;
+        if (!t) continue;
+        if (nrows && (!t->d_p_ptr || !t->d_p_cols || !t->d_p_vals)) return PA_ERR_INVALID_ARG;
+        (k < nlevels ? lt[k] : et) = pa::CoarseTable{nrows, t->ncoarse, t->d_p_ptr, t->d_p_cols, t->d_p_vals};
+    }
+    PA_HIP(ctx, hipSetDevice(ctx->device));
+    const char *who = "pa_conjugated_gradient_multilevel";
+    int reason = 0;
+    pa::MultilevelReport rep;
+    PA_HIP(ctx, pa::conjugated_gradient_multilevel(ctx->stream, nrows, d_rowptr, d_colind, d_values, d_b, d_x, npatches, d_patch_ptr, d_patch_rows,
+                                                   (int)nlevels, lt, exact ? &et : nullptr, convergence_threshold, divergence_threshold, max_iter,
+                                                   &reason, iterations, relative_residual, &rep));
+    switch (rep.status) {
+    case 1: return patch_refused(ctx, who, rep.refusal);
+    case 2: return patch_not_spd(ctx, who, "is not positive definite (pa_patch_precond_factor says which)");
+    case 3: return coarse_refused(ctx, who, rep.refusal);
+    case 4: return coarse_not_spd(ctx, who, rep.pivot);
+    case 5: {
+        const int st = coarse_refused(ctx, who, rep.refusal);
+        ctx->last_error += " (smoothed level " + std::to_string(rep.level) + ")";
+        return st;
+    }
+    case 6: return level_not_spd(ctx, who, rep.level, rep.pivot);
+    default: break;
+    }
+    if (exit_reason) *exit_reason = reason;
+    return PA_OK;
+}
+
 // ---- both levels on the row-partitioned system (rows_precond.hip), the tables of a slab, and the whole-mesh coarse table -----------
 int pa_conjugated_gradient_rows_patch_coarse(pa_context *ctx, const pa_cg_transport *transport, int64_t row_begin, int64_t row_end,
                                              const int64_t *d_rowptr, const int32_t *d_colind, const double *d_values, const double *d_b,
@@ -421,10 +526,10 @@ static int coarse_mesh(pa_context *ctx, pa_degree_info di, int H, int parts, int
     return PA_OK;
 }
 
-int coarse_count_refused(pa_context *ctx, const char *who, int H, uint64_t ncoarse)
+int coarse_count_refused(pa_context *ctx, const char *who, int H, uint64_t ncoarse, uint64_t max_columns)
 {
     ctx->last_error = std::string(who) + ": H = " + std::to_string(H) + " gives " + std::to_string(ncoarse) +
-                      " coarse columns; 1 to " + std::to_string(PA_COARSE_MAX_NODES) + " are served";
+                      " coarse columns; 1 to " + std::to_string(max_columns) + " are served";
     return PA_ERR_INVALID_ARG;
 }
 
@@ -435,8 +540,9 @@ int pa_condensed_coarse_query(pa_context *ctx, pa_degree_info di, int H, int par
     const int st = coarse_mesh(ctx, di, H, parts, where, &m);
     if (st != PA_OK) return st;
     uint64_t nc = 0, ne = 0;
-    PA_HIP(ctx, pa::condensed_coarse(ctx->stream, m, di.face_deg + 1, H, &nc, &ne, nullptr, nullptr, nullptr));
-    if (nc < 1 || nc > (uint64_t)PA_COARSE_MAX_NODES) return coarse_count_refused(ctx, "pa_condensed_coarse_query", H, nc);
+    const uint64_t cap = ctx->coarse_table_cap;
+    PA_HIP(ctx, pa::condensed_coarse(ctx->stream, m, di.face_deg + 1, H, cap, &nc, &ne, nullptr, nullptr, nullptr));
+    if (nc < 1 || nc > cap) return coarse_count_refused(ctx, "pa_condensed_coarse_query", H, nc, cap);
     *ncoarse = (size_t)nc;
     *entries = (size_t)ne;
     return PA_OK;
@@ -449,7 +555,8 @@ int pa_condensed_coarse(pa_context *ctx, pa_degree_info di, int H, int parts, in
     const int st = coarse_mesh(ctx, di, H, parts, where, &m);
     if (st != PA_OK) return st;
     uint64_t nc = 0, ne = 0;
-    PA_HIP(ctx, pa::condensed_coarse(ctx->stream, m, di.face_deg + 1, H, &nc, &ne, d_p_ptr, d_p_cols, d_p_vals));
-    if (nc < 1 || nc > (uint64_t)PA_COARSE_MAX_NODES) return coarse_count_refused(ctx, "pa_condensed_coarse", H, nc);
+    const uint64_t cap = ctx->coarse_table_cap;
+    PA_HIP(ctx, pa::condensed_coarse(ctx->stream, m, di.face_deg + 1, H, cap, &nc, &ne, d_p_ptr, d_p_cols, d_p_vals));
+    if (nc < 1 || nc > cap) return coarse_count_refused(ctx, "pa_condensed_coarse", H, nc, cap);
     return PA_OK;
 }

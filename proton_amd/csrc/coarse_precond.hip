@@ -102,6 +102,7 @@ const char *coarse_refusal_text(int refusal)
     case COARSE_BAD_NODES: return "coarse table: ncoarse must lie within 1 to 4096";
     case COARSE_TOO_LARGE: return "coarse table: 2^29 rows and more";
     case COARSE_W_OVERFLOW: return "coarse table: a row of A P holds more than 16 columns";
+    case COARSE_BAD_LEVEL_NODES: return "coarse table: ncoarse of a smoothed level must lie within 1 to 16777216";
     default: return "";
     }
 }
@@ -359,11 +360,12 @@ __global__ __launch_bounds__(RB) void coarse_prolong_kernel(size_t n, const int6
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-hipError_t coarse_query(hipStream_t stream, size_t n, size_t ncoarse, const int64_t *ptr, CoarseSizes *out, int *refusal)
+hipError_t coarse_check_ptr(hipStream_t stream, size_t n, size_t ncoarse, size_t max_nodes, const int64_t *ptr, uint64_t *entries_out,
+                            int *refusal)
 {
-    *out = CoarseSizes();
+    *entries_out = 0;
     *refusal = COARSE_OK;
-    if (ncoarse < 1 || ncoarse > (size_t)COARSE_MAX_NODES) { *refusal = COARSE_BAD_NODES; return hipSuccess; }
+    if (ncoarse < 1 || ncoarse > max_nodes) { *refusal = max_nodes == (size_t)COARSE_MAX_NODES ? COARSE_BAD_NODES : COARSE_BAD_LEVEL_NODES; return hipSuccess; }
     if (n >= ((size_t)1 << 29)) { *refusal = COARSE_TOO_LARGE; return hipSuccess; }          // 4 n entries stay below 2^31
     int32_t *d_flags = nullptr;
     hipError_t e = hipMalloc((void **)&d_flags, NFLAGS * 4);
@@ -380,7 +382,17 @@ hipError_t coarse_query(hipStream_t stream, size_t n, size_t ncoarse, const int6
     (void)hipFree(d_flags);
     if (e != hipSuccess) return e;
     if (h[FLAG_REFUSAL]) { *refusal = h[FLAG_REFUSAL]; return hipSuccess; }
-    out->entries = (uint64_t)entries;
+    *entries_out = (uint64_t)entries;
+    return hipSuccess;
+}
+
+hipError_t coarse_query(hipStream_t stream, size_t n, size_t ncoarse, const int64_t *ptr, CoarseSizes *out, int *refusal)
+{
+    *out = CoarseSizes();
+    uint64_t entries = 0;
+    const hipError_t e = coarse_check_ptr(stream, n, ncoarse, (size_t)COARSE_MAX_NODES, ptr, &entries, refusal);
+    if (e != hipSuccess || *refusal) return e;
+    out->entries = entries;
     size_t bytes = 0;
     pt_parts(nullptr, ncoarse, (size_t)entries, &bytes);
     out->pt_bytes = bytes;
@@ -392,16 +404,21 @@ hipError_t coarse_query(hipStream_t stream, size_t n, size_t ncoarse, const int6
 
 hipError_t coarse_validate(hipStream_t stream, const CoarseTable &t, const CoarseSizes &sz, void *scratch, int *refusal)
 {
-    *refusal = COARSE_OK;
     const Scratch s = scratch_parts(scratch, t.n, t.ncoarse, (size_t)sz.entries, nullptr);
+    return coarse_check_rows(stream, t, s.counts, s.flags, refusal);
+}
+
+hipError_t coarse_check_rows(hipStream_t stream, const CoarseTable &t, uint32_t *counts, int32_t *flags, int *refusal)
+{
+    *refusal = COARSE_OK;
     int32_t h[NFLAGS] = {0, 0, 0, 0};
-    hipError_t e = hipMemsetAsync(s.counts, 0, (t.ncoarse + 2) * 4, stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s.flags, 0, NFLAGS * 4, stream);
+    hipError_t e = hipMemsetAsync(counts, 0, (t.ncoarse + 2) * 4, stream);
+    if (e == hipSuccess) e = hipMemsetAsync(flags, 0, NFLAGS * 4, stream);
     if (e != hipSuccess) return e;
     if (t.n)
         hipLaunchKernelGGL(coarse_rows_check_kernel, dim3(cg_vector_grid(t.n)), dim3(RB), 0, stream, t.n, (uint32_t)t.ncoarse, t.ptr, t.cols,
-                           t.vals, s.counts, s.flags);
-    e = hipMemcpyAsync(h, s.flags, NFLAGS * 4, hipMemcpyDeviceToHost, stream);
+                           t.vals, counts, flags);
+    e = hipMemcpyAsync(h, flags, NFLAGS * 4, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e == hipSuccess) e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -589,14 +606,22 @@ double *coarse_restrict(hipStream_t stream, const CoarseTable &t, const CoarseSi
     return s.vec;
 }
 
-void coarse_correct(hipStream_t stream, const CoarseTable &t, const CoarseSizes &sz, const double *factor, void *scratch, int accumulate,
-                    const double *r, double *z, double *part_rz)
+const double *coarse_solve(hipStream_t stream, const CoarseTable &t, const CoarseSizes &sz, const double *factor, void *scratch)
 {
     const uint32_t nc = (uint32_t)t.ncoarse;
     const Scratch s = scratch_parts(scratch, t.n, nc, (size_t)sz.entries, nullptr);
     double *rc = s.vec, *tt = s.vec + nc, *u = s.vec + 2 * (size_t)nc;
     hipLaunchKernelGGL(coarse_lower_kernel, dim3((nc + RB / 64 - 1) / (RB / 64)), dim3(RB), 0, stream, nc, factor, rc, tt);
     hipLaunchKernelGGL(coarse_upper_kernel, dim3((nc + 63) / 64), dim3(RB), 0, stream, nc, factor, tt, u);
+    return u;
+}
+
+void coarse_correct(hipStream_t stream, const CoarseTable &t, const CoarseSizes &sz, const double *factor, void *scratch, int accumulate,
+                    const double *r, double *z, double *part_rz)
+{
+    const uint32_t nc = (uint32_t)t.ncoarse;
+    const Scratch s = scratch_parts(scratch, t.n, nc, (size_t)sz.entries, nullptr);
+    const double *u = coarse_solve(stream, t, sz, factor, scratch);
     hipLaunchKernelGGL(coarse_prolong_kernel, dim3(cg_vector_grid(t.n)), dim3(RB), 0, stream, t.n, t.ptr, t.cols, t.vals, u, accumulate, r, z,
                        part_rz);
 }
@@ -873,8 +898,8 @@ __global__ __launch_bounds__(SCAN_BLOCK) void coarse_fill_kernel(Mesh m, uint32_
 
 // the table of either numbering: the columns (by side: the used ones, scanned), the entries (counted, scanned), the fill
 template <class Mesh>
-hipError_t coarse_table(hipStream_t stream, const Mesh &m, int fbs, int H, uint64_t *ncoarse, uint64_t *entries, int64_t *ptr,
-                        int32_t *cols, double *vals)
+hipError_t coarse_table(hipStream_t stream, const Mesh &m, int fbs, int H, uint64_t max_columns, uint64_t *ncoarse, uint64_t *entries,
+                        int64_t *ptr, int32_t *cols, double *vals)
 {
     *ncoarse = 0;
     *entries = 0;
@@ -907,7 +932,7 @@ hipError_t coarse_table(hipStream_t stream, const Mesh &m, int fbs, int H, uint6
     hipLaunchKernelGGL((coarse_count_kernel<Mesh>), dim3(nblk), dim3(SCAN_BLOCK), 0, stream, m, nfaces, H, fbs, blk);
     if (!tmp.ok(scan_block_counts(stream, nblk, blk, &total))) return tmp.error();
     *entries = total;
-    if (ptr == nullptr || *ncoarse < 1 || *ncoarse > (uint64_t)COARSE_MAX_NODES) return hipSuccess;
+    if (ptr == nullptr || *ncoarse < 1 || *ncoarse > max_columns) return hipSuccess;
     const uint64_t nrows = coarse_blocks(m) * fbs;
     hipLaunchKernelGGL((coarse_fill_kernel<Mesh>), dim3(nblk), dim3(SCAN_BLOCK), 0, stream, m, nfaces, H, fbs, nnodes, index, blk, nblk, nrows, ptr,
                        cols, vals);
@@ -917,28 +942,28 @@ hipError_t coarse_table(hipStream_t stream, const Mesh &m, int fbs, int H, uint6
 
 }  // namespace
 
-hipError_t condensed_coarse(hipStream_t stream, const CoarseMesh &m, int fbs, int H, uint64_t *ncoarse, uint64_t *entries, int64_t *ptr,
-                            int32_t *cols, double *vals)
+hipError_t condensed_coarse(hipStream_t stream, const CoarseMesh &m, int fbs, int H, uint64_t max_columns, uint64_t *ncoarse,
+                            uint64_t *entries, int64_t *ptr, int32_t *cols, double *vals)
 {
-    return coarse_table(stream, m, fbs, H, ncoarse, entries, ptr, cols, vals);
+    return coarse_table(stream, m, fbs, H, max_columns, ncoarse, entries, ptr, cols, vals);
 }
 
 hipError_t condensed_rows_coarse(hipStream_t stream, const SlabCoarseMesh &m, int fbs, int H, uint64_t *ncoarse, uint64_t *entries,
                                  int64_t *ptr, int32_t *cols, double *vals)
 {
-    return coarse_table(stream, m, fbs, H, ncoarse, entries, ptr, cols, vals);
+    return coarse_table(stream, m, fbs, H, (uint64_t)COARSE_MAX_NODES, ncoarse, entries, ptr, cols, vals);
 }
 
-hipError_t interface_condensed_coarse(hipStream_t stream, const IfCoarseMesh &m, int fbs, int H, uint64_t *ncoarse, uint64_t *entries,
-                                      int64_t *ptr, int32_t *cols, double *vals)
+hipError_t interface_condensed_coarse(hipStream_t stream, const IfCoarseMesh &m, int fbs, int H, uint64_t max_columns, uint64_t *ncoarse,
+                                      uint64_t *entries, int64_t *ptr, int32_t *cols, double *vals)
 {
-    return coarse_table(stream, m, fbs, H, ncoarse, entries, ptr, cols, vals);
+    return coarse_table(stream, m, fbs, H, max_columns, ncoarse, entries, ptr, cols, vals);
 }
 
 hipError_t interface_rows_coarse(hipStream_t stream, const IfRowsCoarseMesh &m, int fbs, int H, uint64_t *ncoarse, uint64_t *entries,
                                  int64_t *ptr, int32_t *cols, double *vals)
 {
-    return coarse_table(stream, m, fbs, H, ncoarse, entries, ptr, cols, vals);
+    return coarse_table(stream, m, fbs, H, (uint64_t)COARSE_MAX_NODES, ncoarse, entries, ptr, cols, vals);
 }
 
 }  // namespace pa

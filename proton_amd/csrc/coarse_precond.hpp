@@ -36,13 +36,19 @@ struct CoarseSizes {
 
 // why a table was refused (0 = it was not); where a table breaks several rules the largest code is reported
 enum { COARSE_OK = 0, COARSE_BAD_SIZE = 1, COARSE_BAD_VALUE = 2, COARSE_BAD_ORDER = 3, COARSE_BAD_INDEX = 4, COARSE_BAD_NODES = 5,
-       COARSE_TOO_LARGE = 6, COARSE_W_OVERFLOW = 7 };
+       COARSE_TOO_LARGE = 6, COARSE_W_OVERFLOW = 7, COARSE_BAD_LEVEL_NODES = 8 };
 const char *coarse_refusal_text(int refusal);
 
 // sizes of the table; checks ncoarse and ptr alone (ptr[0] = 0, every row of 0..4 entries).  Waits for the stream.
 hipError_t coarse_query(hipStream_t stream, size_t n, size_t ncoarse, const int64_t *ptr, CoarseSizes *out, int *refusal);
 // the columns and values of a table whose ptr has passed coarse_query: in range, ascending, finite.  Writes scratch only.  Waits.
 hipError_t coarse_validate(hipStream_t stream, const CoarseTable &t, const CoarseSizes &sz, void *scratch, int *refusal);
+// the two checks alone, for a table of up to max_nodes columns (multilevel_precond.hip: a smoothed level has no dense matrix and no
+// COARSE_MAX_NODES).  coarse_check_ptr: ncoarse and ptr as coarse_query, -> ptr[n]; coarse_check_rows: the columns and values as
+// coarse_validate, with counts (ncoarse + 2: the rows that hold a column) and flags (4 int32) the caller's.  Both wait.
+hipError_t coarse_check_ptr(hipStream_t stream, size_t n, size_t ncoarse, size_t max_nodes, const int64_t *ptr, uint64_t *entries,
+                            int *refusal);
+hipError_t coarse_check_rows(hipStream_t stream, const CoarseTable &t, uint32_t *counts, int32_t *flags, int *refusal);
 // P^T, A_c = P^T A P (to coarse_matrix as well if not null), its Cholesky factor and the packed L^-1 of a validated table;
 // *pivot = 0 or j + 1 for the first non-positive pivot j; *refusal: a row of A P beyond COARSE_W_SLOTS columns.  Waits.
 hipError_t coarse_factor(hipStream_t stream, const int64_t *rowptr, const int32_t *colind, const double *values, const CoarseTable &t,
@@ -76,6 +82,9 @@ hipError_t coarse_cholesky(hipStream_t stream, const CoarseTable &t, const Coars
 double *coarse_restrict(hipStream_t stream, const CoarseTable &t, const CoarseSizes &sz, const void *pt, void *scratch, const double *r);
 void coarse_correct(hipStream_t stream, const CoarseTable &t, const CoarseSizes &sz, const double *factor, void *scratch, int accumulate,
                     const double *r, double *z, double *part_rz);
+// coarse_correct without its gather: -> u = L^-T L^-1 (P^T r) (ncoarse doubles in the scratch), for a caller that prolongs several
+// levels in one pass (multilevel_precond.hpp)
+const double *coarse_solve(hipStream_t stream, const CoarseTable &t, const CoarseSizes &sz, const double *factor, void *scratch);
 // rows [first, first + count) of the table as 8 doubles each: four (column as double, value) pairs, padded with column -1
 void coarse_rows_pack(hipStream_t stream, const CoarseTable &t, size_t first, size_t count, double *out);
 // P for the window: need_lo packed rows below the table's own, need_hi above (a row ends at the first pair whose column is no
@@ -94,8 +103,10 @@ struct CoarseMesh {
     const int8_t *face_loc;                // null: one part
     int where;
 };
-hipError_t condensed_coarse(hipStream_t stream, const CoarseMesh &m, int fbs, int H, uint64_t *ncoarse, uint64_t *entries, int64_t *ptr,
-                            int32_t *cols, double *vals);
+// max_columns: the table is written only with 1 to max_columns columns (pa_context_set_coarse_table_cap; the counts are given
+// either way)
+hipError_t condensed_coarse(hipStream_t stream, const CoarseMesh &m, int fbs, int H, uint64_t max_columns, uint64_t *ncoarse,
+                            uint64_t *entries, int64_t *ptr, int32_t *cols, double *vals);
 
 // ---- rows [row_begin, row_end) of that table for a slab of the generator mesh, from the closed forms of structured_mesh.hpp: the
 // slab owns the compressed faces [p0, p1); the columns are the whole mesh's, ptr starts at 0 ----
@@ -116,8 +127,8 @@ struct IfCoarseMesh {
     const uint32_t *face_pts;
     int by_side;
 };
-hipError_t interface_condensed_coarse(hipStream_t stream, const IfCoarseMesh &m, int fbs, int H, uint64_t *ncoarse, uint64_t *entries,
-                                      int64_t *ptr, int32_t *cols, double *vals);
+hipError_t interface_condensed_coarse(hipStream_t stream, const IfCoarseMesh &m, int fbs, int H, uint64_t max_columns, uint64_t *ncoarse,
+                                      uint64_t *entries, int64_t *ptr, int32_t *cols, double *vals);
 
 // ---- rows [row_begin, row_end) of that table for a slab of the interface problem (pa_interface_rows_coarse) ----
 // im: the slab's extended tables (interface_rows.hpp: its own faces and those of the cell row below), extended face f being

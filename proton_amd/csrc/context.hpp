@@ -133,6 +133,8 @@ struct pa_context {
     pa::AsmTables asmb;
     pa::CutState cut;
     pa::RecordBuffer records;
+    // pa_context_set_coarse_table_cap: the columns up to which pa_condensed_coarse / pa_interface_condensed_coarse write a table
+    size_t coarse_table_cap = PA_COARSE_MAX_NODES;
     // pa_context_set_cut_overlap: the cut-cell kernel runs on a side stream next to the uncut cells' kernels
     hipStream_t side = nullptr;
     hipEvent_t ev_main = nullptr, ev_side = nullptr;
@@ -187,9 +189,9 @@ PA_INTERNAL int asm_prepare(pa_context *ctx);
 PA_INTERNAL pa::FaceSystemView face_system_view(const pa_context *ctx);
 
 // capi_solver.hip
-// a coarse table without an interior node or with more than PA_COARSE_MAX_NODES columns: PA_ERR_INVALID_ARG, H and the count in
-// pa_last_error()
-PA_INTERNAL int coarse_count_refused(pa_context *ctx, const char *who, int H, uint64_t ncoarse);
+// a coarse table without an interior node or with more than max_columns columns (PA_COARSE_MAX_NODES, or the context's cap for the
+// whole-mesh builders): PA_ERR_INVALID_ARG, H and the count in pa_last_error()
+PA_INTERNAL int coarse_count_refused(pa_context *ctx, const char *who, int H, uint64_t ncoarse, uint64_t max_columns = PA_COARSE_MAX_NODES);
 
 // capi_cut.hip
 PA_INTERNAL int ensure_cut_lists(pa_context *ctx, int face_deg, int where);

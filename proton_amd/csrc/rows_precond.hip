@@ -20,6 +20,9 @@
 //             factors it.
 //   apply:    patch sum (local), P_r^T r (local), its sum over the ranks, the two packed triangular products (redundant), the
 //             gather added onto the patch sum with the block partials of r . z.
+//   levels:   conjugated_gradient_multilevel adds the smoothed levels of multilevel_precond.hip between the two: the tables judged in
+//             the order patches, levels, exact level, then the matrices in the same order, and an apply whose gathers share one pass
+//             over z.  Without a smoothed level it is the two-level solver itself.  One rank only.
 // Every exit of the row-partitioned solve is collective (solver.hip): a local failure -- a refused table (5), a matrix that is not
 // positive definite (6), a callback (1), HIP (4) -- is a flag behind the next sum, and nobody iterates unless everybody can.
 #include <hip/hip_runtime.h>
@@ -30,6 +33,7 @@
 #include "cg.hpp"
 #include "coarse_precond.hpp"
 #include "device_tmp.hpp"
+#include "multilevel_precond.hpp"
 #include "patch_precond.hpp"
 #include "rows_precond.hpp"
 
@@ -58,6 +62,14 @@ struct TwoLevel {
     // judged.  Returns at the first refusal.  The temporaries are tmp's.
     hipError_t prepare(hipStream_t stream, DeviceTmp &tmp, const int64_t *rowptr, const int32_t *colind, const double *values, bool coarse)
     {
+        const hipError_t e = prepare_patches(stream, tmp, rowptr, colind, values);
+        if (e != hipSuccess || level || !coarse) return e;
+        return prepare_coarse(stream, tmp);
+    }
+
+    // its two halves (the multilevel solver judges its smoothed levels between them)
+    hipError_t prepare_patches(hipStream_t stream, DeviceTmp &tmp, const int64_t *rowptr, const int32_t *colind, const double *values)
+    {
         hipError_t e = hipSuccess;
         if (pt.n) {
             e = patch_query(stream, pt.n, pt.npatches, pt.ptr, &psz, &refusal);
@@ -68,15 +80,18 @@ struct TwoLevel {
             e = patch_factor(stream, rowptr, colind, values, pt, psz, factors, slots, pscratch, info, &refusal, &failed);
             if (e != hipSuccess || refused(1)) return e;
         }
-        if (coarse) {
-            e = coarse_query(stream, ct.n, ct.ncoarse, ct.ptr, &csz, &refusal);
-            if (e != hipSuccess || refused(2)) return e;
-            if (!tmp.alloc(&cpt, (size_t)csz.pt_bytes) || !tmp.alloc(&cfactor, (size_t)csz.factor_doubles) ||
-                !tmp.alloc(&cscratch, (size_t)csz.scratch_bytes))
-                return tmp.error();
-            e = coarse_validate(stream, ct, csz, cscratch, &refusal);
-            if (e != hipSuccess || refused(2)) return e;
-        }
+        return hipSuccess;
+    }
+
+    hipError_t prepare_coarse(hipStream_t stream, DeviceTmp &tmp)
+    {
+        hipError_t e = coarse_query(stream, ct.n, ct.ncoarse, ct.ptr, &csz, &refusal);
+        if (e != hipSuccess || refused(2)) return e;
+        if (!tmp.alloc(&cpt, (size_t)csz.pt_bytes) || !tmp.alloc(&cfactor, (size_t)csz.factor_doubles) ||
+            !tmp.alloc(&cscratch, (size_t)csz.scratch_bytes))
+            return tmp.error();
+        e = coarse_validate(stream, ct, csz, cscratch, &refusal);
+        if (e != hipSuccess || refused(2)) return e;
         return hipSuccess;
     }
 };
@@ -129,6 +144,36 @@ hipError_t conjugated_gradient_two_level(hipStream_t stream, size_t n, const int
     if (iterations) *iterations = iter;
     if (relative_residual) *relative_residual = rr;
     return hipSuccess;
+}
+
+// ---- the additive multilevel form: TwoLevel's patches and exactly solved level with smoothed levels between them -------------------
+struct Multilevel {
+    TwoLevel two;                          // (ct.ncoarse = 0: no exact level)
+    int nlevels = 0;
+    CoarseTable lt[MULTILEVEL_MAX_TABLES];
+    SmoothedSizes lsz[MULTILEVEL_MAX_TABLES];
+    char *lpt[MULTILEVEL_MAX_TABLES], *lscratch[MULTILEVEL_MAX_TABLES];
+    double *ldinv[MULTILEVEL_MAX_TABLES];
+};
+
+// z = M^-1 r: the patch sum, every level's coarse vector (u_l = D_l^-1 P_l^T r, then the exact level's L^-T L^-1 P_c^T r), and one
+// pass over z that adds the gathers in the order levels 0, 1, .., exact and leaves the block partials of r . z
+void multilevel_apply(void *user, hipStream_t stream, const double *r, double *z, double *part_rz)
+{
+    const Multilevel &m = *(const Multilevel *)user;
+    const TwoLevel &l = m.two;
+    patch_apply(stream, l.pt, l.psz, l.factors, l.slots, l.pscratch, r, z, nullptr);
+    ProlongTables tb{};
+    for (int k = 0; k < m.nlevels; ++k) {
+        tb.ptr[tb.count] = m.lt[k].ptr; tb.cols[tb.count] = m.lt[k].cols; tb.vals[tb.count] = m.lt[k].vals;
+        tb.u[tb.count++] = smoothed_restrict(stream, m.lt[k], m.lsz[k], m.lpt[k], m.ldinv[k], m.lscratch[k], r);
+    }
+    if (l.ct.ncoarse) {
+        coarse_restrict(stream, l.ct, l.csz, l.cpt, l.cscratch, r);
+        tb.ptr[tb.count] = l.ct.ptr; tb.cols[tb.count] = l.ct.cols; tb.vals[tb.count] = l.ct.vals;
+        tb.u[tb.count++] = coarse_solve(stream, l.ct, l.csz, l.cfactor, l.cscratch);
+    }
+    multilevel_prolong(stream, l.pt.n, tb, r, z, part_rz);
 }
 
 struct RowsPrecond {
@@ -279,6 +324,81 @@ hipError_t conjugated_gradient_patch_coarse(hipStream_t stream, size_t n, const 
     return conjugated_gradient_two_level(stream, n, rowptr, colind, values, b, x, PatchTable{n, npatches, patch_ptr, patch_rows}, true,
                                          CoarseTable{n, ncoarse, p_ptr, p_cols, p_vals}, convergence_threshold, divergence_threshold,
                                          max_iter, exit_reason, iterations, relative_residual, status, refusal, pivot);
+}
+
+hipError_t conjugated_gradient_multilevel(hipStream_t stream, size_t n, const int64_t *rowptr, const int32_t *colind, const double *values,
+                                          const double *b, double *x, size_t npatches, const int64_t *patch_ptr, const int32_t *patch_rows,
+                                          int nlevels, const CoarseTable *levels, const CoarseTable *exact, double convergence_threshold,
+                                          double divergence_threshold, size_t max_iter, int *exit_reason, size_t *iterations,
+                                          double *relative_residual, MultilevelReport *report)
+{
+    *report = MultilevelReport();
+    const PatchTable pt{n, npatches, patch_ptr, patch_rows};
+    if (nlevels == 0) {                    // the two-level solvers themselves: their launches, their bits
+        const hipError_t e = conjugated_gradient_two_level(stream, n, rowptr, colind, values, b, x, pt, exact != nullptr,
+                                                           exact ? *exact : CoarseTable{}, convergence_threshold, divergence_threshold, max_iter,
+                                                           exit_reason, iterations, relative_residual, &report->status, &report->refusal,
+                                                           &report->pivot);
+        report->level = -1;
+        return e;
+    }
+    size_t iter = 0;
+    int reason = 0;
+    double rr = 0.0;
+    if (n) {
+        DeviceTmp tmp(stream);
+        Multilevel m;
+        TwoLevel &l = m.two;
+        l.pt = pt;
+        l.ct = exact ? *exact : CoarseTable{n, 0, nullptr, nullptr, nullptr};
+        m.nlevels = nlevels;
+        double *z = nullptr;
+        if (!tmp.alloc(&z, n)) return tmp.error();
+        // the tables, in their order: patches, levels, exact
+        hipError_t e = l.prepare_patches(stream, tmp, rowptr, colind, values);
+        if (e != hipSuccess) return e;
+        if (l.level) { report->status = 1; report->refusal = l.refusal; return hipSuccess; }
+        for (int k = 0; k < nlevels; ++k) {
+            m.lt[k] = levels[k];
+            report->level = k;
+            e = smoothed_query(stream, n, levels[k].ncoarse, levels[k].ptr, &m.lsz[k], &report->refusal);
+            if (e != hipSuccess) return e;
+            if (report->refusal) { report->status = 5; return hipSuccess; }
+            if (!tmp.alloc(&m.lpt[k], (size_t)m.lsz[k].pt_bytes) || !tmp.alloc(&m.ldinv[k], (size_t)m.lsz[k].dinv_doubles) ||
+                !tmp.alloc(&m.lscratch[k], (size_t)m.lsz[k].scratch_bytes))
+                return tmp.error();
+            e = smoothed_validate(stream, m.lt[k], m.lsz[k], m.lscratch[k], &report->refusal);
+            if (e != hipSuccess) return e;
+            if (report->refusal) { report->status = 5; return hipSuccess; }
+        }
+        report->level = -1;
+        if (exact) {
+            e = l.prepare_coarse(stream, tmp);
+            if (e != hipSuccess) return e;
+            if (l.level) { report->status = 3; report->refusal = l.refusal; return hipSuccess; }
+        }
+        // the matrices, in the same order.  (Every level's validation left its counts in the level's own scratch.)
+        if (l.failed) { report->status = 2; return hipSuccess; }
+        for (int k = 0; k < nlevels; ++k) {
+            e = smoothed_setup(stream, rowptr, colind, values, m.lt[k], m.lsz[k], m.lpt[k], m.ldinv[k], m.lscratch[k], &report->pivot);
+            if (e != hipSuccess) return e;
+            if (report->pivot) { report->status = 6; report->level = k; return hipSuccess; }
+        }
+        if (exact) {
+            e = coarse_factor(stream, rowptr, colind, values, l.ct, l.csz, l.cpt, l.cfactor, l.cscratch, nullptr, &report->pivot, &report->refusal);
+            if (e != hipSuccess) return e;
+            if (report->refusal) { report->status = 3; return hipSuccess; }
+            if (report->pivot) { report->status = 4; return hipSuccess; }
+        }
+        const CgPreconditioner pre{&m, multilevel_apply, z};
+        e = conjugated_gradient_one_rank(stream, n, CgCsr{rowptr, colind, values, nullptr}, &pre, nullptr, b, x, convergence_threshold,
+                                         divergence_threshold, max_iter, 0, &reason, &iter, &rr);
+        if (e != hipSuccess) return e;
+    }
+    if (exit_reason) *exit_reason = reason;
+    if (iterations) *iterations = iter;
+    if (relative_residual) *relative_residual = rr;
+    return hipSuccess;
 }
 
 hipError_t conjugated_gradient_rows_patch_coarse(hipStream_t stream, const CgTransport *tp, int64_t row_begin, int64_t row_end,

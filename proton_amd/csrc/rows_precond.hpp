@@ -9,6 +9,7 @@
 #include <cstdint>
 
 #include "cg.hpp"
+#include "coarse_precond.hpp"
 
 namespace pa {
 
@@ -27,6 +28,21 @@ hipError_t conjugated_gradient_patch_coarse(hipStream_t stream, size_t n, const 
                                             const double *p_vals, double convergence_threshold, double divergence_threshold,
                                             size_t max_iter, int *exit_reason, size_t *iterations, double *relative_residual, int *status,
                                             int *refusal, int32_t *pivot);
+
+// ---- one rank: z = (patch sum) + the smoothed levels in their order (multilevel_precond.hpp) + (coarse term of `exact`, may be null) ----
+// status: those of conjugated_gradient_patch_coarse, and 5: the table of smoothed level `level` was refused (*refusal), 6: column
+// pivot - 1 of smoothed level `level` has no positive finite d_j.  The order: the patch table, every level's table, the exact
+// table; then a patch, a level, the exact level that is not positive definite.  x is written only with status 0.  nlevels = 0: the
+// call is conjugated_gradient_patch_coarse (exact = null: conjugated_gradient_patch) itself.
+struct MultilevelReport {
+    int status = 0, refusal = 0, level = -1;
+    int32_t pivot = 0;
+};
+hipError_t conjugated_gradient_multilevel(hipStream_t stream, size_t n, const int64_t *rowptr, const int32_t *colind, const double *values,
+                                          const double *b, double *x, size_t npatches, const int64_t *patch_ptr, const int32_t *patch_rows,
+                                          int nlevels, const CoarseTable *levels, const CoarseTable *exact, double convergence_threshold,
+                                          double divergence_threshold, size_t max_iter, int *exit_reason, size_t *iterations,
+                                          double *relative_residual, MultilevelReport *report);
 
 // ---- a row-partitioned system ----
 // what this rank's status 5 or 6 was about: level 1 the patches, 2 the coarse level; refusal: the code of patch_refusal_text /

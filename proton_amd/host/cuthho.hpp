@@ -478,14 +478,24 @@ class interface_assembler {
     // system directly in CSR (pa_interface_condensed_csr_*), pa_conjugated_gradient on it (patches = PA_PATCH_FACE / PA_PATCH_CELL:
     // pa_conjugated_gradient_patch on the table of pa_interface_condensed_patches; with coarse = H > 0 as well:
     // pa_conjugated_gradient_patch_coarse with the table of pa_interface_condensed_coarse, coarse_parts = PA_COARSE_BY_SIDE or
-    // PA_COARSE_ONE) and the cell unknowns recovered (pa_interface_condensed_recover).  Returns the full solution vector in the reference's numbering -- what
+    // PA_COARSE_ONE; with coarse_levels = {H_0, H_1, ..} as well: pa_conjugated_gradient_multilevel with a smoothed level on each of
+    // these tables below the exact one, coarse = 0: no exact level) and the cell unknowns recovered (pa_interface_condensed_recover).  Returns the full solution vector in the reference's numbering -- what
     // conjugated_gradient(LHS, RHS, sol) leaves in `sol` -- for take_local_data; LHS / RHS are left untouched.
+    // (The trailing coarse_levels comes as an overload, not as a default: every call without it is the call of before.)
     std::vector<T> solve_condensed(const Mesh &msh, const params<T> &parms, int rhs_fn, int dirichlet_fn, const cg_params<T> &cgp,
                                    size_t *iterations = nullptr, cg_exit_reason *exit_reason = nullptr, int patches = -1, int coarse = 0,
                                    int coarse_parts = PA_COARSE_BY_SIDE)
     {
+        return solve_condensed(msh, parms, rhs_fn, dirichlet_fn, cgp, iterations, exit_reason, patches, coarse, coarse_parts, std::vector<int>());
+    }
+
+    std::vector<T> solve_condensed(const Mesh &msh, const params<T> &parms, int rhs_fn, int dirichlet_fn, const cg_params<T> &cgp,
+                                   size_t *iterations, cg_exit_reason *exit_reason, int patches, int coarse, int coarse_parts,
+                                   std::vector<int> coarse_levels)
+    {
         if (!msh.preprocessed) throw std::logic_error("cutHHO mesh not preprocessed");
         if (coarse > 0 && patches < 0) throw std::invalid_argument("interface_assembler::solve_condensed: coarse needs patches");
+        proton_amd::coarse_level_set::check(coarse_levels, coarse, patches);
         for (size_t c = 0; c < msh.cells.size(); ++c) {                                  // :1304-1305, as assemble_cut
             if (msh.cell_tags[c] != element_location::ON_INTERFACE) continue;
             for (auto f : proton_amd::face_offsets(msh, msh.cells[c]))
@@ -533,7 +543,21 @@ class interface_assembler {
             proton_amd::device_buffer<int64_t> d_pptr(npatches + 1);
             proton_amd::device_buffer<int32_t> d_prows(entries + 1);
             dev.check(pa_interface_condensed_patches(dev.ctx(), fd, patches, d_pptr.get(), d_prows.get()), "pa_interface_condensed_patches");
-            if (coarse > 0) {
+            if (!coarse_levels.empty()) {
+                // ... and the additive multilevel form: smoothed levels below the exact one, all in the parts of coarse_parts
+                const proton_amd::coarse_level_set ls(
+                    nF, coarse_levels, coarse,
+                    [&](int H, size_t *nc, size_t *ne) {
+                        dev.check(pa_interface_condensed_coarse_query(dev.ctx(), fd, H, coarse_parts, nc, ne), "pa_interface_condensed_coarse_query");
+                    },
+                    [&](int H, int64_t *p, int32_t *c, double *v) {
+                        dev.check(pa_interface_condensed_coarse(dev.ctx(), fd, H, coarse_parts, p, c, v), "pa_interface_condensed_coarse");
+                    });
+                dev.check(pa_conjugated_gradient_multilevel(dev.ctx(), nF, d_rowptr.get(), d_colind.get(), d_values.get(), d_b.get(), d_xF.get(),
+                                                            npatches, d_pptr.get(), d_prows.get(), ls.nlevels(), ls.levels(), ls.exact(),
+                                                            cgp.convergence_threshold, cgp.divergence_threshold, cgp.max_iter, &reason, &iters,
+                                                            &rr), "pa_conjugated_gradient_multilevel");
+            } else if (coarse > 0) {
                 // ... and the Galerkin coarse level: bilinear hats on every coarse-th mesh line, whole or split by side of the interface
                 size_t ncoarse = 0, centries = 0;
                 dev.check(pa_interface_condensed_coarse_query(dev.ctx(), fd, coarse, coarse_parts, &ncoarse, &centries),

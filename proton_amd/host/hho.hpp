@@ -180,6 +180,59 @@ class device_buffer {
     }
 };
 
+// The tables of pa_conjugated_gradient_multilevel for a level set: a smoothed level on every H of `levels` (each dividing the next,
+// the last dividing `coarse`: nested hat spaces, else std::invalid_argument before any device call) and the exact level on
+// `coarse` (0: none).  query(H, &ncoarse, &entries) and build(H, ptr, cols, vals) are the two entries of a table builder
+// (pa_condensed_coarse, pa_interface_condensed_coarse); the context's table cap is raised for the smoothed levels' tables and
+// put back to its default.
+class coarse_level_set {
+    std::vector<device_buffer<int64_t>> ptr_;
+    std::vector<device_buffer<int32_t>> cols_;
+    std::vector<device_buffer<double>> vals_;
+    std::vector<pa_coarse_table> tables_;
+    bool exact_ = false;
+
+    template <typename Query, typename Build>
+    void add(size_t nrows, int H, Query query, Build build)
+    {
+        size_t ncoarse = 0, entries = 0;
+        query(H, &ncoarse, &entries);
+        ptr_.emplace_back(nrows + 1); cols_.emplace_back(entries + 1); vals_.emplace_back(entries + 1);
+        build(H, ptr_.back().get(), cols_.back().get(), vals_.back().get());
+        tables_.push_back(pa_coarse_table{ncoarse, ptr_.back().get(), cols_.back().get(), vals_.back().get()});
+    }
+
+  public:
+    static void check(const std::vector<int> &levels, int coarse, int patches)
+    {
+        if (levels.empty()) return;
+        if (patches < 0) throw std::invalid_argument("coarse_levels needs patches");
+        if (levels.size() > (size_t)PA_MULTILEVEL_MAX_LEVELS) throw std::invalid_argument("coarse_levels: at most PA_MULTILEVEL_MAX_LEVELS levels");
+        for (size_t k = 0; k < levels.size(); ++k) {
+            const int next = k + 1 < levels.size() ? levels[k + 1] : coarse;
+            if (levels[k] < 1 || (next > 0 && next % levels[k] != 0))
+                throw std::invalid_argument("coarse_levels: every H must divide the next one and the last must divide coarse");
+        }
+    }
+    template <typename Query, typename Build>
+    coarse_level_set(size_t nrows, const std::vector<int> &levels, int coarse, Query query, Build build)
+    {
+        auto &dev = device::instance();
+        dev.check(pa_context_set_coarse_table_cap(dev.ctx(), PA_SMOOTHED_MAX_NODES), "pa_context_set_coarse_table_cap");
+        try {
+            for (int H : levels) add(nrows, H, query, build);
+        } catch (...) {
+            pa_context_set_coarse_table_cap(dev.ctx(), 0);
+            throw;
+        }
+        dev.check(pa_context_set_coarse_table_cap(dev.ctx(), 0), "pa_context_set_coarse_table_cap");
+        if (coarse > 0) { add(nrows, coarse, query, build); exact_ = true; }
+    }
+    size_t nlevels() const { return tables_.size() - (exact_ ? 1 : 0); }
+    const pa_coarse_table *levels() const { return tables_.data(); }
+    const pa_coarse_table *exact() const { return exact_ ? &tables_.back() : nullptr; }
+};
+
 // column-major dense matrix (vectors are n x 1)
 template <typename T>
 class dense_matrix {
@@ -1096,16 +1149,19 @@ class assembler {
     // (pa_fictdom_condensed_ops_batch: cut cells in double-double), the face-only system directly in CSR (pa_condensed_csr_*),
     // pa_conjugated_gradient on it (patches = PA_PATCH_FACE / PA_PATCH_CELL: pa_conjugated_gradient_patch on the table of
     // pa_condensed_patches; with coarse = H > 0 as well: pa_conjugated_gradient_patch_coarse with the table of pa_condensed_coarse,
-    // every hat split by side of the interface) and the cell unknowns recovered (pa_fictdom_condensed_recover).  Returns the full solution
+    // every hat split by side of the interface; with coarse_levels = {H_0, H_1, ..} as well: pa_conjugated_gradient_multilevel with a
+    // smoothed level on each of these tables below the exact one, coarse = 0: no exact level -- proton_amd::coarse_level_set) and the
+    // cell unknowns recovered (pa_fictdom_condensed_recover).  Returns the full solution
     // vector in the reference's numbering -- what solver.solve(RHS) leaves in `sol` -- for take_local_data; LHS / RHS are left
     // untouched.
     template <typename LevelSet, typename Location>
     std::vector<T> solve_condensed_fictdom(const Mesh &msh, const LevelSet & /*level_set_function*/, Location where, int rhs_fn, int dirichlet_fn,
                                            const cg_params<T> &cgp, size_t *iterations = nullptr, cg_exit_reason *exit_reason = nullptr,
-                                           int patches = -1, int coarse = 0)
+                                           int patches = -1, int coarse = 0, std::vector<int> coarse_levels = {})
     {
         if (!msh.preprocessed) throw std::logic_error("cutHHO mesh not preprocessed");
         if (coarse > 0 && patches < 0) throw std::invalid_argument("solve_condensed_fictdom: coarse needs patches");
+        proton_amd::coarse_level_set::check(coarse_levels, coarse, patches);
         auto &dev = proton_amd::device::instance();
         pa_sizes sz;
         dev.check(pa_sizes_for(di.c_abi(), PA_QUAD_FAN, &sz), "pa_sizes_for");
@@ -1145,7 +1201,21 @@ class assembler {
             proton_amd::device_buffer<int64_t> d_pptr(npatches + 1);
             proton_amd::device_buffer<int32_t> d_prows(entries + 1);
             dev.check(pa_condensed_patches(dev.ctx(), di.c_abi(), patches, d_pptr.get(), d_prows.get()), "pa_condensed_patches");
-            if (coarse > 0) {
+            if (!coarse_levels.empty()) {
+                // ... and the additive multilevel form: smoothed levels below the exact one, all split by side of the interface
+                const proton_amd::coarse_level_set ls(
+                    nF, coarse_levels, coarse,
+                    [&](int H, size_t *nc, size_t *ne) {
+                        dev.check(pa_condensed_coarse_query(dev.ctx(), di.c_abi(), H, PA_COARSE_BY_SIDE, (int)where, nc, ne), "pa_condensed_coarse_query");
+                    },
+                    [&](int H, int64_t *p, int32_t *c, double *v) {
+                        dev.check(pa_condensed_coarse(dev.ctx(), di.c_abi(), H, PA_COARSE_BY_SIDE, (int)where, p, c, v), "pa_condensed_coarse");
+                    });
+                dev.check(pa_conjugated_gradient_multilevel(dev.ctx(), nF, d_rowptr.get(), d_colind.get(), d_values.get(), d_b.get(), d_xF.get(),
+                                                            npatches, d_pptr.get(), d_prows.get(), ls.nlevels(), ls.levels(), ls.exact(),
+                                                            cgp.convergence_threshold, cgp.divergence_threshold, cgp.max_iter, &reason, &iters,
+                                                            &rr), "pa_conjugated_gradient_multilevel");
+            } else if (coarse > 0) {
                 // ... and the Galerkin coarse level: bilinear hats on every coarse-th mesh line, split by side of the interface
                 size_t ncoarse = 0, centries = 0;
                 dev.check(pa_condensed_coarse_query(dev.ctx(), di.c_abi(), coarse, PA_COARSE_BY_SIDE, (int)where, &ncoarse, &centries),
